@@ -154,6 +154,64 @@ def cplex_baseline(lp_files, gap, time_limit, budget_s=30.0):
                        % (found[1], tried, gap, time_limit, solved, tsolve))
 
 
+DUMP_LIMIT = 64 << 20   # bytes of --dump-outputs in all
+DUMP_NODES = 100000     # --dump-outputs: the largest branch-and-bound tree whose result is written
+
+
+def dump_outputs(path, P, ws, sts, seeds):
+    """--dump-outputs: what the caller of solve_batch() holds for the queue of the last timed step after main() has drained that queue once more
+    as a stream of its own (why: see there), one array per file with the instance as the leading axis: `status` (the OptimizationStatus
+    solve_batch returned), `solution_status` / `objective` / `best_bound` / `gap` of getSolutionProperties() (float64), every member of
+    getRawResults() (trajectories float64; binaries and slacks float32, the reference's 9999999 for "not set" kept).  `seed` names the instances,
+    `instance` their place in the step's queue.  Written: the instances whose tree stayed within DUMP_NODES nodes - on the bench's workload they end
+    within a second of the start of that stream, and no time limit has run out by then, so their search never met a decision taken by the clock; the larger trees
+    (measured: 10 to 14 of 2560) are the ones the 10 s limit retires or that live beside such a retirement, and what they return differs from run
+    to run.  An instance that was not solved at all (no device) is written with NaN in every result member.  More than DUMP_LIMIT: a fixed sample
+    of the queue (seeded, sorted), drawn before anything is solved.  Left out on purpose: times, node and iteration counts."""
+    import ctypes
+    from planner_miqp_amd.ctypes_types import _RES_D, _RES_I
+    os.makedirs(path, exist_ok=True)
+    n = len(ws)
+    if n == 0:
+        raise SystemExit("--dump-outputs: the last timed step has no instance on this rank")
+    L = P.load_library()
+    d = (ctypes.c_int * 6)()
+    if L.miqp_solver_get_dims(ws[0]._h, d) != 0:
+        raise SystemExit("--dump-outputs: the first instance of the last timed step has no dimensions")
+    shape = P.RawResults(*list(d))
+    members = [(m, np.float64) for m in _RES_D + ["slackvars_real"]] + [(m, np.float32) for m in _RES_I]
+    per = 7 * 8 + sum(getattr(shape, m).size * np.dtype(t).itemsize for m, t in members)
+    pick = np.arange(n)
+    if n * per > DUMP_LIMIT:
+        pick = np.sort(np.random.Generator(np.random.MT19937(0)).choice(n, DUMP_LIMIT // per, replace=False))
+    prs = {k: ws[k].getSolutionProperties() for k in pick}
+    solved = lambda k: sts[k] == P.OptimizationStatus.SUCCESS
+    large = [int(k) for k in pick if solved(k) and prs[k].nodes > DUMP_NODES]
+    pick = np.array([k for k in pick if not (solved(k) and prs[k].nodes > DUMP_NODES)], dtype=np.int64)
+    m_ = len(pick)
+    out = dict(instance=pick.astype(np.float64), seed=np.array([seeds[k] for k in pick], dtype=np.float64),
+               status=np.array([int(sts[k]) for k in pick], dtype=np.float64))
+    for key in ("solution_status", "objective", "best_bound", "gap"):
+        out[key] = np.full(m_, np.nan)
+    for m, t in members:
+        out[m] = np.full((m_,) + getattr(shape, m).shape, np.nan, dtype=t)
+    ends = []
+    for j, k in enumerate(pick):
+        if not solved(k):
+            continue
+        pr = prs[k]; res = ws[k].getRawResults()
+        ends.append(ws[k].lastAdmission() + pr.time)
+        out["solution_status"][j] = pr.status; out["objective"][j] = pr.objective; out["best_bound"][j] = pr.best_bound; out["gap"][j] = pr.gap
+        for m, t in members:
+            out[m][j] = getattr(res, m)   # (an instance of another shape than the first of its step: numpy refuses, loudly)
+    out = {key: v for key, v in out.items() if v.size}   # (no obstacles, one car: members without an element are not written)
+    for key, v in out.items():
+        np.save(os.path.join(path, key + ".npy"), v)
+    return dict(dir=path, instances=int(m_), of=int(n), bytes=int(sum(v.nbytes for v in out.values())), arrays=sorted(out),
+                left_out_larger_than_nodes=DUMP_NODES, left_out=len(large), left_out_seeds=[int(seeds[k]) for k in large[:64]],
+                last_written_instance_ended_s=(float(max(ends)) if ends else None))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -173,6 +231,11 @@ def main():
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--long-extras", action="store_true", help="also the in-flight sweep (256 / 512 in flight at the reference's 10 s limit; a minute more)")
     ap.add_argument("--no-extras", action="store_true", help="skip the legs behind the timed region (all-proven rate, in-flight sweep, one-batch control); they never enter `value`")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="behind the timed steps: drain the queue of the LAST timed step once more through the timed call, as a stream of its own (rank 0), and write "
+                    "what it returns as DIR/<name>.npy - status, objective, bound and gap, every member of the RawResults records; float64 / float32, at most 64 MB in all (beyond that a fixed seeded "
+                    "sample of the queue). The instances are a function of the arguments alone (seeded generator) and a stream of its own meets no decision of the wall clock before its first instance "
+                    "runs out of time, so two runs write the same arrays and two builds can be compared output for output; the few instances with a tree beyond 100 000 nodes - the ones the time limit "
+                    "retires, and their neighbours - are left out and counted in the result line")
     ap.add_argument("--dump-lp", default=None, metavar="DIR", help="write the raw big-M model of every instance of the first timed step as CPLEX .lp (miqp_solver_export_lp) so that a licence holder can fill in the CPLEX column")
     a = ap.parse_args()
 
@@ -332,6 +395,19 @@ def main():
     def pct(v):
         return dict(p50=float(np.percentile(v, 50)), p95=float(np.percentile(v, 95)), p99=float(np.percentile(v, 99)), max=float(max(v))) if v else None
 
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        # What the timed stream returned for its last queue cannot be compared between two runs: an instance is retired by the wall clock, and from the first
+        # retirement on (10 s into the stream) the clock decides who shares a round with whom - in a 20-step stream the last queue is admitted after that, and
+        # 190 of its 2560 instances returned another incumbent within the gap in a second run.  So the queue of the last timed step goes through the timed call
+        # once more, behind the timed region, as a stream of its own: same handles, same settings, same instances in flight.  Such a stream is free of the clock
+        # until its first instance runs out of time, and dump_outputs() writes the instances that were done long before (two runs: bit for bit the same)
+        lws = batches[a.warmup + a.steps - 1][1]
+        lsts = P.solve_batch(lws, inflight=infl, prepared=True) if lws else []
+        P.materialize_results(lws)
+        dumped = dump_outputs(a.dump_outputs, P, lws, lsts, seeds_of(a.warmup + a.steps - 1))
+        dumped["first_time_limit_could_run_out_s"] = float(min(w.lastAdmission() for w in lws) + a.time_limit)
+
     extras = None
     if rank == 0 and world == 1 and not a.no_extras and not a.no_stream and a.total <= 0:
         # Legs behind the timed region (rank 0, single GPU; they re-solve instances of the timed queues, results are discarded):
@@ -448,6 +524,8 @@ def main():
             out["all_proven"] = extras["time_to_prove_all"]   # (alias: the key of rounds <= 4 for the same leg - 2048 instances at 256 in flight, limit 60 s)
             out["in_flight_sweep"] = extras["in_flight_sweep"]; out["one_batch_control"] = extras["one_batch_control"]
         out["proven_share"] = tot_solved / max(1, tot_att)
+        if dumped:
+            out["dumped_outputs"] = dumped
         if not a.no_cpu and world == 1:
             out["cpu_baseline"] = cpu_baseline(batches[a.warmup][0], a.gap, a.time_limit)
             cpx = cplex_baseline(lp_files, a.gap, a.time_limit) if lp_files else None

@@ -383,3 +383,52 @@ def test_loading_the_library_asks_for_eight_hardware_queues_unless_the_caller_ch
     code2 = "import os, sys; sys.path.insert(0, %r); os.environ.pop('GPU_MAX_HW_QUEUES', None); import planner_miqp_amd.wrapper; print(os.environ.get('GPU_MAX_HW_QUEUES'))" % root
     out = subprocess.run([sys.executable, "-c", code2], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and out.stdout.strip() == "8", (out.stdout, out.stderr[-300:])
+
+
+def _bench_dump(tmp, extra):
+    import json
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "mini", "--batch", "3", "--queue-factor", "2", "--warmup", "1",
+                        "--no-cpu", "--no-extras", "--time-limit", "1", "--dump-outputs", str(tmp)] + extra, capture_output=True, text=True, timeout=600)
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert r.returncode == 0 and len(lines) == 1, r.stdout[-2000:] + r.stderr[-2000:]
+    return json.loads(lines[0]), {f[:-4]: np.load(os.path.join(str(tmp), f)) for f in sorted(os.listdir(str(tmp)))}
+
+
+def test_bench_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """`bench.py --dump-outputs DIR`: one .npy per member of what the timed call returns for the queue of the LAST timed step (drained once more
+    behind the timed region, as a stream of its own), float32 / float64, instance first; the instances depend on the arguments alone (the same seeds in a second run, other seeds with another --steps);
+    `--steps` sets the number of timed steps and the line carries `ms_per_step`.  No GPU here: every status is the loud failure and every
+    result member NaN - the file set, shapes and types are the real ones."""
+    o, d = _bench_dump(tmp_path / "a", ["--steps", "2"])
+    assert o["steps"] == 2 and o["ms_per_step"] > 0 and o["config"]["instances_attempted"] == 12
+    assert o["dumped_outputs"]["instances"] == 6 and o["dumped_outputs"]["bytes"] == sum(v.nbytes for v in d.values()) <= 64 << 20
+    assert sorted(o["dumped_outputs"]["arrays"]) == sorted(d) and o["dumped_outputs"]["of"] == 6 and o["dumped_outputs"]["left_out"] == 0
+    assert {"status", "solution_status", "objective", "best_bound", "gap", "seed", "instance", "pos_x", "vel_y", "u_x", "active_region", "car2car_collision", "slackvars_real"} <= set(d)
+    assert "deltacc" not in d                                         # (mini has no obstacle: nothing to write)
+    assert all(v.dtype in (np.float32, np.float64) and v.shape[0] == 6 for v in d.values())
+    assert d["pos_x"].shape == (6, 2, 8) and d["active_region"].shape == (6, 2, 8, 32) and d["active_region"].dtype == np.float32
+    assert list(d["seed"]) == list(range(12, 18)) and list(d["instance"]) == list(range(6))   # warm-up 0..5, first timed step 6..11, the last one 12..17
+    assert np.all(d["status"] == int(P.OptimizationStatus.FAILED_SEG_FAULT)) and np.all(np.isnan(d["objective"])) and np.all(np.isnan(d["pos_x"]))
+    o2, d2 = _bench_dump(tmp_path / "b", ["--steps", "2"])
+    assert sorted(d2) == sorted(d) and all(np.array_equal(d[k], d2[k], equal_nan=True) for k in d)
+    o3, d3 = _bench_dump(tmp_path / "c", ["--steps", "3"])
+    assert o3["steps"] == 3 and o3["config"]["instances_attempted"] == 18 and list(d3["seed"]) == list(range(18, 24))
+
+
+def test_bench_dump_outputs_samples_beyond_its_limit(lib, tmp_path, monkeypatch):
+    """more than the limit: a fixed sample of the instances - the same in every run, sorted, named by `instance` and `seed`"""
+    import bench
+    ws = []
+    for sd in range(9):
+        w = P.CplexWrapper(); w.resetParameters(synthetic.generate("mini", sd)); ws.append(w)
+    P.prepare_batch(ws)
+    sts = [P.OptimizationStatus.FAILED_SEG_FAULT] * 9
+    full = bench.dump_outputs(str(tmp_path / "full"), P, ws, sts, list(range(100, 109)))
+    assert full["instances"] == 9 and full["of"] == 9
+    monkeypatch.setattr(bench, "DUMP_LIMIT", full["bytes"] // 2)
+    a = bench.dump_outputs(str(tmp_path / "a"), P, ws, sts, list(range(100, 109)))
+    b = bench.dump_outputs(str(tmp_path / "b"), P, ws, sts, list(range(100, 109)))
+    assert a["instances"] == 4 and a["of"] == 9 and a["bytes"] <= full["bytes"] // 2
+    ia, ib = np.load(str(tmp_path / "a" / "instance.npy")), np.load(str(tmp_path / "b" / "instance.npy"))
+    assert np.array_equal(ia, ib) and np.all(np.diff(ia) > 0) and np.array_equal(np.load(str(tmp_path / "a" / "seed.npy")), 100 + ia)
+    assert np.load(str(tmp_path / "a" / "pos_x.npy")).shape == (4, 2, 8)

@@ -1440,3 +1440,57 @@ def test_the_launch_split_of_a_round_is_in_use_and_the_leaves_of_the_local_searc
     print("larger block: %d nodes, %d local-search leaves at %.1f steps" % (big, leaves, lsteps))
     assert big > 0 and leaves > 100, (big, leaves)
     assert lsteps < 30.0, lsteps   # (a cold leaf takes the size of its active set + 4 steps: 57 on average on this instance)
+
+
+def test_bench_dump_outputs_are_the_same_in_two_runs(tmp_path):
+    """`bench.py --dump-outputs` twice with the same arguments (each a fresh process): the same instances, every one of the last timed step
+    proven and written, and the two runs write the same arrays (to rounding: the queue is drained as a stream of its own, which meets no
+    decision of the wall clock); bound <= objective within the gap, one active region per car and step"""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--config", "mini", "--batch", "8", "--queue-factor", "2", "--steps", "2", "--warmup", "1",
+                            "--no-cpu", "--no-extras", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert r.returncode == 0 and len(lines) == 1, r.stdout[-2000:] + r.stderr[-2000:]
+        o = json.loads(lines[0])
+        assert o["steps"] == 2 and o["ms_per_step"] > 0 and o["proven_share"] == 1.0 and o["config"]["instances_attempted"] == 32
+        du = o["dumped_outputs"]
+        assert du["instances"] == 16 and du["of"] == 16 and du["left_out"] == 0 and du["last_written_instance_ended_s"] < du["first_time_limit_could_run_out_s"]
+        runs.append({f[:-4]: np.load(str(d / f)) for f in sorted(os.listdir(str(d)))})
+    a, b = runs
+    assert sorted(a) == sorted(b) and list(a["seed"]) == list(range(32, 48))
+    for x in (a, b):
+        assert np.all(x["status"] == int(P.OptimizationStatus.SUCCESS)) and np.all(np.isin(x["solution_status"], (101, 102)))
+        assert all(np.all(np.isfinite(v)) for v in x.values())
+        assert np.all(x["best_bound"] <= x["objective"] + 1e-9) and np.all(x["gap"] <= 0.01 + 1e-12)
+        assert np.all(x["active_region"].sum(-1) == 1)
+    for n in a:
+        assert np.allclose(a[n], b[n], rtol=1e-9, atol=1e-9), n
+
+
+def test_bench_dump_outputs_leaves_out_the_large_trees(tmp_path, monkeypatch):
+    """the instances whose tree went beyond the dump's node limit are not written: they are counted and named, the others keep their place"""
+    import bench
+    seeds = list(range(8))
+    ws = []
+    for sd in seeds:
+        w = P.CplexWrapper(); w.resetParameters(synthetic.generate("mini", sd, gap=0.01)); ws.append(w)
+    sts = P.solve_batch(ws, inflight=4)
+    assert all(st == P.OptimizationStatus.SUCCESS for st in sts)
+    nodes = [w.getSolutionProperties().nodes for w in ws]
+    cut = sorted(nodes)[len(nodes) // 2]
+    assert min(nodes) <= cut < max(nodes), nodes
+    monkeypatch.setattr(bench, "DUMP_NODES", cut)
+    du = bench.dump_outputs(str(tmp_path), P, ws, sts, seeds)
+    keep = [k for k in range(8) if nodes[k] <= cut]
+    assert du["of"] == 8 and du["instances"] == len(keep) and du["left_out"] == 8 - len(keep) and du["left_out_larger_than_nodes"] == cut
+    assert sorted(du["left_out_seeds"]) == [k for k in range(8) if nodes[k] > cut]
+    assert list(np.load(str(tmp_path / "instance.npy"))) == keep and list(np.load(str(tmp_path / "seed.npy"))) == keep
+    obj = np.load(str(tmp_path / "objective.npy")); px = np.load(str(tmp_path / "pos_x.npy"))
+    for j, k in enumerate(keep):
+        assert obj[j] == ws[k].getSolutionProperties().objective and np.array_equal(px[j], ws[k].getRawResults().pos_x)
