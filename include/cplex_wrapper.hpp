@@ -141,6 +141,24 @@ class CplexWrapper {
   }
 
   std::shared_ptr<RawResults> getRawResults() const { return rawResults_; }  // aliasing pointer, overwritten by the next solve
+  // Certificate of the last solution against the raw big-M model, evaluated on the device (miqp_solver_certify; no reference
+  // counterpart - what IloCplex::getQuality answers there): with the real-valued car/car slacks of the solve.  status 1 when
+  // there is no solution; a failed call (no device) gives status -1.
+  miqp_certificate_c certifySolution() {
+    miqp_certificate_c c{}; c.status = -1;
+    if (!h_ || miqp_solver_certify(h_, nullptr, &c) != 0) c.status = -1;
+    return c;
+  }
+  // ... of a record the caller holds (RawResults carries the car/car slacks truncated to int: those are what is checked)
+  miqp_certificate_c certifySolution(std::shared_ptr<RawResults> candidate) {
+    miqp_certificate_c c{}; c.status = -1;
+    if (!h_ || !candidate || candidate->N <= 0 || candidate->NrCars <= 0) return c;
+    Pod p(candidate->NrCars, candidate->N, candidate->NrRegions, candidate->NrEnvironments, candidate->NrObstacles, candidate->MaxLinesObstacles);
+    fillPod(*candidate, p);
+    p.c.slackvars_real = nullptr;
+    if (miqp_solver_certify(h_, &p.c, &c) != 0) c.status = -1;
+    return c;
+  }
   SolutionProperties getSolutionProperties() const { return solutionProperties_; }
   void setDebugOutputPrint(bool v) { print_debug_outputs_ = v; }
   void setDebugOutputFilePath(std::string in) { debugOutputFilePath_ = in; }
@@ -258,6 +276,10 @@ class CplexWrapper {
   void pushWarmstart(const RawResults& w) {
     if (w.N <= 0 || w.NrCars <= 0) return;
     Pod p(w.NrCars, w.N, w.NrRegions, w.NrEnvironments, w.NrObstacles, w.MaxLinesObstacles);
+    fillPod(w, p);
+    miqp_solver_set_warmstart(h_, &p.c, MIQP_WARMSTART_RECEDING_HORIZON);
+  }
+  static void fillPod(const RawResults& w, Pod& p) {
     // every variable of the start travels (initializeWarmstart flattens all 27 arrays, src/cplex_wrapper.cpp:494-639)
     const Eigen::Tensor<double, 2>* d2[12] = {&w.u_x, &w.u_y, &w.pos_x, &w.vel_x, &w.acc_x, &w.pos_y, &w.vel_y, &w.acc_y, &w.pos_x_front_UB, &w.pos_x_front_LB, &w.pos_y_front_UB, &w.pos_y_front_LB};
     for (int k = 0; k < 12; ++k) fromTensor<double, 2>(*d2[k], p.d[k].data());
@@ -270,7 +292,6 @@ class CplexWrapper {
     fromTensor<int, 4>(w.deltacc, p.i[11].data()); fromTensor<int, 5>(w.deltacc_front, p.i[12].data());
     fromTensor<int, 4>(w.car2car_collision, p.i[13].data()); fromTensor<int, 4>(w.slackvars, p.i[14].data());
     fromTensor<int, 3>(w.slackvarsObstacle, p.i[15].data()); fromTensor<int, 4>(w.slackvarsObstacle_front, p.i[16].data());
-    miqp_solver_set_warmstart(h_, &p.c, MIQP_WARMSTART_RECEDING_HORIZON);
   }
 
   std::string modfile_, datfile_;

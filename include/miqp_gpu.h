@@ -272,6 +272,27 @@ int miqp_obstacle_intersects_environment_roi(const double* pieces_xy, const int*
  * into `out` ([C][n_new][N]) by piece id; new pieces and the last step start as 1 */
 int miqp_environment_warmstart(const miqp_raw_results_c* last, miqp_raw_results_c* out, const int* ids_old, int n_old, const int* ids_new, int n_new);
 
+/* Certificate of a delivered record against the raw big-M model of the instance loaded in s (no reference counterpart; what
+ * IloCplex::getQuality(MaxPrimalInfeas / MaxIntInfeas) answers for a CPLEX user).  Every row of the cplexmodel .mod files is generated and
+ * evaluated on the device, from the host instance and the record - not from the solver's incumbent - so the answer is independent of the
+ * branch and bound.  `candidate` NULL: the last solution of the handle (its record is built, or taken when
+ * miqp_solver_materialize_results ran, and kept in the handle).  The car/car slacks are slackvars_real when the record carries
+ * them, else the truncated ints.  It proves primal feasibility and the objective of that record, not optimality or a bound.
+ * Returns 0 (a handle without a solution gives status 1), -1 invalid arguments / no instance, -2 a NULL array in `candidate`,
+ * -3 `candidate` has other sizes than the instance (as miqp_solver_set_warmstart), -4 no HIP device or no kernel image
+ * (miqp_solver_last_error says which): there is no host evaluation.  Holds the device lock of opts.device like a solve;
+ * uses buffers of its own (two staging and two device buffers of at most 48 MB each, cached per device) and leaves the
+ * solver's device context untouched.  Deterministic: the same record gives the same bytes. */
+int miqp_solver_certify(miqp_solver_t* s, const miqp_raw_results_c* candidate, miqp_certificate_c* out);
+/* ... of the last solution of every handle (out[n]); handles may differ in shape.  Records are packed on at most 16 host threads
+ * and uploaded in chunks beside the kernel of the previous chunk; runs on the device of solvers[0] */
+int miqp_solver_certify_batch(miqp_solver_t* const* solvers, int n, miqp_certificate_c* out);
+/* sizeof(miqp_certificate_c) of the built library (binding check) */
+int miqp_gpu_certificate_size(void);
+/* the last certify call of the process: out[0] = seconds of host packing, out[1] = of uploads, out[2] = of kernels (both from
+ * device events, they overlap each other and the packing), out[3] = the whole call */
+int miqp_gpu_certify_last_timing(double* out4);
+
 const char* miqp_gpu_version(void);
 
 #ifdef __cplusplus

@@ -136,6 +136,23 @@ typedef struct miqp_solution_properties_c {
   long long nodes;
 } miqp_solution_properties_c;
 
+/* A-posteriori certificate of one delivered RawResults record against the raw big-M model (miqp_solver_certify): primal
+ * feasibility and objective of the record as the caller holds it.  Row families in the generation order of the cplexmodel .mod files
+ * and of miqp_solver_export_lp: A1 initial conditions, A2 dynamics, A3 global limits, A4 region block, A5 minimum speed /
+ * region change, A6 environment, A7 obstacles (with the soft-obstacle alternative), A8 car/car collision. */
+typedef struct miqp_certificate_c {
+  double max_violation;        /* worst violation over all raw rows: lhs-rhs for <=, rhs-lhs for >=, |lhs-rhs| for = ; >= 0 */
+  double objective;            /* objective_function.mod recomputed from the record: tracking, acc, jerk, obstacle slack, car/car slack */
+  double family_violation[8];  /* the same maximum per row family A1..A8 */
+  double max_int_infeas;       /* distance of the binary members, as delivered, from {0, 1} (ints: 0 unless a member is outside {0, 1};
+                                  members are read saturated to [-128, 127]) */
+  int    worst_family;         /* 1..8, 0 when max_violation == 0 */
+  int    worst_row;            /* 0-based index of the worst row in the raw model's generation order (row c<worst_row+1> of
+                                  miqp_solver_export_lp); ties: lowest index; -1 when max_violation == 0 */
+  int    rows;                 /* rows evaluated; equals out[0] of miqp_solver_raw_sizes */
+  int    status;               /* 0 evaluated; 1 the handle holds no solution (doubles NaN, ints -1) */
+} miqp_certificate_c;
+
 #ifdef __cplusplus
 }
 #endif

@@ -1561,6 +1561,8 @@ bool solve_batch_impl(miqp_solver_t* const* S, int n, int* statuses, const Split
 
 }  // namespace
 
+#include "certify.hip"
+
 // ================================================================================================
 //  C ABI
 // ================================================================================================

@@ -64,6 +64,35 @@ class SolutionPropertiesC(C.Structure):
                 ("best_bound", C.c_double), ("nodes", C.c_longlong)]
 
 
+class CertificateC(C.Structure):
+    """miqp_certificate_c (include/miqp_types.h)"""
+    _fields_ = [("max_violation", C.c_double), ("objective", C.c_double), ("family_violation", C.c_double * 8),
+                ("max_int_infeas", C.c_double), ("worst_family", C.c_int), ("worst_row", C.c_int), ("rows", C.c_int),
+                ("status", C.c_int)]
+
+
+class Certificate:
+    """certificate of one delivered record against the raw big-M model (CplexWrapper.certify): primal feasibility and
+    objective of that record - not optimality, not a bound.  ``status`` 1: the handle held no solution (fields NaN / -1)."""
+    FAMILIES = ("A1 initial conditions", "A2 dynamics", "A3 global limits", "A4 region block", "A5 minimum speed / region change",
+                "A6 environment", "A7 obstacles", "A8 car/car collision")
+
+    def __init__(self, c: CertificateC):
+        self.max_violation = c.max_violation
+        self.objective = c.objective
+        self.family_violation = np.array(list(c.family_violation), dtype=np.float64)
+        self.max_int_infeas = c.max_int_infeas
+        self.worst_family, self.worst_row, self.rows, self.status = c.worst_family, c.worst_row, c.rows, c.status
+        self.raw = bytes(c)   # the struct as the library wrote it
+
+    def __repr__(self):
+        if self.status != 0:
+            return "Certificate(status=%d: no solution)" % self.status
+        fam = self.FAMILIES[self.worst_family - 1] if 1 <= self.worst_family <= 8 else "-"
+        return ("Certificate(max_violation=%.3e, worst_family=%d (%s), worst_row=%d, rows=%d, objective=%.10g, max_int_infeas=%g)"
+                % (self.max_violation, self.worst_family, fam, self.worst_row, self.rows, self.objective, self.max_int_infeas))
+
+
 class SolverOptsC(C.Structure):
     _fields_ = [("precision", C.c_int), ("device", C.c_int), ("nodes_per_round", C.c_int),
                 ("max_open_nodes", C.c_int), ("gap_override", C.c_double), ("verbose", C.c_int)]

@@ -260,7 +260,10 @@ class MiqpPlanner:
     C-API test uses it).  Reference lines are polylines (see reference_trajectory)."""
     EPS = 0.000001   # MiqpPlanner::eps_ (src/miqp_planner.hpp:415)
 
-    def __init__(self, settings=None, mapPieces=None, **wrapper_args):
+    def __init__(self, settings=None, mapPieces=None, certify_tolerance=None, **wrapper_args):
+        """``certify_tolerance``: when set, every successful Plan is certified on the device against the raw big-M model
+        (CplexWrapper.certify) and counts as failed when a raw row is violated by more than the tolerance; None (default):
+        no certificate is computed"""
         from .ctypes_types import ModelParameters
         from .wrapper import CplexWrapper
         S = dict(DefaultSettings()); S.update(settings or {})
@@ -290,6 +293,9 @@ class MiqpPlanner:
             setattr(p, k, np.zeros((0, R)))
         p.initial_region = np.zeros(0, dtype=np.int32); p.possible_region = np.zeros((0, R), dtype=np.int32)
         self.parameters = p
+        self.certify_tolerance = certify_tolerance
+        self.certificate = None   # of the last successful solve (certify_tolerance set)
+        self.lastError = ""       # why the last Plan was turned into a failure by its certificate
         self.egoCarIdx = 0
         self._obstacles_roi = None   # MiqpPlanner::obstacles_roi_: empty until the ego car is updated with obstacle_roi_filter set
         self._refs = []          # per car: (reference line, desired velocity, delta s)
@@ -372,6 +378,13 @@ class MiqpPlanner:
             self.ResetEnvironment(self.CalculateReferenceTrajectoriesLongerHorizon())
         ws = self._ws if (wt != WarmstartType.NO_WARMSTART and self._ws is not None and self._ws.dims == self._dims()) else None
         ok, self.status = plan(self.wrapper, self.parameters, ws, wt if ws is not None else WarmstartType.NO_WARMSTART, timestamp)
+        self.lastError = ""
+        if ok and self.certify_tolerance is not None:
+            self.certificate = cert = self.wrapper.certify()
+            if cert.status != 0 or not cert.max_violation <= self.certify_tolerance:
+                ok = False
+                self.lastError = ("plan rejected by its certificate: raw-model violation %.3e > tolerance %.3e (family A%d, row %d of %d)"
+                                  % (cert.max_violation, self.certify_tolerance, cert.worst_family, cert.worst_row, cert.rows))
         self._ws = None
         if ok and wt != WarmstartType.NO_WARMSTART:
             self._ws = calculate_warmstart(self.GetSolution(), self.parameters.ts, self.parameters.minimum_region_change_speed)

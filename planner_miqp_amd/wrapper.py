@@ -12,7 +12,8 @@ import numpy as np
 # (four concurrent launches per round + the null stream: see miqp_gpu.hip - effective when set before the process's first HIP call)
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
-from .ctypes_types import (ModelParameters, ModelParamsC, RawResults, RawResultsC, SolutionPropertiesC, SolverOptsC, c_double_p)
+from .ctypes_types import (Certificate, CertificateC, ModelParameters, ModelParamsC, RawResults, RawResultsC, SolutionPropertiesC, SolverOptsC,
+                           c_double_p)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -85,6 +86,10 @@ def load_library():
     L.miqp_solver_last_active_set.restype = C.c_int; L.miqp_solver_last_active_set.argtypes = [vp, C.POINTER(C.c_double)]
     L.miqp_solver_last_error.restype = C.c_char_p; L.miqp_solver_last_error.argtypes = [vp]
     L.miqp_solver_last_admission.restype = C.c_int; L.miqp_solver_last_admission.argtypes = [vp, C.POINTER(C.c_double)]
+    L.miqp_solver_certify.restype = C.c_int; L.miqp_solver_certify.argtypes = [vp, C.POINTER(RawResultsC), C.POINTER(CertificateC)]
+    L.miqp_solver_certify_batch.restype = C.c_int; L.miqp_solver_certify_batch.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(CertificateC)]
+    L.miqp_gpu_certificate_size.restype = C.c_int; L.miqp_gpu_certificate_size.argtypes = []
+    L.miqp_gpu_certify_last_timing.restype = C.c_int; L.miqp_gpu_certify_last_timing.argtypes = [C.POINTER(C.c_double)]
     L.miqp_gpu_version.restype = C.c_char_p
     _LIB = L
     return L
@@ -101,7 +106,8 @@ EXPORTED_SYMBOLS = ["miqp_solver_create", "miqp_solver_destroy", "miqp_solver_se
                     "miqp_solver_solve_batch_multi", "miqp_solver_raw_sizes", "miqp_solver_lift_tables", "miqp_reference_trajectory", "miqp_update_car", "miqp_fitting_polynomial_parameters",
                     "miqp_solver_solve_split", "miqp_solver_solve_split_rccl", "miqp_solver_split_roots", "miqp_comm_unique_id",
                     "miqp_comm_init", "miqp_comm_finalize", "miqp_comm_selftest", "miqp_solver_solve_stream", "miqp_solver_materialize_results",
-                    "miqp_initial_pose_check", "miqp_select_environment", "miqp_obstacle_intersects_environment", "miqp_obstacles_roi", "miqp_bark_trajectory", "miqp_obstacle_intersects_environment_roi", "miqp_environment_warmstart"]
+                    "miqp_initial_pose_check", "miqp_select_environment", "miqp_obstacle_intersects_environment", "miqp_obstacles_roi", "miqp_bark_trajectory", "miqp_obstacle_intersects_environment_roi", "miqp_environment_warmstart",
+                    "miqp_solver_certify", "miqp_solver_certify_batch", "miqp_gpu_certificate_size", "miqp_gpu_certify_last_timing"]
 
 
 class OptimizationStatus(enum.IntEnum):  # src/cplex_wrapper.hpp:54-59
@@ -381,6 +387,28 @@ class CplexWrapper:
             return None
         return dict(rows=o[0], bin=o[1], cont=o[2], nnz=o[3])
 
+    def certify(self, candidate: RawResults = None, use_real_slack=True):
+        """Certificate of a record against the raw big-M model of this wrapper's instance, evaluated on the device
+        (miqp_solver_certify).  ``candidate`` None: the last solution of the wrapper, with its real-valued car/car slacks;
+        a RawResults: that record (``use_real_slack`` False: with its int-truncated ``slackvars`` instead of
+        ``slackvars_real``), against the instance the handle holds (that of the last solve; a wrapper that has not
+        solved yet loads its parameters first).  Raises RuntimeError where the library
+        refuses (record of another shape, no device - there is no host evaluation)."""
+        out = CertificateC()
+        if candidate is None:
+            rc = self._L.miqp_solver_certify(self._h, None, C.byref(out))
+        else:
+            d = (C.c_int * 6)()
+            if self._L.miqp_solver_get_dims(self._h, d) != 0 and self._push_inputs() != 0:   # (a loaded instance is kept: loading drops its solution)
+                raise RuntimeError("invalid parameters")
+            cc = candidate.to_c()
+            if not use_real_slack:
+                cc.slackvars_real = None
+            rc = self._L.miqp_solver_certify(self._h, C.byref(cc), C.byref(out))
+        if rc != 0:
+            raise RuntimeError("miqp_solver_certify failed (%d): %s" % (rc, self.lastError()))
+        return Certificate(out)
+
     def lastAdmission(self):
         """seconds after the start of the last batch / stream call at which this instance was admitted to a slot"""
         o = (C.c_double * 1)()
@@ -431,6 +459,28 @@ def solve_batch(wrappers, gpus=None, inflight=None, prepared=False):
         return [OptimizationStatus.FAILED_SEG_FAULT] * n
     # (-2: the call failed as a whole or in part - the library has set every status: FAILED_SEG_FAULT for the instances it did not run)
     return [w._collect(st[k], lazy=True) for k, w in enumerate(wrappers)]
+
+
+def certify_batch(wrappers):
+    """certificates of the last solutions of ``wrappers`` in one call (miqp_solver_certify_batch): a list of Certificate, entry k
+    with status 1 when wrapper k holds no solution.  The wrappers may differ in shape."""
+    L = load_library()
+    n = len(wrappers)
+    if n == 0:
+        return []
+    hs = (C.c_void_p * n)(*[w._h for w in wrappers])
+    out = (CertificateC * n)()
+    rc = L.miqp_solver_certify_batch(hs, n, out)
+    if rc != 0:
+        raise RuntimeError("miqp_solver_certify_batch failed (%d): %s" % (rc, wrappers[0].lastError()))
+    return [Certificate(out[k]) for k in range(n)]
+
+
+def certify_last_timing():
+    """seconds of the last certify call of the process: dict(pack_s, upload_s, kernel_s, call_s)"""
+    t = (C.c_double * 4)()
+    load_library().miqp_gpu_certify_last_timing(t)
+    return dict(pack_s=t[0], upload_s=t[1], kernel_s=t[2], call_s=t[3])
 
 
 def materialize_results(wrappers, threads=0):
