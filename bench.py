@@ -9,6 +9,11 @@ of the K timed steps (max over ranks).  `--no-stream` restores the semantics of 
 at once, a step ends when its last instance does).  `--total T` is the strong-scaling mode of BASELINE config 4: a fixed
 set of T instances per step (seeds 1000 ...) split b mod G over the ranks.
 Inputs are generated and handed to the solver handles before the timed region; the solve call uploads ~22 KB per instance.
+
+A plain run sets up, warms up, times its steps, writes `--dump-outputs` if asked and prints the result line: what the headline
+figure needs, and what falls out of the timed stream's own counters (latencies, roofline of the dominant kernel).  Everything that
+takes runs of its own - the legs behind the timed region (limit-lifted stream, time to prove all, in-flight sweep, one-batch
+control), the CPU baseline and the CPLEX column - runs with `--full` only; `--no-extras` / `--no-cpu` narrow a full run.
 """
 import argparse
 import json
@@ -16,6 +21,8 @@ import numpy as np
 import os
 import sys
 import time
+
+T_START = time.time()   # (the line's `run_seconds` counts from here: the interpreter's own start is not in it)
 
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")   # before anything initialises HIP: a round's four launches and the null stream each get a hardware queue (miqp_gpu.hip)
 
@@ -228,9 +235,12 @@ def main():
     ap.add_argument("--config", default="cfg3")
     ap.add_argument("--gap", type=float, default=0.01)
     ap.add_argument("--time-limit", type=float, default=10.0, help="max_solution_time per instance (reference default 10 s)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--long-extras", action="store_true", help="also the in-flight sweep (256 / 512 in flight at the reference's 10 s limit; a minute more)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the legs behind the timed region (all-proven rate, in-flight sweep, one-batch control); they never enter `value`")
+    ap.add_argument("--full", action="store_true", help="also what takes runs of its own behind the timed region and never enters `value`: the legs on rank 0 (the timed stream again with the limit lifted to "
+                    "60 s, time to prove all of a 2048-instance queue, one-batch control), the CPU baseline and, with --dump-lp on a host that has CPLEX, the CPLEX column; minutes more. "
+                    "Without it: set-up, warm-up, the timed steps, --dump-outputs, the result line")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline and the CPLEX column")
+    ap.add_argument("--long-extras", action="store_true", help="with --full: also the in-flight sweep (256 / 512 in flight at the reference's 10 s limit; a minute more)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the legs behind the timed region (all-proven rate, in-flight sweep, one-batch control)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="behind the timed steps: drain the queue of the LAST timed step once more through the timed call, as a stream of its own (rank 0), and write "
                     "what it returns as DIR/<name>.npy - status, objective, bound and gap, every member of the RawResults records; float64 / float32, at most 64 MB in all (beyond that a fixed seeded "
                     "sample of the queue). The instances are a function of the arguments alone (seeded generator) and a stream of its own meets no decision of the wall clock before its first instance "
@@ -238,6 +248,8 @@ def main():
                     "retires, and their neighbours - are left out and counted in the result line")
     ap.add_argument("--dump-lp", default=None, metavar="DIR", help="write the raw big-M model of every instance of the first timed step as CPLEX .lp (miqp_solver_export_lp) so that a licence holder can fill in the CPLEX column")
     a = ap.parse_args()
+    if a.long_extras and not a.full:
+        ap.error("--long-extras is a leg of --full")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started as a plain `python bench.py --gpus N`: become the launcher of N ranks (one process per GPU) BEFORE anything
@@ -296,6 +308,7 @@ def main():
         return ps, ws
 
     batches = [make_batch(s) for s in range(a.warmup + a.steps)]
+    t_setup = time.time() - T_START
     if os.environ.get("MIQP_BENCH_DUMP_SEEDS"):   # (tests: which seeds this rank solves in its timed steps)
         print("[bench seeds] " + json.dumps(dict(rank=rank, timed=[sd for st_ in range(a.warmup, a.warmup + a.steps) for sd in seeds_of(st_)])), file=sys.stderr, flush=True)
     infl = None if a.no_stream else B
@@ -317,6 +330,7 @@ def main():
             P.solve_batch(wws, inflight=infl, prepared=True)
     sync()
     t0 = time.time()
+    t_warm = t0 - T_START - t_setup
     solved = 0; attempted = 0; ipm_s = 0.0; launches = 0; iters = 0; rowit = 0; nodes = 0; asx = [0.0] * 8; lat = []; results_s = 0.0; nrec = 0; stream_info = None; stream_ws = None
     # streaming: the queues of the K timed steps are drained as ONE stream (a step = its queue of instances; no idle tail
     # between steps: the slots freed by the last instances of one queue go to the first of the next); --no-stream: step by step
@@ -409,8 +423,8 @@ def main():
         dumped["first_time_limit_could_run_out_s"] = float(min(w.lastAdmission() for w in lws) + a.time_limit)
 
     extras = None
-    if rank == 0 and world == 1 and not a.no_extras and not a.no_stream and a.total <= 0:
-        # Legs behind the timed region (rank 0, single GPU; they re-solve instances of the timed queues, results are discarded):
+    if a.full and rank == 0 and world == 1 and not a.no_extras and not a.no_stream and a.total <= 0:
+        # Legs behind the timed region (--full; rank 0, single GPU; they re-solve instances of the timed queues, results are discarded):
         #  * all_proven_at_bench_in_flight: the whole timed stream again, same in-flight setting, limit 60 s instead of 10 s;
         #  * time_to_prove_all: the head of the stream (2048 instances) at 256 in flight, limit 60 s - ends with its slowest instance;
         #  * in_flight_sweep (--long-extras): the same head at 256 / 512 in flight with the reference's 10 s limit;
@@ -526,12 +540,17 @@ def main():
         out["proven_share"] = tot_solved / max(1, tot_att)
         if dumped:
             out["dumped_outputs"] = dumped
-        if not a.no_cpu and world == 1:
+        if a.full and not a.no_cpu and world == 1:
             out["cpu_baseline"] = cpu_baseline(batches[a.warmup][0], a.gap, a.time_limit)
             cpx = cplex_baseline(lp_files, a.gap, a.time_limit) if lp_files else None
             out["cplex_baseline"] = cpx if cpx else ("CPLEX not available on this host" + ("" if lp_files else " (run with --dump-lp DIR to export the instances)"))
-        elif not a.no_cpu:
+        elif a.full and not a.no_cpu:
             out["cpu_baseline"] = None
+        # where the run's own time went (rank 0): what a caller waits for beside (steps + warmup) x ms_per_step is `outside_steps` - the set-up, the part of the
+        # warm-up stream beyond warmup x ms_per_step (first touch of the device, the flush of its last instances) and everything behind the timed region (with --full: minutes)
+        wall = time.time() - T_START
+        out["run_seconds"] = dict(set_up=round(t_setup, 3), warm_up=round(t_warm, 3), timed=round(dt, 3), behind_timed=round(wall - t_setup - t_warm - dt, 3), total=round(wall, 3),
+                                  outside_steps=round(wall - (a.steps + a.warmup) * T / a.steps, 3))
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()

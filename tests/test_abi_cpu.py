@@ -415,6 +415,42 @@ def test_bench_dump_outputs_writes_the_last_timed_step(tmp_path):
     assert o3["steps"] == 3 and o3["config"]["instances_attempted"] == 18 and list(d3["seed"]) == list(range(18, 24))
 
 
+def test_bench_plain_run_is_lean_and_full_runs_every_leg(lib):
+    """a plain `bench.py --gpus 1 --steps K --warmup W` prints the headline line and nothing that takes a run of its own; `--full` adds the legs
+    behind the timed region, the CPU baseline and the CPLEX column, and `--no-cpu` / `--no-extras` narrow it as they did before the option existed.
+    No GPU here: the device legs end in the loud no-device failure, the CPU baseline (the oracle) is real."""
+    import json
+    moved = {"cpu_baseline", "cplex_baseline", "all_proven_at_bench_in_flight", "time_to_prove_all", "all_proven", "in_flight_sweep", "one_batch_control",
+             "value_limit_lifted", "proven_share_limit_lifted", "value_all_proven"}
+    headline = {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "n_gpus", "config", "roofline", "proven_share", "run_seconds"}
+
+    def run(extra):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "mini", "--batch", "3", "--queue-factor", "2", "--steps", "2", "--warmup", "1",
+                            "--time-limit", "1"] + extra, capture_output=True, text=True, timeout=600)
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert r.returncode == 0 and len(lines) == 1, r.stdout[-2000:] + r.stderr[-2000:]
+        return json.loads(lines[0])
+    plain = run([])
+    assert headline <= set(plain) and not (moved & set(plain))
+    assert plain["metric"].startswith("MIQP solves/sec") and plain["unit"] == "MIQP solves/s" and plain["higher_is_better"] is True and plain["dtype"] == "f64"
+    assert plain["steps"] == 2 and plain["warmup"] == 1 and plain["ms_per_step"] > 0 and plain["config"]["instances_attempted"] == 12
+    rs = plain["run_seconds"]
+    assert abs(rs["set_up"] + rs["warm_up"] + rs["timed"] + rs["behind_timed"] - rs["total"]) < 0.01
+    assert abs(rs["outside_steps"] - (rs["total"] - 3 * plain["ms_per_step"] / 1e3)) < 0.01
+    assert set(run(["--no-cpu", "--no-extras"])) == set(plain)           # (the narrowing options of a full run change nothing in a plain one)
+    full = run(["--full"])
+    assert moved <= set(full) and set(plain) <= set(full)
+    assert full["cpu_baseline"]["kind"] == "port" and full["cpu_baseline"]["share_proven"] == 1.0 and full["cpu_baseline"]["value"] > 0
+    assert full["one_batch_control"]["instances"] == 12 and full["all_proven_at_bench_in_flight"]["queue"] == 12 and full["in_flight_sweep"] == []
+    assert isinstance(full["cplex_baseline"], (str, dict))
+    nocpu = run(["--full", "--no-cpu"])
+    assert "cpu_baseline" not in nocpu and "one_batch_control" in nocpu
+    noext = run(["--full", "--no-extras"])
+    assert "cpu_baseline" in noext and "one_batch_control" not in noext
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "mini", "--long-extras"], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 2 and "--full" in r.stderr                    # (a leg of the full run asked for without it: refused, not dropped)
+
+
 def test_bench_dump_outputs_samples_beyond_its_limit(lib, tmp_path, monkeypatch):
     """more than the limit: a fixed sample of the instances - the same in every run, sorted, named by `instance` and `seed`"""
     import bench

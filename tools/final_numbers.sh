@@ -2,7 +2,7 @@
 # measurement campaign of the round (GPU): bench sweep over the instances in flight, other BASELINE configurations, single solves
 R=${GRAFT_REPO_ROOT:-$PWD}; cd $R; O=gpurun_out/final_numbers; mkdir -p $O
 STEPS=4 tools/bench_sweep.sh > $O/batch_sweep.jsonl 2>$O/batch_sweep.err
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 python bench.py --no-stream --batch 1024 --steps 2 --warmup 1 --no-cpu > $O/bench_nostream_1024.json 2>/dev/null
 python bench.py --no-stream --batch 256 --steps 2 --warmup 1 --no-cpu > $O/bench_nostream_256.json 2>/dev/null
 python bench.py --config cfg4 --total 256 --batch 256 --steps 1 --warmup 1 --no-cpu > $O/bench_cfg4_strong.json 2>/dev/null

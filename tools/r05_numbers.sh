@@ -1,7 +1,7 @@
 #!/bin/bash
 # the other BASELINE configurations at the end of round 5 (the bench lines themselves: profiles/r05_driver_like_bench_final_commit.json)
 R=${GRAFT_REPO_ROOT:-$PWD}; cd $R; O=gpurun_out/r05_numbers; mkdir -p $O
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 python bench.py --config cfg4 --total 256 --batch 256 --steps 1 --warmup 1 --no-cpu --no-extras > $O/bench_cfg4_strong.json 2>/dev/null
 python tools/stream_check.py 256 256 0 10 cfg2 > $O/cfg2.json 2>/dev/null
 python tools/stream_check.py 256 256 1000 10 cfg4 > $O/cfg4.json 2>/dev/null

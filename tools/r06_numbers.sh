@@ -4,8 +4,8 @@
 R=${GRAFT_REPO_ROOT:-$PWD}; cd $R; O=gpurun_out/r06; mkdir -p $O
 part=${1:-a}
 if [ "$part" = a ]; then   # the bench lines
-  python bench.py --gpus 1 --steps 20 --warmup 5 > $O/driver_like_bench.json 2> $O/driver_like_bench.err
-  python bench.py > $O/final_bench.json 2> $O/final_bench.err
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/driver_like_bench.json 2> $O/driver_like_bench.err
+  python bench.py --full > $O/final_bench.json 2> $O/final_bench.err
   python bench.py --no-cpu --no-extras --steps 40 --warmup 0 > $O/long_stream_bench.json 2>/dev/null
   MIQP_AS=0 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu --no-extras > $O/driver_like_bench_interior_point_only.json 2>/dev/null
   for f in driver_like_bench final_bench long_stream_bench driver_like_bench_interior_point_only; do python tools/bl.py $O/$f.json; done
