@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -32,22 +33,31 @@ extern char** environ;
 
 namespace miqp {
 
+// One spelling per read: the macro with the literal name stays at the read site (the switch test finds the names there), these give the value.
+// `v` is what KNOB_P / KNOB_T returned: null when the variable is not set (or, for KNOB_T, in the product build).
+inline bool knob_set(const char* v) { return v != nullptr; }
+inline bool knob_off(const char* v) { return v && std::atoi(v) == 0; }   // present and 0: the way a default-on switch is turned off
+inline int knob_int(const char* v, int dflt) { return v ? std::atoi(v) : dflt; }
+inline double knob_double(const char* v, double dflt) { return v ? std::atof(v) : dflt; }
+inline int knob_bits(const char* v, int dflt) { return v ? (int)std::strtoul(v, nullptr, 0) : dflt; }   // a bit set: decimal, 0x..., 0...
+
 // A MIQP_* variable that the shipped library does not read (a switch of a tuning build, a typo) is named once on stderr instead of being a
-// silent no-op (advisor finding of round 5).  The names the product build reads (KNOB_P) and the two of the Python side:
+// silent no-op (advisor finding of round 5).  The names the product build reads (KNOB_P) and those of the Python side
+// and of bench.py (tests/test_abi_cpu.py compares this list with the sources):
 inline void warn_ignored_switches() {
 #ifndef MIQP_TUNING
-  static bool done = false;
-  if (done) return;
-  done = true;
-  static const char* const known[] = {"MIQP_SEQ_KINDS", "MIQP_LNS", "MIQP_PUMP", "MIQP_CUT_GATE", "MIQP_NPR", "MIQP_OPEN_CAP", "MIQP_FAR_CAP", "MIQP_LANES", "MIQP_AS",
-                                      "MIQP_STATS", "MIQP_DEBUG_SYNC", "MIQP_TRACE", "MIQP_ROUND_LOG", "MIQP_GPU_LIB", "MIQP_BENCH_DUMP_SEEDS"};
-  for (char** e = environ; e && *e; ++e) {
-    if (std::strncmp(*e, "MIQP_", 5) != 0) continue;
-    const char* eq = std::strchr(*e, '='); const size_t len = eq ? (size_t)(eq - *e) : std::strlen(*e);
-    bool ok = false;
-    for (const char* k : known) if (std::strlen(k) == len && std::strncmp(k, *e, len) == 0) { ok = true; break; }
-    if (!ok) std::fprintf(stderr, "[miqp_gpu] environment variable %.*s is ignored: the shipped library reads only the switches of INTEGRATION.md section 5 (experiment switches exist in a tuning build, tools/build_variants.sh)\n", (int)len, *e);
-  }
+  static std::once_flag once;   // (two lanes of a stream call, or two threads of solve_batch_multi, enter a solve at the same time)
+  std::call_once(once, [] {
+    static const char* const known[] = {"MIQP_SEQ_KINDS", "MIQP_LNS", "MIQP_PUMP", "MIQP_CUT_GATE", "MIQP_NPR", "MIQP_OPEN_CAP", "MIQP_FAR_CAP", "MIQP_LANES", "MIQP_AS",
+                                        "MIQP_STATS", "MIQP_DEBUG_SYNC", "MIQP_TRACE", "MIQP_ROUND_LOG", "MIQP_GPU_LIB", "MIQP_BENCH_DUMP_SEEDS", "MIQP_BENCH_MAT_THREADS"};
+    for (char** e = environ; e && *e; ++e) {
+      if (std::strncmp(*e, "MIQP_", 5) != 0) continue;
+      const char* eq = std::strchr(*e, '='); const size_t len = eq ? (size_t)(eq - *e) : std::strlen(*e);
+      bool ok = false;
+      for (const char* k : known) if (std::strlen(k) == len && std::strncmp(k, *e, len) == 0) { ok = true; break; }
+      if (!ok) std::fprintf(stderr, "[miqp_gpu] environment variable %.*s is ignored: the shipped library reads only the switches of INTEGRATION.md section 5 (experiment switches exist in a tuning build, tools/build_variants.sh)\n", (int)len, *e);
+    }
+  });
 #endif
 }
 
@@ -302,7 +312,7 @@ inline Layout make_layout(int C, int N, int R, int P, int E, int EL, int O, int 
   // (OFF by default; MIQP_RELAX_FRONT=1 switches the relaxed rows on.  Measured on the bench instances: deciding a car/car group
   // on a front point BEFORE the region of its car - with the front-point offset bounded over the region set - doubles the nodes,
   // 23 M against 10.9 M on a 2048-instance queue: the exact row is still violated afterwards, the region is branched anyway)
-  { const char* e = KNOB_T("MIQP_RELAX_FRONT"); Y.relax_front_off = (e && std::atoi(e) == 1) ? 0 : 1; }
+  Y.relax_front_off = knob_int(KNOB_T("MIQP_RELAX_FRONT"), 0) == 1 ? 0 : 1;
   Y.SC = 16 + 5 * EL + 5 * O; Y.NSLOT = C * Y.SC + Y.NP * 24; Y.ROWCAP = N * Y.NSLOT;
   int o = 0;
   Y.d_x0 = o; o += C * 6; Y.d_wd = o; o += Y.nz; Y.d_ref = o; o += N * Y.nz; Y.d_glob = o; o += 8; Y.d_u0box = o; o += C * 4;
@@ -628,7 +638,7 @@ inline void compile_instance(const HostInst& I, const Layout& Y, double* D, int*
       // flagged by a sector row, and those are settled by the branching itself), but two more general rows per undecided
       // (car, step) push two thirds of the nodes over the on-chip kernel's 128 general rows into the memory-backed kernel
       // (+25 % interior point time).  The boxes are box rows of the kernels: free.
-      { static const bool cone = KNOB_T("MIQP_HULL_CONE") != nullptr && std::atoi(KNOB_T("MIQP_HULL_CONE")) != 0; if (!cone) continue; }
+      { static const bool cone = knob_int(KNOB_T("MIQP_HULL_CONE"), 0) != 0; if (!cone) continue; }
       // the cone around all sectors = complement of the widest angular gap between them
       std::vector<int> ord(cones.size()); for (size_t k = 0; k < ord.size(); ++k) ord[k] = (int)k;
       std::sort(ord.begin(), ord.end(), [&](int a, int b) { return cones[a][0] < cones[b][0]; });

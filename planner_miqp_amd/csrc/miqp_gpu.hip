@@ -247,6 +247,72 @@ bool step0_check(const HostGeo& G, double& cobj) {
 // ================================================================================================
 namespace {
 
+// ---------------------------------------------------------------- environment switches, by WHEN they are read
+// Each name is read in one place per lifetime:
+//   process: once, at the first solve of the process (ProcessSwitches)
+//   context: when a device context is built, and latched in it until the shape of the call changes (CtxSwitches; MIQP_OPEN_CAP, MIQP_NPR and
+//            MIQP_LANES shape the context through plan_call's result)
+//   call:    at the start of every solve (read_call_switches for what the host decides with, apply_call_switches for the search fields of DevBuf)
+struct ProcessSwitches {
+  int prep_threads;          // (the 51 200 instances of the driver's stream on a 2 x 64-core host: 0.38 / 0.44 / 0.57 / 0.76 s at 16 / 32 / 64 / 128 threads - allocator and first-touch contention, not arithmetic)
+  bool round_log;            // diagnostic: the batch sizes of the rounds, printed after the solve (no extra synchronisation)
+  bool launch_trace; int replay, replay_round;   // diagnostics of solve_diag.hpp
+  int big_grid_cap; double big_w1, big_w2;       // launch_ipm_batch
+};
+const ProcessSwitches& process_switches() {
+  static const ProcessSwitches p = {
+      knob_int(KNOB_T("MIQP_PREP_THREADS"), 16), knob_set(KNOB_P("MIQP_ROUND_LOG")),
+      knob_set(KNOB_T("MIQP_LAUNCH_TRACE")), knob_int(KNOB_T("MIQP_REPLAY"), 0), knob_int(KNOB_T("MIQP_REPLAY_ROUND"), 0),
+      knob_int(KNOB_T("MIQP_BIG_GRID"), 1 << 30),
+      knob_double(KNOB_T("MIQP_BIG_W1"), 6.0), knob_double(KNOB_T("MIQP_BIG_W2"), 28.0)};   // (driver's stream, launch group / standard launch: 9.10 / 8.41 ms at 5 / 20, 8.76 / 8.50 at 6 / 28, 8.87 / 8.53 at 8 / 36)
+  return p;
+}
+
+struct CtxSwitches {
+  bool ipm_v1; int oc_waves;              // (experiment: resident wavefronts of the on-chip kernel per CU; 0: what its LDS admits)
+  bool concurrent_big, oc_big; int oc_oversub;   // 0: off
+  long long far_cap;                      // < 0: from the free memory
+  bool warm;                              // warm start of the node relaxations (MIQP_WARM=0: cold)
+  int opt2; double ws_mu, ws_delta; int as_chunk, as_quota;
+  bool probe_overlap, stats, nocut;
+};
+CtxSwitches read_ctx_switches() {
+  CtxSwitches c;
+  c.ipm_v1 = knob_set(KNOB_T("MIQP_IPM_V1")); c.oc_waves = knob_int(KNOB_T("MIQP_OC_WAVES"), 0);
+  c.concurrent_big = !knob_off(KNOB_T("MIQP_CONCURRENT_BIG")); c.oc_big = !knob_off(KNOB_T("MIQP_OC_BIG"));
+  { const char* e = KNOB_T("MIQP_OC_OVERSUB"); c.oc_oversub = e ? std::max(1, std::min(64, std::atoi(e))) : 0; }
+  { const char* e = KNOB_P("MIQP_FAR_CAP"); c.far_cap = e ? std::max(0LL, std::atoll(e)) : -1; }
+  c.warm = !knob_off(KNOB_T("MIQP_WARM"));
+  c.opt2 = knob_int(KNOB_T("MIQP_OPT2"), 8 << 4);   // rounding probe at nodes with at most 8 violated sites (eval_kernel)
+  c.ws_mu = knob_double(KNOB_T("MIQP_WS_MU"), 1.0); c.ws_delta = knob_double(KNOB_T("MIQP_WS_DELTA"), 1.0e-3);
+  c.as_chunk = knob_int(KNOB_T("MIQP_AS_CHUNK"), 1); c.as_quota = knob_int(KNOB_T("MIQP_AS_QUOTA"), 0);   // (runs of 2 / 4 / 8 / 16: the standard launch 4.7 -> 5.2 / 6.6 / 7.9 / 10.3 ms - a wavefront solves ~14 nodes per launch, longer runs only lengthen its tail)
+  c.probe_overlap = !knob_off(KNOB_T("MIQP_PROBE_OVERLAP"));
+  c.stats = knob_set(KNOB_P("MIQP_STATS"));   // (here: whether the counters are allocated)
+  c.nocut = knob_set(KNOB_T("MIQP_NOCUT"));   // diagnostic: every node relaxation runs to convergence (tells infeasible children from expensive ones)
+  return c;
+}
+
+// what the host side of a call decides with; the loop, the diagnostics and launch_ipm_batch read this (DevCtx::sw), not the environment
+struct CallSwitches {
+  int npr = 0, open_cap = 0;   // MIQP_NPR / MIQP_OPEN_CAP; 0: not set
+  int seq_kinds = 5 << 8;      // plain K-way children, branching order 5 (see eval_kernel)
+  bool debug_sync = false, trace = false, stats = false;
+  bool memsets = false, cls_lists = true, big_pad = true;
+  bool polish_cold = false; double polish_mu = 1.0e-2, polish_delta = 1.0e-4;   // the polish of the incumbents (polish())
+  const char* dump_open = nullptr; const char* wave_dump = nullptr;            // diagnostics that write a file: its path
+};
+CallSwitches read_call_switches() {
+  CallSwitches w;
+  if (const char* e = KNOB_P("MIQP_NPR")) w.npr = std::max(1, std::atoi(e));   // tuning knob
+  if (const char* e = KNOB_P("MIQP_OPEN_CAP")) w.open_cap = std::max(64, std::atoi(e));
+  w.seq_kinds = knob_bits(KNOB_P("MIQP_SEQ_KINDS"), 5 << 8);
+  w.debug_sync = knob_set(KNOB_P("MIQP_DEBUG_SYNC")); w.trace = knob_set(KNOB_P("MIQP_TRACE")); w.stats = knob_set(KNOB_P("MIQP_STATS"));
+  w.memsets = knob_set(KNOB_T("MIQP_MEMSETS")); w.cls_lists = !knob_off(KNOB_T("MIQP_CLS_LISTS")); w.big_pad = !knob_off(KNOB_T("MIQP_BIG_PAD"));
+  w.polish_cold = knob_set(KNOB_T("MIQP_POLISH_COLD")); w.polish_mu = knob_double(KNOB_T("MIQP_POLISH_MU"), 1.0e-2); w.polish_delta = knob_double(KNOB_T("MIQP_POLISH_DELTA"), 1.0e-4);
+  w.dump_open = KNOB_T("MIQP_DUMP_OPEN"); w.wave_dump = KNOB_T("MIQP_WAVE_DUMP");
+  return w;
+}
+
 struct DevCtx {
   std::mutex mu;   // held for the whole solve: one solve at a time per device, different devices run concurrently
   bool ready = false; int device = -1;
@@ -272,6 +338,7 @@ struct DevCtx {
   int* cls_list = nullptr; int cls_n[3] = {-1, -1, -1};   // the round's class lists and (read back with the batch count) their lengths; -1: not known, the launches scan the batch
   unsigned short* as_batch_A = nullptr; unsigned short* as_pool_A = nullptr;   // (kept here: a call with MIQP_AS=0 runs with the DevBuf pointers nulled)   // dual active-set launch in front of the standard interior point launch (two cars; MIQP_AS=0: off)
   DevBuf B{};
+  CallSwitches sw;   // of the call that holds the context (apply_call_switches)
   std::vector<void*> allocs;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   std::vector<hipEvent_t> ipm_ev;  // pairs
@@ -319,92 +386,104 @@ bool same_layout(const Layout& a, const Layout& b) { return std::memcmp(&a, &b, 
 // A ready context of the same shape is reused as it is when the call has no more instances than its per-instance arrays hold
 // (built for 64 queues' worth at least, within 4 GB): releasing and reallocating the pools - most of the device memory - costs
 // seconds, and a service that drains one queue after the other must not pay them per call (measured: 4.3 s of a 17 s bench stream).
-std::mutex g_ctx_build_mu;   // contexts are built one at a time: each sizes its pools from the memory that is free at that moment
-bool ctx_prepare(DevCtx& X, const Layout& Y, int n_inst, int n_slots, int open_cap, int npr, int roots_per_inst, bool clamp_open = false, int mem_div = 1) {
-  int batch_cap = n_slots * npr;
-  HIP_OK(hipSetDevice(X.device));   // the calling thread's current device (threads of solve_batch_multi each set their own)
-  if (X.ready && same_layout(X.Y, Y) && n_inst <= X.n_inst_cap && X.n_slots == n_slots && X.open_cap_req == open_cap && X.npr == npr && X.B.root_stride == roots_per_inst && X.mem_div == mem_div) {
-    X.n_inst = n_inst; X.B.n_inst = n_inst;
-    return true;
-  }
-  std::lock_guard<std::mutex> build_lock(g_ctx_build_mu);
-  if (X.ready || !X.allocs.empty()) X.release();
-  if (!X.stream) HIP_OK(hipStreamCreate(&X.stream));
-  if (!X.ev0) { HIP_OK(hipEventCreate(&X.ev0)); HIP_OK(hipEventCreate(&X.ev1)); }
-  X.open_cap_req = open_cap; X.mem_div = mem_div < 1 ? 1 : mem_div;
-  if (clamp_open) { size_t fb = 0, tb = 0; if (hipMemGetInfo(&fb, &tb) == hipSuccess) { const size_t lim = fb / (size_t)X.mem_div / 8 / 40 / (size_t)n_slots; if ((size_t)open_cap > lim) open_cap = (int)std::max<size_t>(4096, lim); } }
+bool ctx_matches(const DevCtx& X, const Layout& Y, int n_inst, int n_slots, int open_cap, int npr, int roots_per_inst, int mem_div) {
+  return X.ready && same_layout(X.Y, Y) && n_inst <= X.n_inst_cap && X.n_slots == n_slots && X.open_cap_req == open_cap && X.npr == npr && X.B.root_stride == roots_per_inst && X.mem_div == mem_div;
+}
+
+// Every capacity of a context: a pure function of the shape, the memory that is free on the device, its CU count and the context switches.
+// ctx_alloc walks it; the footprint of a context is this value.
+struct CtxSizes {
+  int n_inst_cap, open_cap, far_cap, pool_cap, z_cap, batch_cap, batch_alloc;
+  int ipm_grid_max, oc_grid, ocb_grid, kg_blocks, probe_grid;
+  bool concurrent_big, as_cap, as_starts;   // as_starts: the parents' active sets are kept for the children's starts
+  size_t ring_doubles, ring_margin;         // 0: no ring
+};
+CtxSizes ctx_sizes(const Layout& Y, int n_inst, int n_slots, int open_cap, int npr, int roots_per_inst, bool clamp_open, int mem_div, bool free_known, size_t free_b, int cus, const CtxSwitches& cs) {
+  CtxSizes Z{};
+  if (clamp_open && free_known) { const size_t lim = free_b / (size_t)mem_div / 8 / 40 / (size_t)n_slots; if ((size_t)open_cap > lim) open_cap = (int)std::max<size_t>(4096, lim); }
+  Z.open_cap = open_cap;
   {   // capacity of the per-instance arrays (tables, incumbent records: dstride * 8 + istride * 4 + fix record + solution per instance)
     const size_t per = (size_t)Y.dstride * 8 + (size_t)Y.istride * 4 + (size_t)Y.fixlen * 2 + (size_t)Y.N * Y.nz * 16 + 256;
     size_t cap = std::min<size_t>((size_t)64 * (size_t)n_slots, ((size_t)4 << 30) / per);
-    X.n_inst_cap = (int)std::max<size_t>((size_t)n_inst, cap);
+    Z.n_inst_cap = (int)std::max<size_t>((size_t)n_inst, cap);
   }
-  const int n_call = n_inst;
-  n_inst = X.n_inst_cap;   // everything below is sized for the capacity
-  const int batch_alloc = std::max(batch_cap, n_inst);   // the final polish solves one node per instance in one launch
-  X.Y = Y; X.n_inst = n_call; X.n_slots = n_slots; X.open_cap = open_cap; X.npr = npr; X.batch_cap = batch_cap; X.batch_alloc = batch_alloc;
-  { hipDeviceProp_t pr; int dv = 0; (void)hipGetDevice(&dv); int cus = 256; if (hipGetDeviceProperties(&pr, dv) == hipSuccess) cus = pr.multiProcessorCount;
-    // resident workgroups of the memory-backed kernel per CU: what its LDS admits, and its wavefronts per SIMD (three and four cars: workgroups of four wavefronts)
-    size_t l = ipm_lds_bytes(Y); int per = (int)std::max<size_t>(1, std::min<size_t>(Y.C <= 2 ? 4 * MIQP_IPM_WPE : (4 * MIQP_WIDE_WPE) / (MIQP_WIDE_NT / 64), (160 * 1024) / std::max<size_t>(l + 8, 1))); X.ipm_grid_max = cus * per;
-    // on-chip kernel: up to two cars, horizon within its register slots; 2 wavefronts per SIMD, as many as its LDS admits
-    X.oc_grid = 0;
-    const OcLds ol = oc_lds_layout(Y.N, Y.fixlen);
-    const size_t bitmap_b = (size_t)((Y.N * Y.NSLOT + 63) / 64) * 10 + 16;   // decode bitmap + prefix inside the scratch region
-    if (Y.C <= 2 && Y.N <= 2 * OC_NSL && bitmap_b + 1024 <= (size_t)(ol.r - ol.u) && !KNOB_T("MIQP_IPM_V1")) {
-      size_t lo = (size_t)ol.total + 16;
-      int perc = (int)std::min<size_t>(8, (160 * 1024) / lo);
-      if (KNOB_T("MIQP_OC_WAVES")) perc = std::max(1, std::min(perc, std::atoi(KNOB_T("MIQP_OC_WAVES"))));   // (experiment: resident wavefronts of the on-chip kernel per CU)
-      if (perc >= 1) X.oc_grid = cus * perc;
-      X.ocb_grid = 0; X.concurrent_big = !(KNOB_T("MIQP_CONCURRENT_BIG") && std::atoi(KNOB_T("MIQP_CONCURRENT_BIG")) == 0);
-      if (X.oc_grid > 0 && !(KNOB_T("MIQP_OC_BIG") && std::atoi(KNOB_T("MIQP_OC_BIG")) == 0)) {
-        const size_t lb = (size_t)oc_lds_layout(Y.N, Y.fixlen, OC_GCAP_BIG).total + 16;
-        const int pb = (int)std::min<size_t>(4, (160 * 1024) / lb);
-        if (pb >= 1) X.ocb_grid = cus * pb;
-      }
+  n_inst = Z.n_inst_cap;   // everything below is sized for the capacity
+  Z.batch_cap = n_slots * npr;
+  const int batch_alloc = Z.batch_alloc = std::max(Z.batch_cap, n_inst);   // the final polish solves one node per instance in one launch
+  // resident workgroups of the memory-backed kernel per CU: what its LDS admits, and its wavefronts per SIMD (three and four cars: workgroups of four wavefronts)
+  size_t l = ipm_lds_bytes(Y); int per = (int)std::max<size_t>(1, std::min<size_t>(Y.C <= 2 ? 4 * MIQP_IPM_WPE : (4 * MIQP_WIDE_WPE) / (MIQP_WIDE_NT / 64), (160 * 1024) / std::max<size_t>(l + 8, 1))); Z.ipm_grid_max = cus * per;
+  // on-chip kernel: up to two cars, horizon within its register slots; 2 wavefronts per SIMD, as many as its LDS admits
+  Z.concurrent_big = true;
+  const OcLds ol = oc_lds_layout(Y.N, Y.fixlen);
+  const size_t bitmap_b = (size_t)((Y.N * Y.NSLOT + 63) / 64) * 10 + 16;   // decode bitmap + prefix inside the scratch region
+  if (Y.C <= 2 && Y.N <= 2 * OC_NSL && bitmap_b + 1024 <= (size_t)(ol.r - ol.u) && !cs.ipm_v1) {
+    size_t lo = (size_t)ol.total + 16;
+    int perc = (int)std::min<size_t>(8, (160 * 1024) / lo);
+    if (cs.oc_waves) perc = std::max(1, std::min(perc, cs.oc_waves));
+    if (perc >= 1) Z.oc_grid = cus * perc;
+    Z.concurrent_big = cs.concurrent_big;
+    if (Z.oc_grid > 0 && cs.oc_big) {
+      const size_t lb = (size_t)oc_lds_layout(Y.N, Y.fixlen, OC_GCAP_BIG).total + 16;
+      const int pb = (int)std::min<size_t>(4, (160 * 1024) / lb);
+      if (pb >= 1) Z.ocb_grid = cus * pb;
     }
-    if (X.oc_grid > X.ipm_grid_max) X.ipm_grid_max = X.oc_grid;   // the per-block buffers are sized for the larger grid
-    // Oversubscribed launches of the on-chip kernels (MIQP_OC_OVERSUB = F): F times the resident wavefronts, each working through 1 / F of the
-    // nodes - a wavefront slot comes free F times as often, so the short kernels of ANOTHER lane of the same device (MIQP_LANES: its
-    // evaluation and selection) are dispatched between them instead of waiting for the whole launch.  Only the gain buffer grows.
-    X.kg_blocks = X.ipm_grid_max;
-    if (const char* e = KNOB_T("MIQP_OC_OVERSUB")) { const int f = std::max(1, std::min(64, std::atoi(e)));
-      X.oc_grid = std::min(batch_alloc, X.oc_grid * f); X.ocb_grid = std::min(batch_alloc, X.ocb_grid * f); X.kg_blocks = std::max(X.kg_blocks, std::max(X.oc_grid, X.ocb_grid)); }
   }
+  if (Z.oc_grid > Z.ipm_grid_max) Z.ipm_grid_max = Z.oc_grid;   // the per-block buffers are sized for the larger grid
+  // Oversubscribed launches of the on-chip kernels (MIQP_OC_OVERSUB = F): F times the resident wavefronts, each working through 1 / F of the
+  // nodes - a wavefront slot comes free F times as often, so the short kernels of ANOTHER lane of the same device (MIQP_LANES: its
+  // evaluation and selection) are dispatched between them instead of waiting for the whole launch.  Only the gain buffer grows.
+  Z.kg_blocks = Z.ipm_grid_max;
+  if (const int f = cs.oc_oversub) { Z.oc_grid = std::min(batch_alloc, Z.oc_grid * f); Z.ocb_grid = std::min(batch_alloc, Z.ocb_grid * f); Z.kg_blocks = std::max(Z.kg_blocks, std::max(Z.oc_grid, Z.ocb_grid)); }
   // node pool: live nodes are bounded by the open lists plus one round of children; processed records are recycled
-  size_t free_b = 0, total_b = 0; if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = (size_t)16 << 30;
-  free_b /= (size_t)X.mem_div;
+  if (!free_known) free_b = (size_t)16 << 30;
+  free_b /= (size_t)mem_div;
   // far tier of the open lists (16 B per entry): up to 2^24 entries per instance within a tenth of the free memory
   // (256 instances: 4 M entries each, 16 GB); MIQP_FAR_CAP overrides, 0 switches the tier off
   { size_t fc = std::min<size_t>((size_t)1 << 24, free_b / 10 / 16 / (size_t)n_slots);
-    if (const char* e = KNOB_P("MIQP_FAR_CAP")) fc = (size_t)std::max(0LL, std::atoll(e));
-    X.far_cap = fc < 4096 ? 0 : (int)fc; }
-  size_t want = (size_t)n_slots * ((size_t)open_cap + (size_t)X.far_cap + (size_t)npr * 64 + 64) + (size_t)n_inst * roots_per_inst;
-  const bool ws_on = !(KNOB_T("MIQP_WARM") && std::atoi(KNOB_T("MIQP_WARM")) == 0);   // warm start of the node relaxations (MIQP_WARM=0: cold)
+    if (cs.far_cap >= 0) fc = (size_t)cs.far_cap;
+    Z.far_cap = fc < 4096 ? 0 : (int)fc; }
+  size_t want = (size_t)n_slots * ((size_t)open_cap + (size_t)Z.far_cap + (size_t)npr * 64 + 64) + (size_t)n_inst * roots_per_inst;
   size_t maxrec = std::min<size_t>((size_t)64 << 30, free_b / 4) / (size_t)Y.fixlen;   // node records: up to 64 GB of the 288 GB, at most a quarter of what is free
-  X.pool_cap = (int)std::min<size_t>(std::min(want, maxrec), (size_t)0x7FFFFFF0);
+  Z.pool_cap = (int)std::min<size_t>(std::min(want, maxrec), (size_t)0x7FFFFFF0);
+  // the parents' solutions for the warm starts: for the first z_cap records (recycled records keep the live set at low
+  // indices) - 16384 per instance in flight, at least 2 M, within an eighth of the free memory (42 GB at 1024 in flight, 5 GB
+  // for a single solve: a large allocation costs seconds, and a context is rebuilt whenever the shape of the call changes)
+  if (cs.warm) {
+    const size_t zb = (size_t)Y.N * Y.nz * 8;
+    size_t zc = std::max<size_t>((size_t)2 << 20, (size_t)n_slots * 16384);
+    Z.z_cap = (int)std::min(zc, std::min<size_t>((size_t)Z.pool_cap, free_b / 8 / zb));
+  }
+  Z.as_cap = Y.C == 2 && Z.oc_grid > 0;   // the shape has the active-set launches (whether a call uses them: MIQP_AS, read per call)
+  Z.as_starts = Z.as_cap && Z.z_cap > 0 && Y.N * Y.NSLOT + 1024 < 65535;   // the parents' active sets for the children's starts (128 B per record)
+  if (Z.as_starts) {
+    // ... and the ring their M travels through (4 KB per node on average, at most 12.8): a quarter of the free memory, at most 96 GB
+    const size_t rd = std::min<size_t>(std::min<size_t>((size_t)12 << 30, free_b / 4 / 8), std::max<size_t>((size_t)1 << 30, (size_t)n_slots * ((size_t)8 << 20)));   // doubles: 64 MB per instance in flight, at least 8 GB (a single solve: hundreds of its rounds; a large allocation costs seconds when the context is built)
+    const size_t margin = (size_t)batch_alloc * AS_MSTR + ((size_t)1 << 20);   // what one round's launches can allocate, and more
+    if (rd >= 2 * margin) { Z.ring_doubles = rd; Z.ring_margin = margin; }
+  }
+  // buffers of the concurrent probe launch (two cars and fewer, on-chip kernel in use): 1024 resident blocks
+  if (Z.oc_grid > 0 && cs.probe_overlap) Z.probe_grid = std::min(batch_alloc, 1536);
+  return Z;
+}
+
+// the allocations of a context, in the order that decides their addresses
+bool ctx_alloc(DevCtx& X, const CtxSizes& Z, const CtxSwitches& cs, int n_call, int n_slots, int npr, int roots_per_inst) {
+  const Layout& Y = X.Y;
+  const int n_inst = Z.n_inst_cap, open_cap = Z.open_cap, batch_alloc = Z.batch_alloc;
+  X.n_inst_cap = Z.n_inst_cap; X.open_cap = Z.open_cap; X.far_cap = Z.far_cap; X.pool_cap = Z.pool_cap; X.batch_cap = Z.batch_cap; X.batch_alloc = Z.batch_alloc;
+  X.ipm_grid_max = Z.ipm_grid_max; X.oc_grid = Z.oc_grid; X.ocb_grid = Z.ocb_grid; X.kg_blocks = Z.kg_blocks; X.concurrent_big = Z.concurrent_big;
   DevBuf& B = X.B; std::memset(&B, 0, sizeof(B));
-  B.qp_tol = QP_TOL; B.use_cutoff = 1;
-  B.cut_gate = KNOB_P("MIQP_CUT_GATE") ? std::atof(KNOB_P("MIQP_CUT_GATE")) : 1.0e-5;
-  B.opt2 = KNOB_T("MIQP_OPT2") ? std::atoi(KNOB_T("MIQP_OPT2")) : (8 << 4);   // rounding probe at nodes with at most 8 violated sites (eval_kernel)
-  B.seq_kinds = KNOB_P("MIQP_SEQ_KINDS") ? (int)std::strtoul(KNOB_P("MIQP_SEQ_KINDS"), nullptr, 0) : (5 << 8);   // plain K-way children, branching order 5 (see eval_kernel)
-  B.Y = Y; B.pool_cap = X.pool_cap; B.open_cap = open_cap; B.batch_cap = batch_cap; B.nodes_per_round = npr; B.n_inst = n_call; B.n_slots = n_slots; B.root_stride = roots_per_inst;
+  // (cut_gate, seq_kinds and the other search fields: apply_call_switches, at every call)
+  B.qp_tol = QP_TOL; B.use_cutoff = cs.nocut ? 0 : 1;
+  B.opt2 = cs.opt2;
+  B.Y = Y; B.pool_cap = X.pool_cap; B.open_cap = open_cap; B.batch_cap = Z.batch_cap; B.nodes_per_round = npr; B.n_inst = n_call; B.n_slots = n_slots; B.root_stride = roots_per_inst;
   double* dd; int* ii;
   if (!X.alloc(&dd, (size_t)n_inst * Y.dstride)) return false; B.inst_d = dd;
   if (!X.alloc(&ii, (size_t)n_inst * Y.istride)) return false; B.inst_i = ii;
   if (!X.alloc(&B.pool_fix, (size_t)X.pool_cap * Y.fixlen)) return false;
-  // the parents' solutions for the warm starts: for the first z_cap records (recycled records keep the live set at low
-  // indices) - 16384 per instance in flight, at least 2 M, within an eighth of the free memory (42 GB at 1024 in flight, 5 GB
-  // for a single solve: a large allocation costs seconds, and a context is rebuilt whenever the shape of the call changes)
-  B.z_cap = 0;
-  if (ws_on) {
-    const size_t zb = (size_t)Y.N * Y.nz * 8;
-    size_t zc = std::max<size_t>((size_t)2 << 20, (size_t)n_slots * 16384);
-    zc = std::min(zc, std::min<size_t>((size_t)X.pool_cap, free_b / 8 / zb));
-    if (!X.alloc(&B.pool_Z, zc * (size_t)Y.N * Y.nz)) return false;
-    B.z_cap = (int)zc;
-  }
-  B.ws_on = ws_on ? 1 : 0;
-  B.ws_mu = KNOB_T("MIQP_WS_MU") ? std::atof(KNOB_T("MIQP_WS_MU")) : 1.0;
-  B.ws_delta = KNOB_T("MIQP_WS_DELTA") ? std::atof(KNOB_T("MIQP_WS_DELTA")) : 1.0e-3;
+  if (cs.warm && !X.alloc(&B.pool_Z, (size_t)Z.z_cap * (size_t)Y.N * Y.nz)) return false;
+  B.z_cap = Z.z_cap;
+  B.ws_on = cs.warm ? 1 : 0; B.ws_mu = cs.ws_mu; B.ws_delta = cs.ws_delta;
   if (!X.alloc(&B.pool_count, 1)) return false;
   if (!X.alloc(&B.free_q, (size_t)X.pool_cap)) return false;
   if (!X.alloc(&B.free_head, 1)) return false;
@@ -473,36 +552,31 @@ bool ctx_prepare(DevCtx& X, const Layout& Y, int n_inst, int n_slots, int open_c
   if (!X.alloc(&B.work_counter, 1)) return false;
   if (!X.alloc(&X.ctr, 2 * CTR_SET)) return false;
   HIP_OK(hipMemset(X.ctr, 0, 2 * CTR_SET * 4));
-  X.as_cap = Y.C == 2 && X.oc_grid > 0;   // the shape has the active-set launches (whether a call uses them: MIQP_AS, read per call)
+  X.as_cap = Z.as_cap;
   X.as_on = X.as_cap;
-  if (X.as_cap && !X.alloc(&X.cls_list, (size_t)3 * batch_cap)) return false;   // the class lists of a round (large_class 1 / 2 / 3)
+  if (X.as_cap && !X.alloc(&X.cls_list, (size_t)3 * Z.batch_cap)) return false;   // the class lists of a round (large_class 1 / 2 / 3)
   if (!X.alloc(&X.as_stats, 32)) return false;
   HIP_OK(hipMemset(X.as_stats, 0, 256));
-  B.as_stats = X.as_stats; B.as_chunk = KNOB_T("MIQP_AS_CHUNK") ? std::atoi(KNOB_T("MIQP_AS_CHUNK")) : 1; B.as_quota = KNOB_T("MIQP_AS_QUOTA") ? std::atoi(KNOB_T("MIQP_AS_QUOTA")) : 0;   // (runs of 2 / 4 / 8 / 16: the standard launch 4.7 -> 5.2 / 6.6 / 7.9 / 10.3 ms - a wavefront solves ~14 nodes per launch, longer runs only lengthen its tail)
-  B.batch_A = nullptr; B.pool_A = nullptr; X.as_batch_A = nullptr; X.as_pool_A = nullptr; B.ring_M = nullptr; B.ring_head = nullptr; B.ring_doubles = 0; B.ring_margin = 0; B.batch_Mtag = nullptr; B.pool_Mtag = nullptr;
-  if (X.as_on && B.z_cap > 0 && Y.N * Y.NSLOT + 1024 < 65535) {   // the parents' active sets for the children's starts (128 B per record)
+  B.as_stats = X.as_stats; B.as_chunk = cs.as_chunk; B.as_quota = cs.as_quota;
+  X.as_batch_A = nullptr; X.as_pool_A = nullptr;
+  if (Z.as_starts) {
     if (!X.alloc(&B.batch_A, (size_t)batch_alloc * 64)) return false;
     if (!X.alloc(&B.pool_A, (size_t)B.z_cap * 64)) return false;
     // (pool_A / pool_Mtag need no initial value: a record's entries are written when the record is created - eval_kernel, lns_kernel - and roots start cold)
     HIP_OK(hipMemset(B.batch_A, 0xFF, (size_t)batch_alloc * 128));
     X.as_batch_A = B.batch_A; X.as_pool_A = B.pool_A;
-    // ... and the ring their M travels through (4 KB per node on average, at most 12.8): a quarter of the free memory, at most 96 GB
-    size_t rd = std::min<size_t>(std::min<size_t>((size_t)12 << 30, free_b / 4 / 8), std::max<size_t>((size_t)1 << 30, (size_t)n_slots * ((size_t)8 << 20)));   // doubles: 64 MB per instance in flight, at least 8 GB (a single solve: hundreds of its rounds; a large allocation costs seconds when the context is built)
-    const size_t margin = (size_t)batch_alloc * AS_MSTR + ((size_t)1 << 20);   // what one round's launches can allocate, and more
-    if (rd >= 2 * margin) {
-      if (!X.alloc(&B.ring_M, rd)) return false;
+    if (Z.ring_doubles) {
+      if (!X.alloc(&B.ring_M, Z.ring_doubles)) return false;
       if (!X.alloc(&B.ring_head, 1)) return false;
       if (!X.alloc(&B.batch_Mtag, batch_alloc)) return false;
       if (!X.alloc(&B.pool_Mtag, (size_t)B.z_cap)) return false;
       { const unsigned long long h0 = 1024ull; HIP_OK(hipMemcpy(B.ring_head, &h0, 8, hipMemcpyHostToDevice)); }
       HIP_OK(hipMemset(B.batch_Mtag, 0, (size_t)batch_alloc * 8));
-      B.ring_doubles = (unsigned long long)rd; B.ring_margin = (unsigned long long)margin;
+      B.ring_doubles = (unsigned long long)Z.ring_doubles; B.ring_margin = (unsigned long long)Z.ring_margin;
     }
   }
-  // buffers of the concurrent probe launch (two cars and fewer, on-chip kernel in use): 1024 resident blocks
-  X.probe_grid = 0;
-  if (X.oc_grid > 0 && !(KNOB_T("MIQP_PROBE_OVERLAP") && std::atoi(KNOB_T("MIQP_PROBE_OVERLAP")) == 0)) {
-    X.probe_grid = std::min(batch_alloc, 1536);
+  X.probe_grid = Z.probe_grid;
+  if (X.probe_grid > 0) {
     if (!X.alloc(&X.work_counter2, 1)) return false;
     if (!X.alloc(&X.rowstate2, (size_t)X.probe_grid * NFIELD * Y.ROWCAP)) return false;
     if (!X.alloc(&X.rowcache2, (size_t)X.probe_grid * NCACHE * Y.ROWCAP)) return false;
@@ -518,11 +592,10 @@ bool ctx_prepare(DevCtx& X, const Layout& Y, int n_inst, int n_slots, int open_c
   if (!X.alloc(&B.ovf2_list, batch_alloc)) return false;
   HIP_OK(hipMemset(B.ovf2_count, 0, 4));
   HIP_OK(hipMemset(B.ovf_count, 0, 4));
-  if (KNOB_P("MIQP_STATS")) {
+  if (cs.stats) {
     if (!X.alloc(&B.stats, 256)) return false; HIP_OK(hipMemset(B.stats, 0, 256 * 8));
     if (!X.alloc(&B.pool_origin, (size_t)X.pool_cap)) return false; HIP_OK(hipMemset(B.pool_origin, 0, (size_t)X.pool_cap));
   }
-  if (KNOB_T("MIQP_NOCUT")) B.use_cutoff = 0;   // diagnostic: every node relaxation runs to convergence (tells infeasible children from expensive ones)
   if (!X.alloc(&B.prof, 160 + 5 * 4 * 4096)) return false;
   (void)hipMemset(B.prof, 0, (160 + 5 * 4 * 4096) * 8);
   if (!X.alloc(&B.active_insts, 1)) return false;
@@ -530,6 +603,28 @@ bool ctx_prepare(DevCtx& X, const Layout& Y, int n_inst, int n_slots, int open_c
 #ifdef MIQP_PROFILE
   if (!B.pool_origin) { if (!X.alloc(&B.pool_origin, (size_t)X.pool_cap)) return false; HIP_OK(hipMemset(B.pool_origin, 0, (size_t)X.pool_cap)); }
 #endif
+  return true;
+}
+
+std::mutex g_ctx_build_mu;   // contexts are built one at a time: each sizes its pools from the memory that is free at that moment
+// `rebuilt` (optional): whether the call found no matching context and built one
+bool ctx_prepare(DevCtx& X, const Layout& Y, int n_inst, int n_slots, int open_cap, int npr, int roots_per_inst, bool clamp_open = false, int mem_div = 1, bool* rebuilt = nullptr) {
+  HIP_OK(hipSetDevice(X.device));   // the calling thread's current device (threads of solve_batch_multi each set their own)
+  const bool reuse = ctx_matches(X, Y, n_inst, n_slots, open_cap, npr, roots_per_inst, mem_div);
+  if (rebuilt) *rebuilt = !reuse;
+  if (reuse) { X.n_inst = n_inst; X.B.n_inst = n_inst; return true; }
+  std::lock_guard<std::mutex> build_lock(g_ctx_build_mu);
+  if (X.ready || !X.allocs.empty()) X.release();
+  if (!X.stream) HIP_OK(hipStreamCreate(&X.stream));
+  if (!X.ev0) { HIP_OK(hipEventCreate(&X.ev0)); HIP_OK(hipEventCreate(&X.ev1)); }
+  X.open_cap_req = open_cap; X.mem_div = mem_div < 1 ? 1 : mem_div;
+  // (the memory that is free and the CU count are read after the old context is released and before the first allocation of the new one)
+  size_t free_b = 0, total_b = 0; const bool free_known = hipMemGetInfo(&free_b, &total_b) == hipSuccess;
+  hipDeviceProp_t pr; int dv = 0; (void)hipGetDevice(&dv); int cus = 256; if (hipGetDeviceProperties(&pr, dv) == hipSuccess) cus = pr.multiProcessorCount;
+  const CtxSwitches cs = read_ctx_switches();
+  const CtxSizes Z = ctx_sizes(Y, n_inst, n_slots, open_cap, npr, roots_per_inst, clamp_open, X.mem_div, free_known, free_b, cus, cs);
+  X.Y = Y; X.n_inst = n_inst; X.n_slots = n_slots; X.npr = npr;
+  if (!ctx_alloc(X, Z, cs, n_inst, n_slots, npr, roots_per_inst)) return false;
   X.ready = true;
   return true;
 }
@@ -542,11 +637,11 @@ size_t ipm_lds_bytes(const Layout& Y) {
   size_t d = (size_t)N * NZ + (size_t)ipm_scratch_doubles(N, Y.C) + NZ + 8 + 32 + 2 * ((N + 6) / 2 + 1);
   return d * 8 + (size_t)Y.fixlen + 16;
 }
-bool multi_row_lifting_on() { const char* e = KNOB_P("MIQP_SEQ_KINDS"); return e && (std::strtoul(e, nullptr, 0) & 0x80000000ul) != 0ul; }
-size_t eval_lds_bytes(const Layout& Y) {
+bool multi_row_lifting_on(int seq_kinds) { return ((unsigned)seq_kinds & 0x80000000u) != 0u; }
+size_t eval_lds_bytes(const Layout& Y, int seq_kinds) {
   size_t d = (size_t)Y.N * Y.nz + (size_t)eval_shared_doubles(Y.C, Y.N, Y.P) + 2 * (size_t)Y.C * Y.N;   // (the slow-alternative table and the lifting's dense rows share one region)
   return d * 8 + (size_t)(2 * Y.C * Y.N + 64) * 4 + 64 * 8 + 3 * (size_t)Y.fixlen + 8 + 64
-         + (multi_row_lifting_on() ? (size_t)(LIFT_ROWS * (2 * Y.nz + 3) + Y.nz) * 8 : 0) + 64   // rows of the multi-row lifting (an experiment: MIQP_SEQ_KINDS bit 31)
+         + (multi_row_lifting_on(seq_kinds) ? (size_t)(LIFT_ROWS * (2 * Y.nz + 3) + Y.nz) * 8 : 0) + 64   // rows of the multi-row lifting (an experiment: MIQP_SEQ_KINDS bit 31)
          + (size_t)Y.fixlen + 16;                                  // ploose
 }
 
@@ -592,7 +687,7 @@ void launch_ipm_batch(DevCtx& X, const DevBuf& B, int bc, hipStream_t st, bool o
   if (X.oc_grid > 0) {
     const size_t l_oc = (size_t)oc_lds_layout(Y.N, Y.fixlen).total;
     const size_t l_ocb = (size_t)oc_lds_layout(Y.N, Y.fixlen, OC_GCAP_BIG).total;
-    const size_t l_ocb_as = Y.C == 2 && !(KNOB_T("MIQP_BIG_PAD") && std::atoi(KNOB_T("MIQP_BIG_PAD")) == 0) ? oc_big_lds_beside_as(Y) : l_ocb;
+    const size_t l_ocb_as = Y.C == 2 && X.sw.big_pad ? oc_big_lds_beside_as(Y) : l_ocb;
     const bool big = X.ocb_grid > 0;
     const bool ov = overlap && X.probe_grid > 0 && X.stream2 && bc <= 4096;   // (a full batch keeps the device busy on its own: measured no gain there, 5.4 against 5.1 s on a 2048-instance queue; single solves: median 6.0 instead of 7.0 ms)
     DevBuf Bc = B;
@@ -609,15 +704,15 @@ void launch_ipm_batch(DevCtx& X, const DevBuf& B, int bc, hipStream_t st, bool o
       int* const cs = pc ? X.ctr + CTR_SET * par : nullptr;   // [0] batch count, [1] standard launch, [2] its hand-over list, [3] the larger variant's list, [4] the larger variant, [5] the memory-backed launch behind it
       if (pc) { Bc.work_counter = cs + 1; Bc.ovf_count = cs + 2; Bc.ovf2_count = cs + 3; }
       DevBuf Bp = Bc; Bp.ovf_mode = 2; Bp.work_counter = pc ? cs + 4 : X.work_counter2; Bp.rowstate = X.rowstate2; Bp.rowcache = X.rowcache2; Bp.kgain = X.kgain2;
-      static const int big_grid_cap = KNOB_T("MIQP_BIG_GRID") ? std::atoi(KNOB_T("MIQP_BIG_GRID")) : 1 << 30;
-      const int gb = std::min(std::min(bc, big_grid_cap), std::min(X.probe_grid, X.ocb_grid));
+      const ProcessSwitches& ps = process_switches();
+      const int gb = std::min(std::min(bc, ps.big_grid_cap), std::min(X.probe_grid, X.ocb_grid));
       const bool as2 = X.as_on && pc && Y.C == 2 && X.stream3;
       const bool lists = as2 && X.stream4 && B.cls_list && X.cls_n[0] >= 0;
       // With the class lists the larger launches get the SHARE of the device their work is of the round's, not all of it: their wavefronts take a SIMD
       // each (450 / 424 registers) and are enqueued first - a full grid of them held every SIMD until the larger active-set launch was through
       // (5 of 16 ms, tools/wave_dump.py), the standard launch started behind them and never got its holes back.  Weights: SIMD time of a node of the
       // class in units of a standard node's (half a SIMD for ~0.19 ms)
-      static const double w1_ = KNOB_T("MIQP_BIG_W1") ? std::atof(KNOB_T("MIQP_BIG_W1")) : 6.0, w2_ = KNOB_T("MIQP_BIG_W2") ? std::atof(KNOB_T("MIQP_BIG_W2")) : 28.0;   // (driver's stream, launch group / standard launch: 9.10 / 8.41 ms at 5 / 20, 8.76 / 8.50 at 6 / 28, 8.87 / 8.53 at 8 / 36)
+      const double w1_ = ps.big_w1, w2_ = ps.big_w2;
       int g1s = gb, g2s = gb;
       if (lists && w1_ > 0) {
         const double n1 = X.cls_n[0], n2 = X.cls_n[1], n0 = std::max(0, bc - X.cls_n[0] - X.cls_n[1] - X.cls_n[2]);
@@ -903,94 +998,82 @@ void split_roots(const Layout& Y, const int* T, std::vector<std::vector<std::pai
   }
 }
 
+#include "solve_diag.hpp"
+
+// ---------------------------------------------------------------- the batch solve: shape of the call
 // `inflight`: instances solved concurrently (<= 0 or >= n: all of them).  With fewer than n the call is a queue drained by
 // streaming admission: an instance that is proven (or has used up its own max_solution_time, counted from its admission)
 // hands its slot to the next one at the following round.
 // `lane` / `lanes`: this call is one of `lanes` concurrent calls that share the device, each with its own context (miqp_solver_solve_stream)
-bool solve_batch_impl(miqp_solver_t* const* S, int n, int* statuses, const SplitCtx* split = nullptr, int inflight = 0, int lane = 0, int lanes = 1) {
-  // every way out of this function that is not the result loop at its end (a failed HIP call, a failed exchange) leaves "the solver
-  // could not run" behind: a caller's zero-filled status array would otherwise read as SUCCESS for instances that were never solved
-  for (int k = 0; k < n; ++k) { statuses[k] = MIQP_STATUS_FAILED_SEG_FAULT; if (S[k]) { S[k]->status = MIQP_STATUS_FAILED_SEG_FAULT; S[k]->has_sol = false; S[k]->rescache.reset(); } }
-  if (split && n != 1) return false;
-  BatchShape bs = batch_layout(S, n);
-  if (!bs.ok) { for (int k = 0; k < n; ++k) { if (S[k]) S[k]->err = bs.err; statuses[k] = MIQP_STATUS_FAILED_SEG_FAULT; } std::fprintf(stderr, "[miqp_gpu] %s\n", bs.err.c_str()); return false; }
-  const Layout& Y = bs.Y;
-  const miqp_solver_opts& O0 = S[0]->opts;
-  auto fail_all = [&](const char* why) { if (why) std::fprintf(stderr, "[miqp_gpu] %s\n", why); for (int k = 0; k < n; ++k) statuses[k] = MIQP_STATUS_FAILED_SEG_FAULT; return false; };
-  for (int k = 1; k < n; ++k) if (S[k]->opts.device != O0.device) return fail_all("instances of one batch must name the same device (use miqp_solver_solve_batch_multi to span devices)");
-  const double t_enter = wall_s();
-  DevCtx* Xp = ctx_for_device(O0.device, lane);
-  if (!Xp) return fail_all(nullptr);
-  warn_ignored_switches();
-  DevCtx& X = *Xp;
-  std::lock_guard<std::mutex> ctx_lock(X.mu);
-  if (hipSetDevice(X.device) != hipSuccess) return fail_all("hipSetDevice failed");
-  const int NS = (split || inflight <= 0 || inflight >= n) ? n : inflight;   // slots = instances in flight
+struct CallShape {
+  int n, NS, lanes;          // instances, slots = instances in flight, lanes that share the device
+  int npr, open_cap, MAXR;   // nodes per instance and round, near-list capacity asked for, root records per instance
+  bool adaptive_width; int width0, width_max;   // a single solve starts at width0 nodes per round and widens up to width_max
+  bool queue_mode, clamp_open;
+};
+// pure: the layout, the options, the sizes of the call and the switches in, the shape out.  Precedence: opts.nodes_per_round > MIQP_NPR > the rules
+CallShape plan_call(const Layout& Y, const miqp_solver_opts& O0, int n, int inflight, int lanes, bool split, const CallSwitches& sw) {
+  CallShape sh{};
+  sh.n = n; sh.lanes = lanes;
+  const int NS = sh.NS = (split || inflight <= 0 || inflight >= n) ? n : inflight;   // slots = instances in flight
   // nodes of a round, all instances together: 32768 for three and four cars (and one), 98304 for two - since the node relaxations of two cars are active-set
   // solves (round 6) a round of 32768 lasts 5-6 ms of which 1.1 ms are the serial kernels and the tail of the launch; the driver's stream at 32 k / 49 k / 65 k /
   // 97 k / 131 k / 164 k nodes per round: 1783 / 1849 / 1864 / 1911 / 1856 / 1826 solves/s (time to a proof p50 0.043 -> 0.106 s, p99 7.4 -> 4.3 s at 97 k)
   const int round_nodes = Y.C == 2 ? 98304 : 32768;
-  int npr = O0.nodes_per_round > 0 ? O0.nodes_per_round : std::max(16, std::min(16384, round_nodes / (NS * lanes)));   // (the lanes of a call keep the round width of the undivided call)
+  const bool rules = O0.nodes_per_round <= 0;
+  int npr = !rules ? O0.nodes_per_round : std::max(16, std::min(16384, round_nodes / (NS * lanes)));   // (the lanes of a call keep the round width of the undivided call)
   // three and four cars: a node relaxation costs ~15 x that of two cars (memory-backed kernel, stage vector 24 / 32), a round of 32768 nodes
   // lasts 0.13 s and an instance that shares the device gets 80 rounds in its 10 s - fewer than the levels of its first dive.  Rounds of
   // 5120 nodes (0.035 s) give the tree its depth back at a quarter less node throughput: cfg5, 16 in flight, 7 -> 11 of 16 proven in 10 s.
   // Since the re-rounding finds the first incumbents within a few rounds the depth matters less and the throughput more: 8192 nodes
   // (3072 / 5120 / 8192 / 10240 / 12288 / 16384: 14 / 14 / 15 / 14 / 14 / 14 of 16, the open gaps smallest at 8192 - 12288; profiles/r04b_heuristics_ab.txt)
-  if (O0.nodes_per_round <= 0 && Y.C >= 3 && NS > 1) npr = std::max(16, std::min(npr, 8192 / NS));
+  if (rules && Y.C >= 3 && NS > 1) npr = std::max(16, std::min(npr, 8192 / NS));
   // ... and a single solve of three or four cars takes 2048 nodes per round (16384 / 8192 / 4096 / 2048: the sixteen cfg5 seeds in 35.1 / 34.3 / 29.5 / 25.3 s, 15 proven each time;
   // seed 15 8.5 -> 4.5 s): its rounds are as long as their slowest node whatever their width (~25 ms), so what a narrower round gives up is node throughput it could not use for the proof anyway
-  if (O0.nodes_per_round <= 0 && Y.C >= 3 && NS == 1) npr = std::min(npr, 2048);
+  if (rules && Y.C >= 3 && NS == 1) npr = std::min(npr, 2048);
   // ... and so does a single solve of one or two cars (round 5): 2048 nodes are one per resident wavefront of the standard on-chip launch (256 CUs x 8) - a
   // wider round lasts longer (several nodes per wavefront) and solves nodes that the incumbents of a narrower round would have pruned.  Measured on seeds 0-95
   // (tools/single_latency.py, profiles/r05_single_latency.txt), 16384 -> 2048 nodes per round: p99 58 -> 47 ms at gap 0.1 (seed 62: 55 k -> 26 k node
   // relaxations), 92 -> 75 ms at 0.01; p50 / p90 unchanged (5 / 18 ms); 1024: 51 / 76 ms (too narrow: more rounds), 4096: 51 / 86, 8192: 58 / 90
-  if (O0.nodes_per_round <= 0 && Y.C <= 2 && NS == 1) npr = std::min(npr, 2048);
-  if (O0.nodes_per_round <= 0 && KNOB_P("MIQP_NPR")) npr = std::max(1, std::atoi(KNOB_P("MIQP_NPR")));  // tuning knob
+  if (rules && Y.C <= 2 && NS == 1) npr = std::min(npr, 2048);
+  if (rules && sw.npr > 0) npr = sw.npr;
   // A single solve starts narrow (above) and WIDENS its rounds once it is bound-limited: the incumbent has not moved for 32 rounds and the
   // near list offers eight rounds' worth of eligible nodes - then the tree needs node throughput, not fresher incumbents (cfg5 seed 11: 1.61 / 2.17 / 2.92 M relaxations in 10 s at
   // 1024 / 2048 / 4096 nodes per round).  The batch arrays are sized for the widest round, select_kernel caps at width_cap
-  const bool adaptive_width = NS == 1 && !split && O0.nodes_per_round <= 0 && !KNOB_P("MIQP_NPR");
-  const int width0 = npr, width_max = Y.C >= 3 ? 4096 : 16384;   // (three and four cars: 4096 - cfg5 seed 11 relaxes 2.57 / 3.21 / 3.09 / 2.96 M nodes in its 10 s at 2048 / 4096 / 8192 / 16384, its gap 2.1 / 1.8 / 3.4 / 45 %)
-  if (adaptive_width) npr = width_max;
-  int open_cap = O0.max_open_nodes > 0 ? O0.max_open_nodes : (KNOB_P("MIQP_OPEN_CAP") ? std::atoi(KNOB_P("MIQP_OPEN_CAP")) : std::max(1 << 17, std::min(1 << 20, (1 << 28) / NS)));   // near lists: 1 M entries per instance up to n = 256 (10 GB of list entries), 262144 at n = 1024; records are shared
+  sh.adaptive_width = NS == 1 && !split && rules && sw.npr <= 0;
+  sh.width0 = npr; sh.width_max = Y.C >= 3 ? 4096 : 16384;   // (three and four cars: 4096 - cfg5 seed 11 relaxes 2.57 / 3.21 / 3.09 / 2.96 M nodes in its 10 s at 2048 / 4096 / 8192 / 16384, its gap 2.1 / 1.8 / 3.4 / 45 %)
+  if (sh.adaptive_width) npr = sh.width_max;
+  int open_cap = O0.max_open_nodes > 0 ? O0.max_open_nodes : (sw.open_cap > 0 ? sw.open_cap : std::max(1 << 17, std::min(1 << 20, (1 << 28) / NS)));   // near lists: 1 M entries per instance up to n = 256 (10 GB of list entries), 262144 at n = 1024; records are shared
   if (open_cap < 64) open_cap = 64;
   if (split && open_cap < SPLIT_MAXROOTS + 4 + 64) open_cap = SPLIT_MAXROOTS + 4 + 64;   // the root records of a tree split are the head of the list
   // (list entries - 40 B per open node - must fit an eighth of the free device memory: ctx_prepare cuts the capacity when it builds the context)
   if ((size_t)NS * npr >= ((size_t)1 << 20)) npr = (int)((((size_t)1 << 20) - 1) / NS);
-  const int MAXR = split ? SPLIT_MAXROOTS + 4 : 5;   // root records per instance: the root (or this rank's roots of a tree split), the MIP starts and their repair roots
-  size_t l_ipm = ipm_lds_bytes(Y), l_eval = eval_lds_bytes(Y);
-  bool ctx_built = false;
-  {
-    // the fallible part of the set-up (device buffers, kernel attributes).  In a tree split the ranks agree on its outcome with
-    // one exchange before the first round: a rank that failed alone would otherwise leave its peers waiting in their all-reduce
-    ctx_built = !(X.ready && same_layout(X.Y, Y) && n <= X.n_inst_cap && X.n_slots == NS && X.open_cap_req == open_cap && X.npr == npr && X.B.root_stride == MAXR && X.mem_div == lanes);
-    bool setup_ok = ctx_prepare(X, Y, n, NS, open_cap, npr, MAXR, O0.max_open_nodes <= 0, lanes);
-    open_cap = X.open_cap;
-    if (setup_ok && (l_ipm > 160 * 1024 || l_eval > 160 * 1024)) { std::fprintf(stderr, "[miqp_gpu] instance too large for LDS (%zu bytes)\n", l_ipm); setup_ok = false; }
-    if (setup_ok && !set_kernel_lds(Y, l_ipm, l_eval)) setup_ok = false;
-    if (split) {
-      unsigned long long w = setup_ok ? 1ull : 0ull;
-      if (split->fn(split->user, 0, &w, 1, 0) != 0) return fail_all("set-up exchange failed");
-      if (setup_ok && w == 0ull) return fail_all("another rank of the tree split failed its set-up");
-    }
-    if (!setup_ok) return fail_all(nullptr);
-  }
-  const double t_ctx = wall_s() - t_enter;
-  DevBuf& B = X.B;
-  // ---- host tables, step-1 presolve
+  sh.npr = npr; sh.open_cap = open_cap;
+  sh.MAXR = split ? SPLIT_MAXROOTS + 4 : 5;   // root records per instance: the root (or this rank's roots of a tree split), the MIP starts and their repair roots
+  sh.queue_mode = NS < n; sh.clamp_open = O0.max_open_nodes <= 0;
+  return sh;
+}
+
+// ---------------------------------------------------------------- host tables, step-1 presolve, root records
+struct HostTables {
   // (not value-initialised: compile_instance writes every word of an instance's slice, and zeroing 1.4 GB for the 51 200 instances of the driver's stream
   // on the calling thread came before the threads below could start)
-  const size_t nD_ = (size_t)n * Y.dstride, nT_ = (size_t)n * Y.istride;
-  std::unique_ptr<double[]> hD_own(new double[nD_]); std::unique_ptr<int[]> hT_own(new int[nT_]);
-  double* const hD = hD_own.get(); int* const hT = hT_own.get();
-  std::vector<double> h_const(n, 0.0), h_gap(n), h_tlim(n);
-  std::vector<int> h_done(n, 0);
-  std::vector<signed char> roots; roots.reserve((size_t)MAXR * n * Y.fixlen);
-  std::vector<int> on((size_t)n * MAXR, 0), od((size_t)n * MAXR, 0), oc(n, 0);   // root records of every instance: the head of its open list at admission
-  int nrec = 0;
-  auto add_root = [&](int k, const std::vector<signed char>& fx, int depth_word) { roots.insert(roots.end(), fx.begin(), fx.end()); on[(size_t)k * MAXR + oc[k]] = nrec++; od[(size_t)k * MAXR + oc[k]] = depth_word; oc[k]++; };
-  int active = 0;
-  // per instance (independent, spread over host threads): tables, step-0 check, the fix records of its roots
+  std::unique_ptr<double[]> D; std::unique_ptr<int[]> T; size_t nD = 0, nT = 0;
+  std::vector<double> h_const, h_gap, h_tlim;
+  std::vector<int> h_done;              // 1: never starts (infeasible first step, no root on this rank)
+  std::vector<signed char> roots;       // fix records of all roots, in the order of their record numbers
+  std::vector<int> on, od, oc; int nrec = 0;   // root records of every instance (record, depth word; count): the head of its open list at admission
+};
+
+// per instance (independent, spread over host threads): tables, step-0 check, the fix records of its roots, the raw model sizes
+void prepare_instances(miqp_solver_t* const* S, const Layout& Y, const CallShape& sh, const SplitCtx* split, HostTables& H) {
+  const int n = sh.n, MAXR = sh.MAXR;
+  H.nD = (size_t)n * Y.dstride; H.nT = (size_t)n * Y.istride;
+  H.D.reset(new double[H.nD]); H.T.reset(new int[H.nT]);
+  double* const hD = H.D.get(); int* const hT = H.T.get();
+  H.h_const.assign(n, 0.0); H.h_gap.resize(n); H.h_tlim.resize(n); H.h_done.assign(n, 0);
+  H.roots.reserve((size_t)MAXR * n * Y.fixlen);
+  H.on.assign((size_t)n * MAXR, 0); H.od.assign((size_t)n * MAXR, 0); H.oc.assign(n, 0);
   std::vector<std::vector<std::vector<signed char>>> inst_roots(n);
   std::vector<std::vector<int>> inst_root_depth(n);
   std::vector<char> h_feas0(n, 0);
@@ -999,7 +1082,7 @@ bool solve_batch_impl(miqp_solver_t* const* S, int n, int* statuses, const Split
     compile_instance(s->inst, Y, &hD[(size_t)k * Y.dstride], &hT[(size_t)k * Y.istride]);
     HostGeo G{s->inst, Y, &hD[(size_t)k * Y.dstride], &hT[(size_t)k * Y.istride]};
     double cobj = 0; bool feas0 = step0_check(G, cobj);
-    h_const[k] = cobj; h_gap[k] = s->opts.gap_override >= 0 ? s->opts.gap_override : s->inst.gap; h_tlim[k] = s->inst.tilim;
+    H.h_const[k] = cobj; H.h_gap[k] = s->opts.gap_override >= 0 ? s->opts.gap_override : s->inst.gap; H.h_tlim[k] = s->inst.tilim;
     h_feas0[k] = feas0 ? 1 : 0;
     auto& R = inst_roots[k];
     if (feas0 && !split) R.emplace_back(Y.fixlen, (signed char)-1);
@@ -1030,533 +1113,507 @@ bool solve_batch_impl(miqp_solver_t* const* S, int n, int* statuses, const Split
     s->props = miqp_solution_properties_c{}; s->props.NrConstraints = rows; s->props.NrBinaryVariables = bin; s->props.NrFloatVariables = cont;
     s->props.NonZeroCoefficients = nnz;
   };
-  { static const int prep_cap = KNOB_T("MIQP_PREP_THREADS") ? std::atoi(KNOB_T("MIQP_PREP_THREADS")) : 16;   // (the 51 200 instances of the driver's stream on a 2 x 64-core host: 0.38 / 0.44 / 0.57 / 0.76 s at 16 / 32 / 64 / 128 threads - allocator and first-touch contention, not arithmetic)
-    const int nth = std::max(1, std::min<int>({n / 8, (int)std::thread::hardware_concurrency(), prep_cap}));
-    if (nth <= 1) for (int k = 0; k < n; ++k) prepare_one(k);
-    else {
-      std::atomic<int> next{0}; std::vector<std::thread> th;
-      for (int t = 0; t < nth; ++t) th.emplace_back([&] { for (int k = next.fetch_add(1); k < n; k = next.fetch_add(1)) prepare_one(k); });
-      for (auto& t : th) t.join();
-    } }
-  for (int k = 0; k < n; ++k) {
-    if (!h_feas0[k]) h_done[k] = 1;
-    for (size_t q = 0; q < inst_roots[k].size(); ++q) add_root(k, inst_roots[k][q], inst_root_depth[k][q]);
-    if (oc[k] > 0) active++; else h_done[k] = 1;   // (a rank of a tree split may own no root)
+  const int nth = std::max(1, std::min<int>({n / 8, (int)std::thread::hardware_concurrency(), process_switches().prep_threads}));
+  if (nth <= 1) for (int k = 0; k < n; ++k) prepare_one(k);
+  else {
+    std::atomic<int> next{0}; std::vector<std::thread> th;
+    for (int t = 0; t < nth; ++t) th.emplace_back([&] { for (int k = next.fetch_add(1); k < n; k = next.fetch_add(1)) prepare_one(k); });
+    for (auto& t : th) t.join();
   }
-  const double t_tables = wall_s() - t_enter - t_ctx;
-  { double gmin = 1.0; for (int k = 0; k < n; ++k) gmin = std::min(gmin, h_gap[k]);
-    const double ftol = KNOB_T("MIQP_QPTOL_F") ? std::atof(KNOB_T("MIQP_QPTOL_F")) : 1e-4;   // (tuning knob)
-    const double tolcap = KNOB_T("MIQP_QPTOL") ? std::atof(KNOB_T("MIQP_QPTOL")) : QP_TOL;
-    B.qp_tol = std::min(tolcap, std::max(1e-12, ftol * gmin)); }  // node relaxations: accurate to a small fraction of the MIP gap
-  hipStream_t st = X.stream;
-  HIP_OK(hipMemcpyAsync((void*)B.inst_d, hD, nD_ * 8, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync((void*)B.inst_i, hT, nT_ * 4, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(B.pool_fix, roots.data(), roots.size(), hipMemcpyHostToDevice, st));
-  int pool0 = nrec;
-  if (B.pool_big && nrec > 0) HIP_OK(hipMemsetAsync(B.pool_big, 0, (size_t)nrec, st));   // the root records start unmarked (children are marked or cleared when they are written)
+  for (int k = 0; k < n; ++k) {
+    if (!h_feas0[k]) H.h_done[k] = 1;
+    for (size_t q = 0; q < inst_roots[k].size(); ++q) {
+      const auto& fx = inst_roots[k][q];
+      H.roots.insert(H.roots.end(), fx.begin(), fx.end()); H.on[(size_t)k * MAXR + H.oc[k]] = H.nrec++; H.od[(size_t)k * MAXR + H.oc[k]] = inst_root_depth[k][q]; H.oc[k]++;
+    }
+    if (H.oc[k] == 0) H.h_done[k] = 1;   // (a rank of a tree split may own no root)
+  }
+}
+
+// every copy and reset that a call starts from: the tables and roots up, the per-instance and per-slot state of the context back to "nothing yet"
+bool upload_and_reset(DevCtx& X, const HostTables& H, const CallShape& sh) {
+  const DevBuf& B = X.B; const Layout& Y = X.Y; hipStream_t st = X.stream; const int n = sh.n, NS = sh.NS;
+  HIP_OK(hipMemcpyAsync((void*)B.inst_d, H.D.get(), H.nD * 8, hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync((void*)B.inst_i, H.T.get(), H.nT * 4, hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(B.pool_fix, H.roots.data(), H.roots.size(), hipMemcpyHostToDevice, st));
+  const int pool0 = H.nrec;
+  if (B.pool_big && H.nrec > 0) HIP_OK(hipMemsetAsync(B.pool_big, 0, (size_t)H.nrec, st));   // the root records start unmarked (children are marked or cleared when they are written)
   HIP_OK(hipMemcpyAsync(B.pool_count, &pool0, 4, hipMemcpyHostToDevice, st));
   HIP_OK(hipMemsetAsync(B.free_head, 0, 4, st)); HIP_OK(hipMemsetAsync(B.free_tail, 0, 4, st)); HIP_OK(hipMemsetAsync(B.free_limit, 0, 4, st));
-  HIP_OK(hipMemcpyAsync((void*)B.root_node, on.data(), on.size() * 4, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync((void*)B.root_depth, od.data(), od.size() * 4, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync((void*)B.root_cnt, oc.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync((void*)B.root_node, H.on.data(), H.on.size() * 4, hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync((void*)B.root_depth, H.od.data(), H.od.size() * 4, hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync((void*)B.root_cnt, H.oc.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
   HIP_OK(hipMemsetAsync(B.open_count, 0, (size_t)n * 4, st));
   HIP_OK(hipMemsetAsync(B.inst_slot, 0xFF, (size_t)n * 4, st)); HIP_OK(hipMemsetAsync(B.slot_inst, 0xFF, (size_t)NS * 4, st));
   HIP_OK(hipMemsetAsync(B.inst_kill, 0, (size_t)n * 4, st));
   HIP_OK(hipMemsetAsync(B.slot_demand, 0, (size_t)NS * 4, st));
-  { std::vector<int> t0_(NS, npr); HIP_OK(hipMemcpyAsync(B.slot_take, t0_.data(), (size_t)NS * 4, hipMemcpyHostToDevice, st)); HIP_OK(hipStreamSynchronize(st)); }
-  B.base_take = std::max(1, std::min(npr, KNOB_T("MIQP_BASE_TAKE") ? std::atoi(KNOB_T("MIQP_BASE_TAKE")) : 8));
+  { std::vector<int> t0_(NS, sh.npr); HIP_OK(hipMemcpyAsync(B.slot_take, t0_.data(), (size_t)NS * 4, hipMemcpyHostToDevice, st)); HIP_OK(hipStreamSynchronize(st)); }
+  HIP_OK(hipMemsetAsync(B.far_count, 0, (size_t)n * 4, st)); HIP_OK(hipMemsetAsync(B.far_minkey, 0xFF, (size_t)n * 8, st));
+  HIP_OK(hipMemsetAsync(B.inst_mode, 0, (size_t)n * 4, st));
+  HIP_OK(hipMemsetAsync(B.inc_key, 0xFF, (size_t)n * 8, st));
+  HIP_OK(hipMemsetAsync(B.inc_seen, 0xFF, (size_t)n * 8, st));
+  HIP_OK(hipMemsetAsync(B.inc_fix, 0xFF, (size_t)n * Y.fixlen, st));   // no incumbent yet: every disjunction undecided
+  if (B.inc_Mtag) HIP_OK(hipMemsetAsync(B.inc_Mtag, 0, (size_t)n * 8, st));
+  const std::vector<double> big(n, 1e300);
+  HIP_OK(hipMemcpyAsync(B.inc_obj, big.data(), n * 8, hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(B.inc_ext, big.data(), n * 8, hipMemcpyHostToDevice, st)); HIP_OK(hipMemcpyAsync(B.near_thr, big.data(), n * 8, hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(B.lower_bound, big.data(), n * 8, hipMemcpyHostToDevice, st)); HIP_OK(hipStreamSynchronize(st));
+  HIP_OK(hipMemcpyAsync(B.inst_done, H.h_done.data(), n * 4, hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemsetAsync(B.inst_flags, 0, (size_t)n * 4, st));
+  HIP_OK(hipMemcpyAsync(B.inst_gap, H.h_gap.data(), n * 8, hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(B.inst_const, H.h_const.data(), n * 8, hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemsetAsync(B.inst_nodes, 0, (size_t)n * 8, st));
+  HIP_OK(hipMemsetAsync(B.inst_iters, 0, (size_t)n * 8, st));
+  HIP_OK(hipMemsetAsync(B.inst_ninc, 0, (size_t)n * 4, st));
+  HIP_OK(hipMemsetAsync(B.as_stats, 0, 256, st));
+  HIP_OK(hipMemsetAsync(B.inst_lns, 0, (size_t)n * 4, st));
+  HIP_OK(hipMemcpyAsync(B.inst_lns_obj, big.data(), (size_t)n * 8, hipMemcpyHostToDevice, st)); HIP_OK(hipStreamSynchronize(st));
+  HIP_OK(hipMemsetAsync(B.active_insts, 0, 4, st));   // admit_kernel counts the instances in as they enter
+  HIP_OK(hipMemsetAsync(B.stat_rowiters, 0, 8, st));
+  HIP_OK(hipStreamSynchronize(st));
+  return true;
+}
+
+// call lifetime: the search fields of DevBuf, read at every call (a context is reused by every later call of the same shape)
+void apply_call_switches(DevCtx& X, const CallShape& sh, const CallSwitches& sw, const std::vector<double>& h_gap) {
+  DevBuf& B = X.B; const Layout& Y = X.Y; const int NS = sh.NS;
+  { double gmin = 1.0; for (double g : h_gap) gmin = std::min(gmin, g);
+    const double ftol = knob_double(KNOB_T("MIQP_QPTOL_F"), 1e-4);   // (tuning knob)
+    const double tolcap = knob_double(KNOB_T("MIQP_QPTOL"), QP_TOL);
+    B.qp_tol = std::min(tolcap, std::max(1e-12, ftol * gmin)); }  // node relaxations: accurate to a small fraction of the MIP gap
+  B.base_take = std::max(1, std::min(sh.npr, knob_int(KNOB_T("MIQP_BASE_TAKE"), 8)));
   // Batch shares (share_kernel).  A QUEUE (more instances than slots: admissions go on while the old instances run against their limits): half
   // of the batch is shared evenly as a floor, the rest goes by admission order up to 256 nodes per instance - an instance that waits for its
   // turn no longer crawls at 8 nodes per round (its tree then costs 3-4 x the nodes, tools/crowd_probe.py), and narrow shares cost the fewest
   // nodes in all; measured on the 12-step bench stream: 1010 -> 1160 solves/s, 99.57 -> 99.39 % proven, p95 6.9 -> 4.5 s (the whole curve:
   // profiles/r04_share_policy.txt).  ONE batch with every instance in flight from the start (cfg4's 256, cfg5's 16): all deadlines are the same and
   // serving a few instances to their end frees the device for the others - admission order up to 1024 each, no floor (cfg5: 11 of 16 proven against 5).
-  const bool queue_mode = NS < n;
-  B.share_cap = std::max(1, KNOB_T("MIQP_SHARE_CAP") ? std::atoi(KNOB_T("MIQP_SHARE_CAP")) : (queue_mode ? 256 : 1024));
-  B.floor_pct = std::max(0, std::min(100, KNOB_T("MIQP_FLOOR_PCT") ? std::atoi(KNOB_T("MIQP_FLOOR_PCT")) : (queue_mode ? 50 : 0)));
-  B.lns_narrow = std::max(0, KNOB_T("MIQP_LNS_NARROW") ? std::atoi(KNOB_T("MIQP_LNS_NARROW")) : 512);   // width of a round that carries local-search leaves (0: as wide as any)
-  B.defer_cap = KNOB_T("MIQP_DEFER") ? std::atoi(KNOB_T("MIQP_DEFER")) : (Y.C >= 3 ? 24 : 0);   // (see ipm_kernel.  Measured on cfg5 at 0 / 16 / 20 / 24: seed 8 0.96 / 0.85 / 0.78 / 0.77 s, seed 14 0.75 / 0.67 / 0.65 / 0.66 s, seed 15 2.47 / 2.62 / 2.39 / 2.42 s, node relaxations in seed 11's 10 s 2.22 / 2.25 / 2.43 / 2.49 M, sixteen in flight 3.33 / 3.71 / 3.42 / 3.49 M.  Two cars (both on-chip variants have the same exit): OFF - the bench on 8 steps at 0 / 16 / 18 / 20 / 24 / 28: 1160 / 1174 / 1176-1182 / 1172 / 1156 / 1160 solves/s (the standard launch 10.0 -> 9.2 ms but 6 % more nodes per instance), single solves p99 46 -> 44 ms; and cfg3 seed 1913 - the pinned hard instance of test_local_search_changes_the_order_not_the_answer - 135 k -> 327 k nodes: a result that arrives a round late reorders the local search's chains)
-  B.probe_itcap0 = KNOB_T("MIQP_PROBE_ITCAP0") ? std::atoi(KNOB_T("MIQP_PROBE_ITCAP0")) : (Y.C >= 3 ? 0 : 40);   // (the cap while the instance has no incumbent)
-  B.pump_max = std::max(0, std::min(15, KNOB_P("MIQP_PUMP") ? std::atoi(KNOB_P("MIQP_PUMP")) : 6));   // re-rounding of infeasible rounding probes (eval_kernel)
-  B.pump_inc = KNOB_T("MIQP_PUMP_INC") ? std::atoi(KNOB_T("MIQP_PUMP_INC")) : (Y.C >= 3 ? 1 : 0);   // re-rounding also with an incumbent (probes whose OBJECTIVE is below it): three and four cars - cfg5 seed 15 proven in 8 s, the gaps of the two seeds left at 10 s with 16 in flight 0.38 / 0.32 -> 0.09 / 0.03; two cars: the probes it lets converge are the critical path of a round (single-solve p99 62 -> 72 ms, queue -1 %)
-  B.young_nodes = std::max(0, KNOB_T("MIQP_YOUNG_NODES") ? std::atoi(KNOB_T("MIQP_YOUNG_NODES")) : 0);
-  B.probe_room = KNOB_T("MIQP_PROBE_ROOM") ? std::atof(KNOB_T("MIQP_PROBE_ROOM")) : 0.0;
-  B.live_inc = KNOB_T("MIQP_LIVE_INC") ? std::atoi(KNOB_T("MIQP_LIVE_INC")) : 0;
-  B.probe_every = KNOB_T("MIQP_PROBE_EVERY") ? std::atoi(KNOB_T("MIQP_PROBE_EVERY")) : 1;
-  B.probe_itcap = KNOB_T("MIQP_PROBE_ITCAP") ? std::atoi(KNOB_T("MIQP_PROBE_ITCAP")) : (Y.C >= 3 ? 0 : 24);   // (three and four cars: no cap - EVERY probe of the phase without incumbent hit it there, at 25 iterations: infeasible roundings take 36-48, and it is their least-violation solution that the re-rounding needs)   // (0: never; solved probes take 9-24 iterations; 40 until round 4: the heuristic nodes - probes, local-search leaves - are the critical path of a single solve's round: p99 99 -> 80 ms at 24)
-  B.probe_margin = KNOB_T("MIQP_PROBE_MARGIN") ? std::atof(KNOB_T("MIQP_PROBE_MARGIN")) : 0.25;   // (0: every disjunction of a probe fixed, as in round 2)
-  B.det_ties = KNOB_T("MIQP_DET_TIES") ? std::atoi(KNOB_T("MIQP_DET_TIES")) : 1;
-  B.window_pct = std::max(1, std::min(100, KNOB_T("MIQP_WINDOW") ? std::atoi(KNOB_T("MIQP_WINDOW")) : 100));
-  HIP_OK(hipMemsetAsync(B.far_count, 0, (size_t)n * 4, st)); HIP_OK(hipMemsetAsync(B.far_minkey, 0xFF, (size_t)n * 8, st));
-  HIP_OK(hipMemsetAsync(B.inst_mode, 0, (size_t)n * 4, st));
-
-  HIP_OK(hipMemsetAsync(B.inc_key, 0xFF, (size_t)n * 8, st));
-  HIP_OK(hipMemsetAsync(B.inc_seen, 0xFF, (size_t)n * 8, st));
-  HIP_OK(hipMemsetAsync(B.inc_fix, 0xFF, (size_t)n * Y.fixlen, st));   // no incumbent yet: every disjunction undecided
-  if (B.inc_Mtag) HIP_OK(hipMemsetAsync(B.inc_Mtag, 0, (size_t)n * 8, st));
-  B.lns_warm = !(KNOB_T("MIQP_LNS_WARM") && std::atoi(KNOB_T("MIQP_LNS_WARM")) == 0);
-  { std::vector<double> big(n, 1e300); HIP_OK(hipMemcpyAsync(B.inc_obj, big.data(), n * 8, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(B.inc_ext, big.data(), n * 8, hipMemcpyHostToDevice, st)); HIP_OK(hipMemcpyAsync(B.near_thr, big.data(), n * 8, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(B.lower_bound, big.data(), n * 8, hipMemcpyHostToDevice, st)); HIP_OK(hipStreamSynchronize(st)); }
-  HIP_OK(hipMemcpyAsync(B.inst_done, h_done.data(), n * 4, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemsetAsync(B.inst_flags, 0, (size_t)n * 4, st));
-  HIP_OK(hipMemcpyAsync(B.inst_gap, h_gap.data(), n * 8, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(B.inst_const, h_const.data(), n * 8, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemsetAsync(B.inst_nodes, 0, (size_t)n * 8, st));
-  HIP_OK(hipMemsetAsync(B.inst_iters, 0, (size_t)n * 8, st));
-  HIP_OK(hipMemsetAsync(B.inst_ninc, 0, (size_t)n * 4, st));
-  HIP_OK(hipMemsetAsync(B.as_stats, 0, 256, st));
-  HIP_OK(hipMemsetAsync(B.inst_lns, 0, (size_t)n * 4, st));
-  { std::vector<double> big_(n, 1e300); HIP_OK(hipMemcpyAsync(B.inst_lns_obj, big_.data(), (size_t)n * 8, hipMemcpyHostToDevice, st)); HIP_OK(hipStreamSynchronize(st)); }
-  B.lns_step = KNOB_T("MIQP_LNS_STEP") ? std::atof(KNOB_T("MIQP_LNS_STEP")) : 0.0;
-  // (read per call, not only when the device context is built: a context is reused by every later call of the same shape)
-  B.cut_gate = KNOB_P("MIQP_CUT_GATE") ? std::atof(KNOB_P("MIQP_CUT_GATE")) : 1.0e-5;
-  B.seq_kinds = KNOB_P("MIQP_SEQ_KINDS") ? (int)std::strtoul(KNOB_P("MIQP_SEQ_KINDS"), nullptr, 0) : (5 << 8);
+  B.share_cap = std::max(1, knob_int(KNOB_T("MIQP_SHARE_CAP"), sh.queue_mode ? 256 : 1024));
+  B.floor_pct = std::max(0, std::min(100, knob_int(KNOB_T("MIQP_FLOOR_PCT"), sh.queue_mode ? 50 : 0)));
+  B.lns_narrow = std::max(0, knob_int(KNOB_T("MIQP_LNS_NARROW"), 512));   // width of a round that carries local-search leaves (0: as wide as any)
+  B.defer_cap = knob_int(KNOB_T("MIQP_DEFER"), Y.C >= 3 ? 24 : 0);   // (see ipm_kernel.  Measured on cfg5 at 0 / 16 / 20 / 24: seed 8 0.96 / 0.85 / 0.78 / 0.77 s, seed 14 0.75 / 0.67 / 0.65 / 0.66 s, seed 15 2.47 / 2.62 / 2.39 / 2.42 s, node relaxations in seed 11's 10 s 2.22 / 2.25 / 2.43 / 2.49 M, sixteen in flight 3.33 / 3.71 / 3.42 / 3.49 M.  Two cars (both on-chip variants have the same exit): OFF - the bench on 8 steps at 0 / 16 / 18 / 20 / 24 / 28: 1160 / 1174 / 1176-1182 / 1172 / 1156 / 1160 solves/s (the standard launch 10.0 -> 9.2 ms but 6 % more nodes per instance), single solves p99 46 -> 44 ms; and cfg3 seed 1913 - the pinned hard instance of test_local_search_changes_the_order_not_the_answer - 135 k -> 327 k nodes: a result that arrives a round late reorders the local search's chains)
+  B.probe_itcap0 = knob_int(KNOB_T("MIQP_PROBE_ITCAP0"), Y.C >= 3 ? 0 : 40);   // (the cap while the instance has no incumbent)
+  B.pump_max = std::max(0, std::min(15, knob_int(KNOB_P("MIQP_PUMP"), 6)));   // re-rounding of infeasible rounding probes (eval_kernel)
+  B.pump_inc = knob_int(KNOB_T("MIQP_PUMP_INC"), Y.C >= 3 ? 1 : 0);   // re-rounding also with an incumbent (probes whose OBJECTIVE is below it): three and four cars - cfg5 seed 15 proven in 8 s, the gaps of the two seeds left at 10 s with 16 in flight 0.38 / 0.32 -> 0.09 / 0.03; two cars: the probes it lets converge are the critical path of a round (single-solve p99 62 -> 72 ms, queue -1 %)
+  B.young_nodes = std::max(0, knob_int(KNOB_T("MIQP_YOUNG_NODES"), 0));
+  B.probe_room = knob_double(KNOB_T("MIQP_PROBE_ROOM"), 0.0);
+  B.live_inc = knob_int(KNOB_T("MIQP_LIVE_INC"), 0);
+  B.probe_every = knob_int(KNOB_T("MIQP_PROBE_EVERY"), 1);
+  B.probe_itcap = knob_int(KNOB_T("MIQP_PROBE_ITCAP"), Y.C >= 3 ? 0 : 24);   // (three and four cars: no cap - EVERY probe of the phase without incumbent hit it there, at 25 iterations: infeasible roundings take 36-48, and it is their least-violation solution that the re-rounding needs)   // (0: never; solved probes take 9-24 iterations; 40 until round 4: the heuristic nodes - probes, local-search leaves - are the critical path of a single solve's round: p99 99 -> 80 ms at 24)
+  B.probe_margin = knob_double(KNOB_T("MIQP_PROBE_MARGIN"), 0.25);   // (0: every disjunction of a probe fixed, as in round 2)
+  B.det_ties = knob_int(KNOB_T("MIQP_DET_TIES"), 1);
+  B.window_pct = std::max(1, std::min(100, knob_int(KNOB_T("MIQP_WINDOW"), 100)));
+  B.lns_warm = !knob_off(KNOB_T("MIQP_LNS_WARM"));
+  B.lns_step = knob_double(KNOB_T("MIQP_LNS_STEP"), 0.0);
+  B.cut_gate = knob_double(KNOB_P("MIQP_CUT_GATE"), 1.0e-5);
+  B.seq_kinds = sw.seq_kinds;
   // a single solve sends its re-roundable rounding probes to the active-set launch first (the interior point - up to 40 iterations of 70 us on the
   // critical path of its round - only sees the ones that turn out infeasible, a round later): seeds 0-95 p50 5.0 -> 4.0 ms at gap 0.1, 5.7 -> 5.0 at
   // 0.01, p90 / p99 unchanged; a queue keeps the direct route (1898 against 1868 solves/s on the driver's stream)
-  B.as_probe_first = KNOB_T("MIQP_AS_PROBE_FIRST") ? std::atoi(KNOB_T("MIQP_AS_PROBE_FIRST")) : (NS == 1 ? 1 : 0);
-  { const char* e = KNOB_P("MIQP_AS"); X.as_on = X.as_cap && !(e && std::atoi(e) == 0);   // (per call, like the other search switches: a context is reused by later calls of the same shape)
-    B.batch_A = X.as_on ? X.as_batch_A : nullptr; B.pool_A = X.as_on ? X.as_pool_A : nullptr; }
-  B.lns_mode = KNOB_P("MIQP_LNS") ? std::atoi(KNOB_P("MIQP_LNS")) : 45;
+  B.as_probe_first = knob_int(KNOB_T("MIQP_AS_PROBE_FIRST"), NS == 1 ? 1 : 0);
+  X.as_on = X.as_cap && !knob_off(KNOB_P("MIQP_AS"));
+  B.batch_A = X.as_on ? X.as_batch_A : nullptr; B.pool_A = X.as_on ? X.as_pool_A : nullptr;
+  B.lns_mode = knob_int(KNOB_P("MIQP_LNS"), 45);
 #ifndef MIQP_TUNING
   B.lns_mode &= 127;   // (bits 7-9: the neighbourhood sub-problems of round 4 - measured without effect, DESIGN.md 2b - exist in a tuning build only)
 #endif
-  B.lns_min_nodes = KNOB_T("MIQP_LNS_MIN") ? std::atoi(KNOB_T("MIQP_LNS_MIN")) : (NS == 1 ? 500 : 2000);   // (a single solve: sooner - 90 % quantile of seeds 0-95 24 -> 19 ms; a queue at 500: 1 % slower)
-  HIP_OK(hipMemsetAsync(B.active_insts, 0, 4, st));   // admit_kernel counts the instances in as they enter
-  HIP_OK(hipMemsetAsync(B.stat_rowiters, 0, 8, st));
-  HIP_OK(hipStreamSynchronize(st));
+  B.lns_min_nodes = knob_int(KNOB_T("MIQP_LNS_MIN"), NS == 1 ? 500 : 2000);   // (a single solve: sooner - 90 % quantile of seeds 0-95 24 -> 19 ms; a queue at 500: 1 % slower)
+  X.sw = sw;
+}
 
-  // ---- rounds
-  double t0 = wall_s();
-  const double t_setup = t0 - t_enter;
-  double tlim = 0; for (int k = 0; k < n; ++k) tlim = std::max(tlim, h_tlim[k]);
-  HIP_OK(hipEventRecord(X.ev0, st));
-  std::vector<int> h_done_now(h_done); std::vector<double> h_tdone(n, -1.0);
-  size_t nev = 0; int rounds = 0, empty_rounds = 0; long long launched_nodes = 0;
-  double sp_inc = 1e300, sp_lb = -1e300; int sp_owner = 0; bool sp_timeup = false, sp_finished = false;   // state of a tree split
-  // ---- streaming admission (host side): which instance holds which slot, when it entered, who is next
-  std::vector<int> h_slot_inst(NS, -1), h_kill(n, 0), h_pairs; std::vector<double> t_admit(n, 0.0);
-  std::vector<char> h_stalled(n, 0);   // retired because it made no progress (not because its time was up)
-  int next_q = 0, in_flight = 0;
-  bool abandoned = false, stuck_once = false;   // the round loop was left with instances still queued or in flight (reported, never silent)
+// ---------------------------------------------------------------- the round loop
+// Tree split of ONE instance: what the ranks agreed on at the last exchange
+struct SplitState { double inc = 1e300, lb = -1e300; int owner = 0; bool timeup = false, finished = false; };
+
+struct Rounds {
+  DevCtx& X; const CallShape& sh; const HostTables& H; const SplitCtx* split; int verbose;
+  DevBuf& B; hipStream_t st; const int n, NS;
+  // streaming admission (host side): which instance holds which slot, when it entered, who is next
+  std::vector<int> slot_inst, kill, pairs; std::vector<double> t_admit;
+  std::vector<char> stalled;   // retired because it made no progress (not because its time was up)
+  int next_q = 0, in_flight = 0, empty_rounds = 0;
+  bool abandoned = false, stuck_once = false;   // abandoned: the loop was left with instances still queued or in flight (reported, never silent)
+  std::vector<int> done_now; std::vector<double> t_done;   // inst_done as of this round; seconds from admission to proof (-1: not proven)
+  SplitState sp;
+  // the launches
+  size_t nev = 0; int rounds = 0, prev_bc = 0; long long launched_nodes = 0;
+  bool use_par = false, use_cls = false; size_t l_eval = 0;
+  std::vector<int> round_bc;   // MIQP_ROUND_LOG
+  // adaptive width of a single solve
+  int width_now = 0, width_since = 0, demand_now = 0; unsigned long long width_key = ~0ull, kinc_now = ~0ull; double lb_now = -1e300;
+  double t0 = 0, tlim = 0;
+
+  Rounds(DevCtx& X_, const CallShape& sh_, const HostTables& H_, const SplitCtx* split_, int verbose_, size_t l_eval_)
+      : X(X_), sh(sh_), H(H_), split(split_), verbose(verbose_), B(X_.B), st(X_.stream), n(sh_.n), NS(sh_.NS),
+        slot_inst(sh_.NS, -1), kill(sh_.n, 0), t_admit(sh_.n, 0.0), stalled(sh_.n, 0), done_now(H_.h_done), t_done(sh_.n, -1.0), l_eval(l_eval_) {}
+
   // frees the slots of proven / retired instances and fills them from the queue; `sel`: the list buffer the next select reads
-  auto admit = [&](double now, int sel) -> bool {
-    h_pairs.clear();
+  bool admit(double now, int sel) {
+    pairs.clear();
     for (int sl = 0; sl < NS; ++sl) {
-      const int k = h_slot_inst[sl];
-      if (k >= 0 && !h_done_now[k]) continue;   // busy
-      if (k >= 0) { in_flight--; h_slot_inst[sl] = -1; }
-      while (next_q < n && h_done[next_q]) next_q++;   // instances that never start (infeasible first step, no root on this rank)
-      if (next_q < n) { h_pairs.push_back(sl); h_pairs.push_back(next_q); h_slot_inst[sl] = next_q; t_admit[next_q] = now; next_q++; in_flight++; }
-      else if (k >= 0) { h_pairs.push_back(sl); h_pairs.push_back(-1); }
+      const int k = slot_inst[sl];
+      if (k >= 0 && !done_now[k]) continue;   // busy
+      if (k >= 0) { in_flight--; slot_inst[sl] = -1; }
+      while (next_q < n && H.h_done[next_q]) next_q++;   // instances that never start (infeasible first step, no root on this rank)
+      if (next_q < n) { pairs.push_back(sl); pairs.push_back(next_q); slot_inst[sl] = next_q; t_admit[next_q] = now; next_q++; in_flight++; }
+      else if (k >= 0) { pairs.push_back(sl); pairs.push_back(-1); }
     }
-    if (!h_pairs.empty()) {
-      const int np_ = (int)h_pairs.size() / 2;
-      HIP_OK(hipMemcpyAsync(X.d_pairs, h_pairs.data(), h_pairs.size() * 4, hipMemcpyHostToDevice, st));
+    if (!pairs.empty()) {
+      const int np_ = (int)pairs.size() / 2;
+      HIP_OK(hipMemcpyAsync(X.d_pairs, pairs.data(), pairs.size() * 4, hipMemcpyHostToDevice, st));
       hipLaunchKernelGGL(admit_kernel, dim3((np_ + 63) / 64), dim3(64), 0, st, B, (const int*)X.d_pairs, np_, sel);
       // (no synchronisation: the copy from pageable memory is staged before the call returns, the device buffer is protected by the stream order)
     }
     return true;
-  };
-  if (!admit(0.0, 0)) return fail_all(nullptr);
-  // (Enqueueing the launches of a round before the host has read the selection's counters - "pipelined rounds" - was measured twice and
-  // removed in round 5: no gain on queues (round 3: the time between the interior point launches is the selection and evaluation kernels, not
-  // the host) and none on single solves (round 5: p99 58.3 -> 59.6 ms, profiles/r05_single_latency.txt))
-  int prev_bc = 0;
-  static const bool round_log = KNOB_P("MIQP_ROUND_LOG") != nullptr;   // diagnostic: the batch sizes of the rounds, printed after the solve (no extra synchronisation)
-  std::vector<int> round_bc;
-  // the counters of a round's launches (batch count, work counters, hand-over counts) come in two parity sets: a round uses one, its
-  // roll_kernel zeroes the other for the round after - six 4-byte memsets per round less in the stream (0.65 ms of the 1.4 ms round of a single solve)
-  const bool use_par = X.ctr && X.oc_grid > 0 && X.ocb_grid > 0 && X.concurrent_big && X.stream2 && X.probe_grid > 0 && !KNOB_T("MIQP_MEMSETS");
-  if (use_par) HIP_OK(hipMemsetAsync(X.ctr, 0, 2 * CTR_SET * 4, st));
-  const bool use_cls = use_par && X.as_on && X.cls_list && !(KNOB_T("MIQP_CLS_LISTS") && std::atoi(KNOB_T("MIQP_CLS_LISTS")) == 0);
-  B.cls_list = use_cls ? X.cls_list : nullptr; B.cls_take = 0; X.cls_n[0] = X.cls_n[1] = X.cls_n[2] = -1;
-  int width_now = adaptive_width ? width0 : 0, width_since = 0, demand_now = 0; unsigned long long width_key = ~0ull, kinc_now = ~0ull; double lb_now = -1e300;
-  for (;;) {
-    const int par = rounds & 1;
-    B.width_cap = width_now;
-    if (use_par) { B.batch_count = X.ctr + CTR_SET * par; B.cls_count = B.batch_count + 8; } else HIP_OK(hipMemsetAsync(B.batch_count, 0, 4, st));
-    B.open_sel = rounds & 1;
-    B.prev_bc = prev_bc;
-    hipLaunchKernelGGL(select_kernel, dim3(NS), dim3(SEL_THREADS), 0, st, B, rounds);
+  }
+
+  // time limit per instance, counted from its admission: the instance is retired by the next select_kernel (its records
+  // return to the pool) and reports TIME_LIM_* in report()
+  bool kill_timed_out(double tnow) {
+    bool any_kill = false;
+    for (int sl = 0; sl < NS; ++sl) { const int k = slot_inst[sl]; if (k >= 0 && !done_now[k] && !kill[k] && tnow - t_admit[k] > H.h_tlim[k]) { kill[k] = 1; any_kill = true; } }
+    if (any_kill) HIP_OK(hipMemcpyAsync(B.inst_kill, kill.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+    return true;
+  }
+
+  // An empty round (one may come up while a list tier is being reorganised, or right after admissions).  64 of them in a row: the instances
+  // in flight are stuck (none of them is done, none has an open node to offer).  They are retired like instances at their time limit - the
+  // slots go to the rest of the queue, which is NOT abandoned; a second such streak with nothing admitted in between ends the call with an
+  // error (`abandoned`)
+  bool empty_round() {
+    if (++empty_rounds <= 64) return true;
+    if (stuck_once) { for (int sl = 0; sl < NS; ++sl) { const int k = slot_inst[sl]; if (k >= 0 && !done_now[k]) stalled[k] = 1; } abandoned = true; return true; }   // (the instances in flight did not run out of time either)
+    stuck_once = true; empty_rounds = 0;
+    for (int sl = 0; sl < NS; ++sl) { const int k = slot_inst[sl]; if (k >= 0 && !done_now[k]) { kill[k] = 1; stalled[k] = 1; } }
+    HIP_OK(hipMemcpyAsync(B.inst_kill, kill.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+    std::fprintf(stderr, "[miqp_gpu] %d instances in flight made no progress for 64 rounds: retired, the queue goes on\n", in_flight);
+    return true;
+  }
+
+  // Tree split, once per round: the ranks agree on incumbent, bound and whether to go on (identical decisions everywhere).
+  // `stop`: the job is over (sp.finished says whether with a proof); `local_done`: this rank has nothing left and only keeps taking part
+  bool exchange(int bc, bool& stop, bool& local_done) {
+    unsigned long long kinc = ~0ull; double lbl = 1e300;
+    HIP_OK(hipMemcpy(&kinc, B.inc_key, 8, hipMemcpyDeviceToHost)); HIP_OK(hipMemcpy(&lbl, B.lower_bound, 8, hipMemcpyDeviceToHost));
+    local_done = bc <= 0;
+    unsigned long long w[4];
+    w[0] = kinc >= 0xFFF0000000000000ull ? ~0ull : ((kinc & ~0xFFFFFull) | (unsigned long long)split->rank);
+    w[1] = host_d2key(local_done && kinc >= 0xFFF0000000000000ull ? 1e300 : (local_done ? std::min(lbl, 1e300) : lbl));
+    w[2] = local_done ? ~0ull : 0ull;
+    w[3] = (wall_s() - t0 > tlim) ? 0ull : ~0ull;
+    if (split->fn(split->user, 0, w, 4, 0) != 0) { std::fprintf(stderr, "[miqp_gpu] incumbent exchange failed\n"); return false; }
+    sp.inc = w[0] >= 0xFFF0000000000000ull ? 1e300 : host_key2d(w[0] & ~0xFFFFFull); sp.owner = (int)(w[0] & 0xFFFFFull);
+    sp.lb = host_key2d(w[1]); sp.timeup = w[3] == 0ull;
+    HIP_OK(hipMemcpyAsync(B.inc_ext, &sp.inc, 8, hipMemcpyHostToDevice, st));
+    const bool all_done = w[2] == ~0ull;
+    const bool gap_ok = sp.inc < 1e299 && (sp.inc - sp.lb) <= H.h_gap[0] * (1e-10 + std::fabs(sp.inc));
+    stop = all_done || sp.timeup || gap_ok;
+    if (stop) sp.finished = all_done || gap_ok;
+    return true;
+  }
+
+  // A single solve widens its rounds once it is bound-limited (plan_call): the incumbent has not moved for 32 rounds, the near list offers
+  // eight rounds' worth of eligible nodes ...
+  void adapt_width() {
+    if (kinc_now != width_key) { width_key = kinc_now; width_since = rounds; }
+    else if (kinc_now < 0xFFF0000000000000ull && rounds - width_since >= 32 && demand_now >= 8 * width_now && width_now < sh.width_max) {
+      // ... and the incumbent is already close to the bound (within 5 %): with a poor incumbent a wide round solves what a better one would have pruned
+      // (cfg5 seed 11 widened on a stale incumbent alone ended at a gap of 45 % instead of 2 %)
+      const double io_ = host_key2d(kinc_now & ~0xFFFFFull);
+      if (lb_now > -1e299 && io_ - lb_now <= 0.05 * std::fabs(io_)) { width_now *= 2; width_since = rounds; }
+    }
+  }
+
+  bool run() {
+    const ProcessSwitches& ps = process_switches(); const CallSwitches& sw = X.sw; const Layout& Y = X.Y;
+    t0 = wall_s();
+    for (int k = 0; k < n; ++k) tlim = std::max(tlim, H.h_tlim[k]);
+    HIP_OK(hipEventRecord(X.ev0, st));
+    if (!admit(0.0, 0)) return false;
+    // (Enqueueing the launches of a round before the host has read the selection's counters - "pipelined rounds" - was measured twice and
+    // removed in round 5: no gain on queues (round 3: the time between the interior point launches is the selection and evaluation kernels, not
+    // the host) and none on single solves (round 5: p99 58.3 -> 59.6 ms, profiles/r05_single_latency.txt))
+    // the counters of a round's launches (batch count, work counters, hand-over counts) come in two parity sets: a round uses one, its
+    // roll_kernel zeroes the other for the round after - six 4-byte memsets per round less in the stream (0.65 ms of the 1.4 ms round of a single solve)
+    use_par = X.ctr && X.oc_grid > 0 && X.ocb_grid > 0 && X.concurrent_big && X.stream2 && X.probe_grid > 0 && !sw.memsets;
+    if (use_par) HIP_OK(hipMemsetAsync(X.ctr, 0, 2 * CTR_SET * 4, st));
+    use_cls = use_par && X.as_on && X.cls_list && sw.cls_lists;
+    B.cls_list = use_cls ? X.cls_list : nullptr; B.cls_take = 0; X.cls_n[0] = X.cls_n[1] = X.cls_n[2] = -1;
+    width_now = sh.adaptive_width ? sh.width0 : 0;
     // (share_kernel - one workgroup, 0.23 ms: the shares of the NEXT round from this selection's demands - beside lns_kernel, 0.22 ms, on the second stream:
     // neither reads what the other writes)
-    const bool share_aside = B.lns_mode > 0 && NS >= 64 && X.stream2 && X.ev_sfork && !KNOB_P("MIQP_DEBUG_SYNC");
-    if (share_aside) { (void)hipEventRecord(X.ev_sfork, st); (void)hipStreamWaitEvent(X.stream2, X.ev_sfork, 0); hipLaunchKernelGGL(share_kernel, dim3(1), dim3(1024), 0, X.stream2, B); (void)hipEventRecord(X.ev_sjoin, X.stream2); }
-    if (B.lns_mode > 0) hipLaunchKernelGGL(lns_kernel, dim3(NS), dim3(64), 0, st, B);   // the neighbours of new incumbents join this round's batch
-    if (KNOB_P("MIQP_DEBUG_SYNC")) { hipError_t e_ = hipStreamSynchronize(st); std::fprintf(stderr, "[dbg] round %d select: %s\n", rounds, hipGetErrorString(e_)); }
-    hipLaunchKernelGGL(roll_kernel, dim3(1), dim3(CTR_SET), 0, st, B, use_par ? X.ctr + CTR_SET * (par ^ 1) : (int*)nullptr);
-    if (share_aside) (void)hipStreamWaitEvent(st, X.ev_sjoin, 0); else hipLaunchKernelGGL(share_kernel, dim3(1), dim3(1024), 0, st, B);
-    int bc = 0; int hctr[CTR_SET] = {0};
-    HIP_OK(hipMemcpyAsync(use_cls ? hctr : &bc, B.batch_count, use_cls ? CTR_SET * 4 : 4, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(h_done_now.data(), B.inst_done, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    if (adaptive_width) { HIP_OK(hipMemcpyAsync(&kinc_now, B.inc_key, 8, hipMemcpyDeviceToHost, st)); HIP_OK(hipMemcpyAsync(&demand_now, B.slot_demand, 4, hipMemcpyDeviceToHost, st)); HIP_OK(hipMemcpyAsync(&lb_now, B.lower_bound, 8, hipMemcpyDeviceToHost, st)); }
-    HIP_OK(hipStreamSynchronize(st));
-    if (use_cls) { bc = hctr[0]; for (int q = 0; q < 3; ++q) X.cls_n[q] = std::min(hctr[8 + q], X.batch_cap); }
-    if (adaptive_width) {
-      if (kinc_now != width_key) { width_key = kinc_now; width_since = rounds; }
-      else if (kinc_now < 0xFFF0000000000000ull && rounds - width_since >= 32 && demand_now >= 8 * width_now && width_now < width_max) {
-        // ... and the incumbent is already close to the bound (within 5 %): with a poor incumbent a wide round solves what a better one would have pruned
-        // (cfg5 seed 11 widened on a stale incumbent alone ended at a gap of 45 % instead of 2 %)
-        const double io_ = host_key2d(kinc_now & ~0xFFFFFull);
-        if (lb_now > -1e299 && io_ - lb_now <= 0.05 * std::fabs(io_)) { width_now *= 2; width_since = rounds; }
-      }
-    }
-    const double tnow = wall_s() - t0;
-    for (int sl = 0; sl < NS; ++sl) { const int k = h_slot_inst[sl]; if (k >= 0 && h_done_now[k] && h_tdone[k] < 0) h_tdone[k] = tnow - t_admit[k]; }   // time from admission to proof
-    if (split) {   // once per round: the ranks agree on incumbent, bound and whether to go on (identical decisions everywhere)
-      unsigned long long kinc = ~0ull; double lbl = 1e300;
-      HIP_OK(hipMemcpy(&kinc, B.inc_key, 8, hipMemcpyDeviceToHost)); HIP_OK(hipMemcpy(&lbl, B.lower_bound, 8, hipMemcpyDeviceToHost));
-      const bool local_done = bc <= 0;
-      unsigned long long w[4];
-      w[0] = kinc >= 0xFFF0000000000000ull ? ~0ull : ((kinc & ~0xFFFFFull) | (unsigned long long)split->rank);
-      w[1] = host_d2key(local_done && kinc >= 0xFFF0000000000000ull ? 1e300 : (local_done ? std::min(lbl, 1e300) : lbl));
-      w[2] = local_done ? ~0ull : 0ull;
-      w[3] = (wall_s() - t0 > tlim) ? 0ull : ~0ull;
-      if (split->fn(split->user, 0, w, 4, 0) != 0) return fail_all("incumbent exchange failed");
-      sp_inc = w[0] >= 0xFFF0000000000000ull ? 1e300 : host_key2d(w[0] & ~0xFFFFFull); sp_owner = (int)(w[0] & 0xFFFFFull);
-      sp_lb = host_key2d(w[1]); sp_timeup = w[3] == 0ull;
-      HIP_OK(hipMemcpyAsync(B.inc_ext, &sp_inc, 8, hipMemcpyHostToDevice, st));
-      const bool all_done = w[2] == ~0ull;
-      const bool gap_ok = sp_inc < 1e299 && (sp_inc - sp_lb) <= h_gap[0] * (1e-10 + std::fabs(sp_inc));
-      if (all_done || sp_timeup || gap_ok) { sp_finished = all_done || gap_ok; break; }
-      if (local_done) { rounds++; continue; }   // nothing left here: keep taking part in the exchange
-    } else {
-      // time limit per instance, counted from its admission: the instance is retired by the next select_kernel (its records
-      // return to the pool) and reports TIME_LIM_* below
-      bool any_kill = false;
-      for (int sl = 0; sl < NS; ++sl) { const int k = h_slot_inst[sl]; if (k >= 0 && !h_done_now[k] && !h_kill[k] && tnow - t_admit[k] > h_tlim[k]) { h_kill[k] = 1; any_kill = true; } }
-      if (any_kill) HIP_OK(hipMemcpyAsync(B.inst_kill, h_kill.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
-      if (!admit(tnow, 1 - (rounds & 1))) return fail_all(nullptr);
-      if (in_flight == 0 && next_q >= n) break;   // the queue is drained
-      if (tnow > tlim * (double)((n + NS - 1) / NS + 1) + 30.0) { abandoned = true; break; }   // (safety net: no instance can outlive its limit by more than a round)
-      if (bc <= 0) {   // a round may come up empty while a list tier is being reorganised, or right after admissions
-        // 64 empty rounds in a row: the instances in flight are stuck (none of them is done, none has an open node to offer).  They are
-        // retired like instances at their time limit - the slots go to the rest of the queue, which is NOT abandoned; a second such
-        // streak with nothing admitted in between ends the call with an error
-        if (++empty_rounds > 64) {
-          if (stuck_once) { for (int sl = 0; sl < NS; ++sl) { const int k = h_slot_inst[sl]; if (k >= 0 && !h_done_now[k]) h_stalled[k] = 1; } abandoned = true; break; }   // (the instances in flight did not run out of time either)
-          stuck_once = true; empty_rounds = 0;
-          for (int sl = 0; sl < NS; ++sl) { const int k = h_slot_inst[sl]; if (k >= 0 && !h_done_now[k]) { h_kill[k] = 1; h_stalled[k] = 1; } }
-          HIP_OK(hipMemcpyAsync(B.inst_kill, h_kill.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
-          std::fprintf(stderr, "[miqp_gpu] %d instances in flight made no progress for 64 rounds: retired, the queue goes on\n", in_flight);
+    const bool share_aside = B.lns_mode > 0 && NS >= 64 && X.stream2 && X.ev_sfork && !sw.debug_sync;
+    for (;;) {
+      // ---- select, local search, roll, shares
+      const int par = rounds & 1;
+      B.width_cap = width_now;
+      if (use_par) { B.batch_count = X.ctr + CTR_SET * par; B.cls_count = B.batch_count + 8; } else HIP_OK(hipMemsetAsync(B.batch_count, 0, 4, st));
+      B.open_sel = rounds & 1;
+      B.prev_bc = prev_bc;
+      hipLaunchKernelGGL(select_kernel, dim3(NS), dim3(SEL_THREADS), 0, st, B, rounds);
+      if (share_aside) { (void)hipEventRecord(X.ev_sfork, st); (void)hipStreamWaitEvent(X.stream2, X.ev_sfork, 0); hipLaunchKernelGGL(share_kernel, dim3(1), dim3(1024), 0, X.stream2, B); (void)hipEventRecord(X.ev_sjoin, X.stream2); }
+      if (B.lns_mode > 0) hipLaunchKernelGGL(lns_kernel, dim3(NS), dim3(64), 0, st, B);   // the neighbours of new incumbents join this round's batch
+      if (sw.debug_sync) debug_sync(st, rounds, "select");
+      hipLaunchKernelGGL(roll_kernel, dim3(1), dim3(CTR_SET), 0, st, B, use_par ? X.ctr + CTR_SET * (par ^ 1) : (int*)nullptr);
+      if (share_aside) (void)hipStreamWaitEvent(st, X.ev_sjoin, 0); else hipLaunchKernelGGL(share_kernel, dim3(1), dim3(1024), 0, st, B);
+      // ---- the round's counters
+      int bc = 0; int hctr[CTR_SET] = {0};
+      HIP_OK(hipMemcpyAsync(use_cls ? hctr : &bc, B.batch_count, use_cls ? CTR_SET * 4 : 4, hipMemcpyDeviceToHost, st));
+      HIP_OK(hipMemcpyAsync(done_now.data(), B.inst_done, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+      if (sh.adaptive_width) { HIP_OK(hipMemcpyAsync(&kinc_now, B.inc_key, 8, hipMemcpyDeviceToHost, st)); HIP_OK(hipMemcpyAsync(&demand_now, B.slot_demand, 4, hipMemcpyDeviceToHost, st)); HIP_OK(hipMemcpyAsync(&lb_now, B.lower_bound, 8, hipMemcpyDeviceToHost, st)); }
+      HIP_OK(hipStreamSynchronize(st));
+      if (use_cls) { bc = hctr[0]; for (int q = 0; q < 3; ++q) X.cls_n[q] = std::min(hctr[8 + q], X.batch_cap); }
+      if (sh.adaptive_width) adapt_width();
+      const double tnow = wall_s() - t0;
+      for (int sl = 0; sl < NS; ++sl) { const int k = slot_inst[sl]; if (k >= 0 && done_now[k] && t_done[k] < 0) t_done[k] = tnow - t_admit[k]; }   // time from admission to proof
+      // ---- who goes on: the ranks of a tree split agree; a batch or queue retires, admits, and stops when it is drained
+      if (split) {
+        bool stop = false, local_done = false;
+        if (!exchange(bc, stop, local_done)) return false;
+        if (stop) break;
+        if (local_done) { rounds++; continue; }   // nothing left here: keep taking part in the exchange
+      } else {
+        if (!kill_timed_out(tnow)) return false;
+        if (!admit(tnow, 1 - (rounds & 1))) return false;
+        if (in_flight == 0 && next_q >= n) break;   // the queue is drained
+        if (tnow > tlim * (double)((n + NS - 1) / NS + 1) + 30.0) { abandoned = true; break; }   // (safety net: no instance can outlive its limit by more than a round)
+        if (bc <= 0) {
+          if (!empty_round()) return false;
+          if (abandoned) break;
+          rounds++; prev_bc = 0; continue;
         }
-        rounds++; prev_bc = 0; continue;
+        stuck_once = false;
+        empty_rounds = 0;
       }
-      stuck_once = false;
-      empty_rounds = 0;
+      if (bc > X.batch_cap) bc = X.batch_cap;
+      if (sw.trace && bc > 0 && bc <= 256 && !trace_selection(X, rounds, bc)) return false;
+      // ---- the launch group of the round, between two events (and a third where the standard launch ends)
+      if (X.ipm_ev.size() < nev + 2) { hipEvent_t a, b; HIP_OK(hipEventCreate(&a)); HIP_OK(hipEventCreate(&b)); X.ipm_ev.push_back(a); X.ipm_ev.push_back(b); }
+      if (ps.launch_trace && !X.ev_mid) HIP_OK(hipEventCreate(&X.ev_mid));
+      if (X.std_ev.size() < nev / 2 + 1) { hipEvent_t a_; HIP_OK(hipEventCreate(&a_)); X.std_ev.push_back(a_); }
+      HIP_OK(hipEventRecord(X.ipm_ev[nev], st));
+      launch_ipm_batch(X, B, bc, st, true, use_par ? par : -1, X.std_ev[nev / 2]);
+      HIP_OK(hipEventRecord(X.ipm_ev[nev + 1], st));
+      if (ps.launch_trace && !trace_launches(X, rounds, bc, nev)) return false;
+      nev += 2;
+      if (bc >= X.batch_cap / 2 && rounds >= ps.replay_round && !replay_batch(X, bc)) return false;
+      if (sw.debug_sync) debug_sync(st, rounds, "ipm", bc);
+      if (sw.trace && !trace_batch(X, rounds, bc)) return false;
+      // ---- evaluation: incumbents, pruning, children into the list buffer the next select reads
+      { DevBuf Be = B; Be.open_sel = 1 - (rounds & 1); launch_eval_c(Y.C, Be, bc, l_eval, st); }
+      if (sw.debug_sync) debug_sync(st, rounds, "eval");
+      launched_nodes += bc; rounds++; prev_bc = bc;
+      if (ps.round_log) round_bc.push_back(bc);
+      if (verbose > 1) std::fprintf(stderr, "[miqp_gpu] round %d: %d nodes\n", rounds, bc);
+      if (verbose == 1 && rounds % 25 == 0 && !print_progress(X, wall_s() - t0, rounds, launched_nodes, H.h_const[0])) return false;
     }
-    if (bc > X.batch_cap) bc = X.batch_cap;
-    if (KNOB_P("MIQP_TRACE") && bc > 0 && bc <= 256) {   // diagnostic: what the selection picked (list bound, depth word), the incumbent it pruned with, its mode
-      std::vector<double> sb(bc); std::vector<int> sd(bc); double io_ = 0; int md_ = 0;
-      HIP_OK(hipMemcpy(sb.data(), B.batch_bound, (size_t)bc * 8, hipMemcpyDeviceToHost)); HIP_OK(hipMemcpy(sd.data(), B.batch_depth, (size_t)bc * 4, hipMemcpyDeviceToHost));
-      HIP_OK(hipMemcpy(&io_, B.inc_obj, 8, hipMemcpyDeviceToHost)); HIP_OK(hipMemcpy(&md_, B.inst_mode, 4, hipMemcpyDeviceToHost));
-      std::vector<int> ord(bc); for (int k = 0; k < bc; ++k) ord[k] = k;
-      std::sort(ord.begin(), ord.end(), [&](int a, int b) { return sd[a] != sd[b] ? sd[a] > sd[b] : sb[a] < sb[b]; });
-      std::fprintf(stderr, "[sel] r%d mode %d incumbent %a:", rounds, md_, io_);
-      for (int k : ord) std::fprintf(stderr, " %d.%d/%a", sd[k] >> 6, sd[k] & 63, sb[k]);
-      std::fprintf(stderr, "\n");
-    }
-    if (X.ipm_ev.size() < nev + 2) { hipEvent_t a, b; HIP_OK(hipEventCreate(&a)); HIP_OK(hipEventCreate(&b)); X.ipm_ev.push_back(a); X.ipm_ev.push_back(b); }
-    static const bool launch_trace = KNOB_T("MIQP_LAUNCH_TRACE") != nullptr;
-    if (launch_trace && !X.ev_mid) HIP_OK(hipEventCreate(&X.ev_mid));
-    if (X.std_ev.size() < nev / 2 + 1) { hipEvent_t a_; HIP_OK(hipEventCreate(&a_)); X.std_ev.push_back(a_); }
-    HIP_OK(hipEventRecord(X.ipm_ev[nev], st));
-    launch_ipm_batch(X, B, bc, st, true, use_par ? par : -1, X.std_ev[nev / 2]);
-    HIP_OK(hipEventRecord(X.ipm_ev[nev + 1], st));
-    if (launch_trace) {   // diagnostic: the two interior point launches of the round apart, and what the memory-backed one had to solve
-      HIP_OK(hipStreamSynchronize(st));
-      float m1 = 0, m2 = 0; HIP_OK(hipEventElapsedTime(&m1, X.ipm_ev[nev], X.ev_mid)); HIP_OK(hipEventElapsedTime(&m2, X.ev_mid, X.ipm_ev[nev + 1]));
-      int oc = 0; HIP_OK(hipMemcpy(&oc, B.ovf_count, 4, hipMemcpyDeviceToHost));
-      std::vector<int> ol(std::max(oc, 1)), hit(bc), hdw(bc), hok(bc);
-      if (oc > 0) HIP_OK(hipMemcpy(ol.data(), B.ovf_list, (size_t)oc * 4, hipMemcpyDeviceToHost));
-      HIP_OK(hipMemcpy(hit.data(), B.batch_it, (size_t)bc * 4, hipMemcpyDeviceToHost)); HIP_OK(hipMemcpy(hdw.data(), B.batch_depth, (size_t)bc * 4, hipMemcpyDeviceToHost));
-      HIP_OK(hipMemcpy(hok.data(), B.batch_ok, (size_t)bc * 4, hipMemcpyDeviceToHost));
-      int np = 0, mxp = 0, mxo = 0, mxc = 0; long long sp = 0, so = 0, sc = 0;
-      for (int q = 0; q < oc; ++q) { const int k = ol[q]; if ((hdw[k] & 63) == 63 && (hdw[k] >> 6) >= 1) { np++; sp += hit[k]; mxp = std::max(mxp, hit[k]); } else { so += hit[k]; mxo = std::max(mxo, hit[k]); } }
-      std::vector<char> isov(bc, 0); for (int q = 0; q < oc; ++q) isov[ol[q]] = 1;
-      for (int k = 0; k < bc; ++k) if (!isov[k]) { sc += hit[k]; mxc = std::max(mxc, hit[k]); }
-      // (with the concurrent launches of the large nodes - the default - the first time is the standard launch incl. its wait for room, the
-      // second the wait for the second stream after it, and the node split below is empty: nothing is handed on behind the standard launch;
-      // MIQP_CONCURRENT_BIG=0 MIQP_OC_BIG=0 gives the two launches of the first half of round 3 apart)
-      std::fprintf(stderr, "[launch] round %d nodes %d: on-chip %.2f ms (%d nodes, mean it %.1f, max %d); behind it %.2f ms: %d probes (mean it %.1f, max %d), %d others (mean it %.1f, max %d)\n",
-                   rounds, bc, m1, bc - oc, (double)sc / std::max(1, bc - oc), mxc, m2, np, (double)sp / std::max(1, np), mxp, oc - np, (double)so / std::max(1, oc - np), mxo);
-    }
-    nev += 2;
-    static const int replay_round = KNOB_T("MIQP_REPLAY_ROUND") ? std::atoi(KNOB_T("MIQP_REPLAY_ROUND")) : 0;
-    if (bc >= X.batch_cap / 2 && rounds >= replay_round) {   // MIQP_REPLAY=k (diagnostic): the first batch that is at least half full is solved k more times under a timer - the kernels
-      static int replay = KNOB_T("MIQP_REPLAY") ? std::atoi(KNOB_T("MIQP_REPLAY")) : 0;   // only read and write batch slots
-      if (replay > 0) {
-        hipEvent_t e0, e1; HIP_OK(hipEventCreate(&e0)); HIP_OK(hipEventCreate(&e1));
-        HIP_OK(hipEventRecord(e0, st));
-        for (int r = 0; r < replay; ++r) launch_ipm_batch(X, B, bc, st);
-        HIP_OK(hipEventRecord(e1, st)); HIP_OK(hipStreamSynchronize(st));
-        float ms = 0; HIP_OK(hipEventElapsedTime(&ms, e0, e1));
-        std::vector<int> its(bc); HIP_OK(hipMemcpy(its.data(), B.batch_it, (size_t)bc * 4, hipMemcpyDeviceToHost));
-        long long tot = 0; for (int v : its) tot += v;
-        std::fprintf(stderr, "[miqp_gpu replay] %d nodes, %lld node-iterations: %.3f ms per pass, %.1f ns per node-iteration\n", bc, tot, ms / replay, 1e6 * ms / replay / (double)tot);
-#ifdef MIQP_ABLATE
-        if (X.oc_grid > 0 && Y.C == 2) {   // cost map of the on-chip kernel: the same batch, 15 iterations per node, parts switched off
-          const size_t l_oc = (size_t)oc_lds_layout(Y.N, Y.fixlen).total;
-          auto run = [&](auto kern, int mask) {
-            HIP_OK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l_oc));
-            auto once = [&] { (void)hipMemsetAsync(B.work_counter, 0, 4, st); (void)hipMemsetAsync(B.ovf_count, 0, 4, st); hipLaunchKernelGGL(kern, dim3(std::min(bc, X.oc_grid)), dim3(64), l_oc, st, B); };
-            once(); HIP_OK(hipEventRecord(e0, st)); for (int r = 0; r < 3; ++r) once(); HIP_OK(hipEventRecord(e1, st)); HIP_OK(hipStreamSynchronize(st));
-            float m2 = 0; HIP_OK(hipEventElapsedTime(&m2, e0, e1));
-            std::fprintf(stderr, "[miqp_gpu ablate] mask %4d: %.3f ms per pass of %d nodes x 15 iterations = %.1f ns per node-iteration\n", mask, m2 / 3, bc, 1e6 * m2 / 3 / (bc * 15.0));
-            return true;
-          };
-          run(ipm_onchip_kernel<2, OC_NSL, 1>, 1); run(ipm_onchip_kernel<2, OC_NSL, 3>, 3); run(ipm_onchip_kernel<2, OC_NSL, 5>, 5); run(ipm_onchip_kernel<2, OC_NSL, 9>, 9);
-          run(ipm_onchip_kernel<2, OC_NSL, 17>, 17); run(ipm_onchip_kernel<2, OC_NSL, 33>, 33); run(ipm_onchip_kernel<2, OC_NSL, 65>, 65); run(ipm_onchip_kernel<2, OC_NSL, 129>, 129);
-          run(ipm_onchip_kernel<2, OC_NSL, 257>, 257); run(ipm_onchip_kernel<2, OC_NSL, 513>, 513); run(ipm_onchip_kernel<2, OC_NSL, 1023>, 1023);
-          run(ipm_onchip_kernel<2, OC_NSL, 1025>, 1025);   // the MFMA form of P [A B], [A B]' T on the model's column order
-          launch_ipm_batch(X, B, bc, st);   // the replays clobbered the batch results: solve the real batch again
-        }
-#endif
-        replay = 0;
-      }
-    }
-    if (KNOB_P("MIQP_DEBUG_SYNC")) { hipError_t e_ = hipStreamSynchronize(st); std::fprintf(stderr, "[dbg] round %d ipm (%d nodes): %s\n", rounds, bc, hipGetErrorString(e_)); }
-    if (KNOB_P("MIQP_TRACE")) {   // diagnostic: the solved batch of the round in an order that does not depend on the batch slots, for diffing two runs
-      HIP_OK(hipStreamSynchronize(st));
-      if (X.stream2) HIP_OK(hipStreamSynchronize(X.stream2));
-      std::vector<int> hd(bc), hi(bc), hk(bc); std::vector<double> ho(bc), hb(bc), hv(bc);
-      HIP_OK(hipMemcpy(hd.data(), B.batch_depth, bc * 4, hipMemcpyDeviceToHost)); HIP_OK(hipMemcpy(hi.data(), B.batch_it, bc * 4, hipMemcpyDeviceToHost));
-      HIP_OK(hipMemcpy(hk.data(), B.batch_ok, bc * 4, hipMemcpyDeviceToHost)); HIP_OK(hipMemcpy(ho.data(), B.batch_obj, bc * 8, hipMemcpyDeviceToHost));
-      HIP_OK(hipMemcpy(hb.data(), B.batch_bound, bc * 8, hipMemcpyDeviceToHost)); HIP_OK(hipMemcpy(hv.data(), B.batch_viol, bc * 8, hipMemcpyDeviceToHost));
-      std::vector<int> ord(bc); for (int k = 0; k < bc; ++k) ord[k] = k;
-      std::sort(ord.begin(), ord.end(), [&](int a, int b) { return hd[a] != hd[b] ? hd[a] < hd[b] : (ho[a] != ho[b] ? ho[a] < ho[b] : hi[a] < hi[b]); });
-      { int oc_ = 0, fc_ = 0, tk_ = 0, dm_ = 0; double nt_ = 0;
-        HIP_OK(hipMemcpy(&oc_, B.open_count, 4, hipMemcpyDeviceToHost)); if (B.far_cap > 0) HIP_OK(hipMemcpy(&fc_, B.far_count, 4, hipMemcpyDeviceToHost));
-        HIP_OK(hipMemcpy(&nt_, B.near_thr, 8, hipMemcpyDeviceToHost)); HIP_OK(hipMemcpy(&tk_, B.slot_take, 4, hipMemcpyDeviceToHost)); HIP_OK(hipMemcpy(&dm_, B.slot_demand, 4, hipMemcpyDeviceToHost));
-        std::fprintf(stderr, "[lists] r%d batch %d: near list after selection %d, far tier %d, near_thr %g, share of the next round %d, demand %d\n", rounds, bc, oc_, fc_, nt_, tk_, dm_); }
-      for (int k : ord) std::fprintf(stderr, "[trace] r%d depth %d.%d ok %d it %d obj %a bound %a viol %.3e\n", rounds, hd[k] >> 6, hd[k] & 63, hk[k], hi[k], ho[k], hb[k], hv[k]);
-    }
-    { DevBuf Be = B; Be.open_sel = 1 - (rounds & 1); launch_eval_c(Y.C, Be, bc, l_eval, st); }
-    if (KNOB_P("MIQP_DEBUG_SYNC")) { hipError_t e_ = hipStreamSynchronize(st); std::fprintf(stderr, "[dbg] round %d eval: %s\n", rounds, hipGetErrorString(e_)); }
-    launched_nodes += bc; rounds++; prev_bc = bc;
-    if (round_log) round_bc.push_back(bc);
-    if (O0.verbose > 1) std::fprintf(stderr, "[miqp_gpu] round %d: %d nodes\n", rounds, bc);
-    if (O0.verbose == 1 && rounds % 25 == 0) {  // progress of the first instance
-      double lb0 = 0, io0 = 0; int oc0 = 0; unsigned long long k0 = 0;
-      HIP_OK(hipMemcpyAsync(&lb0, B.lower_bound, 8, hipMemcpyDeviceToHost, st)); HIP_OK(hipMemcpyAsync(&io0, B.inc_obj, 8, hipMemcpyDeviceToHost, st));
-      HIP_OK(hipMemcpyAsync(&oc0, B.open_count, 4, hipMemcpyDeviceToHost, st)); HIP_OK(hipMemcpyAsync(&k0, B.inc_key, 8, hipMemcpyDeviceToHost, st));
-      int fc0 = 0; HIP_OK(hipMemcpyAsync(&fc0, B.far_count, 4, hipMemcpyDeviceToHost, st));
-      HIP_OK(hipStreamSynchronize(st));
-      std::fprintf(stderr, "[miqp_gpu] t %.2f s round %d nodes %lld: instance 0 bound %.4f incumbent %.4f open %d + %d\n", wall_s() - t0, rounds, launched_nodes, lb0, k0 >= 0xFFF0000000000000ull ? INFINITY : io0 + h_const[0], oc0, fc0);
-    }
+    return true;
   }
-  if (const char* dp = KNOB_T("MIQP_DUMP_OPEN")) {   // diagnostic: open list of instance 0 (bound, depth, fix record of the 400 lowest)
-    int oc0 = 0; HIP_OK(hipMemcpy(&oc0, B.open_count, 4, hipMemcpyDeviceToHost)); oc0 = std::min(oc0, open_cap);
-    const size_t src = ((size_t)(rounds & 1) * NS + 0) * open_cap;
-    std::vector<double> hb(oc0); std::vector<int> hn(oc0), hd(oc0);
-    if (oc0 > 0) { HIP_OK(hipMemcpy(hb.data(), B.open_bound + src, (size_t)oc0 * 8, hipMemcpyDeviceToHost)); HIP_OK(hipMemcpy(hn.data(), B.open_node + src, (size_t)oc0 * 4, hipMemcpyDeviceToHost));
-      HIP_OK(hipMemcpy(hd.data(), B.open_depth + src, (size_t)oc0 * 4, hipMemcpyDeviceToHost)); }
-    std::vector<int> ord(oc0); for (int k = 0; k < oc0; ++k) ord[k] = k;
-    std::sort(ord.begin(), ord.end(), [&](int x, int y) { return hb[x] < hb[y]; });
-    if (FILE* f = std::fopen(dp, "w")) {
-      std::fprintf(f, "%d %d %d %d %d %d %d\n", oc0, Y.fixlen, Y.f_reg, Y.f_env, Y.f_obs, Y.f_c2c, Y.N);
-      std::vector<signed char> rec(Y.fixlen);
-      for (int q = 0; q < std::min(oc0, 400); ++q) {
-        int k = ord[q]; HIP_OK(hipMemcpy(rec.data(), B.pool_fix + (size_t)hn[k] * Y.fixlen, Y.fixlen, hipMemcpyDeviceToHost));
-        std::fprintf(f, "%.9g %d", hb[k] + h_const[0], hd[k] >> 6); for (int x = 0; x < Y.fixlen; ++x) std::fprintf(f, " %d", (int)rec[x]); std::fprintf(f, "\n");
-      }
-      std::fclose(f);
-    }
-  }
-  // ---- polish: the incumbent of every instance is re-solved (all disjunctions fixed as completed) to a tight
-  //      tolerance; its objective and states are what the caller receives
-  std::vector<double> h_pobj(n, 0.0), h_pviol(n, 1.0); std::vector<int> h_pok(n, 0), h_pit(n, 0);
-  {
-    HIP_OK(hipMemcpyAsync(B.pool_fix, B.inc_fix, (size_t)n * Y.fixlen, hipMemcpyDeviceToDevice, st));
-    std::vector<int> ids(n); for (int k = 0; k < n; ++k) ids[k] = k;
-    HIP_OK(hipMemcpyAsync(B.batch_node, ids.data(), n * 4, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(B.batch_inst, ids.data(), n * 4, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(B.batch_count, &n, 4, hipMemcpyHostToDevice, st));
-    HIP_OK(hipStreamSynchronize(st));
-    DevBuf Bp = B; Bp.qp_tol = QP_TOL_FINAL; Bp.use_cutoff = 0; Bp.batch_cap = X.batch_alloc;
-    // the polish starts at the incumbent's own solution (integer feasible: every row of the completed record holds there), centred
-    // at a small complementarity - a third of the iterations of a cold solve to 1e-13 (the last thing a single solve waits for)
-    Bp.ws_on = (B.ws_on && !KNOB_T("MIQP_POLISH_COLD")) ? 2 : 0; Bp.ws_mu = KNOB_T("MIQP_POLISH_MU") ? std::atof(KNOB_T("MIQP_POLISH_MU")) : 1.0e-2; Bp.ws_delta = KNOB_T("MIQP_POLISH_DELTA") ? std::atof(KNOB_T("MIQP_POLISH_DELTA")) : 1.0e-4;
-    int nb = std::min(n, X.batch_alloc);
-    launch_ipm_batch(X, Bp, nb, st);
-    HIP_OK(hipMemcpyAsync(h_pobj.data(), B.batch_obj, nb * 8, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(h_pviol.data(), B.batch_viol, nb * 8, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(h_pok.data(), B.batch_ok, nb * 4, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(h_pit.data(), B.batch_it, nb * 4, hipMemcpyDeviceToHost, st));
-  }
+};
+
+// ---------------------------------------------------------------- behind the rounds: polish, read-back, the verdicts
+// polish: the incumbent of every instance is re-solved (all disjunctions fixed as completed) to a tight tolerance; its objective and
+// states are what the caller receives.  Ends the device work of the call: `ms_all` is the time between its first round and here
+struct Polished { std::vector<double> obj, viol; std::vector<int> ok, it; };
+bool polish(DevCtx& X, int n, Polished& P, float& ms_all) {
+  const DevBuf& B = X.B; const Layout& Y = X.Y; hipStream_t st = X.stream;
+  P.obj.assign(n, 0.0); P.viol.assign(n, 1.0); P.ok.assign(n, 0); P.it.assign(n, 0);
+  HIP_OK(hipMemcpyAsync(B.pool_fix, B.inc_fix, (size_t)n * Y.fixlen, hipMemcpyDeviceToDevice, st));
+  std::vector<int> ids(n); for (int k = 0; k < n; ++k) ids[k] = k;
+  HIP_OK(hipMemcpyAsync(B.batch_node, ids.data(), n * 4, hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(B.batch_inst, ids.data(), n * 4, hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(B.batch_count, &n, 4, hipMemcpyHostToDevice, st));
+  HIP_OK(hipStreamSynchronize(st));
+  DevBuf Bp = B; Bp.qp_tol = QP_TOL_FINAL; Bp.use_cutoff = 0; Bp.batch_cap = X.batch_alloc;
+  // the polish starts at the incumbent's own solution (integer feasible: every row of the completed record holds there), centred
+  // at a small complementarity - a third of the iterations of a cold solve to 1e-13 (the last thing a single solve waits for)
+  Bp.ws_on = (B.ws_on && !X.sw.polish_cold) ? 2 : 0; Bp.ws_mu = X.sw.polish_mu; Bp.ws_delta = X.sw.polish_delta;
+  int nb = std::min(n, X.batch_alloc);
+  launch_ipm_batch(X, Bp, nb, st);
+  HIP_OK(hipMemcpyAsync(P.obj.data(), B.batch_obj, nb * 8, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(P.viol.data(), B.batch_viol, nb * 8, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(P.ok.data(), B.batch_ok, nb * 4, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(P.it.data(), B.batch_it, nb * 4, hipMemcpyDeviceToHost, st));
   HIP_OK(hipEventRecord(X.ev1, st));
   HIP_OK(hipStreamSynchronize(st));
   HIP_OK(hipGetLastError());
-  float ms_all = 0; HIP_OK(hipEventElapsedTime(&ms_all, X.ev0, X.ev1));
-#ifdef MIQP_PROFILE
-  { unsigned long long pf[64]; HIP_OK(hipMemcpy(pf, B.prof + 64, 64 * 8, hipMemcpyDeviceToHost));
-    const char* nm[10] = {"decode", "rowpass", "bw.phi", "bw.TS+p", "bw.readlane+LDL", "bw.Ksolve", "bw.update", "forward", "step", "update"};
-    double tot = 0; for (int q = 0; q < 10; ++q) tot += (double)pf[q];
-    { unsigned long long po[16]; HIP_OK(hipMemcpy(po, B.prof, 16 * 8, hipMemcpyDeviceToHost));
-      const char* no[9] = {"build", "bw.rows/assemble", "bw.mfma", "bw.TS", "bw.cholK", "bw.P", "forward", "step", "update"};
-      double to = 0; for (int q = 0; q < 9; ++q) to += (double)po[q];
-      if (po[10]) { std::fprintf(stderr, "[miqp_gpu profile] memory-backed kernel nodes %llu iters %llu cycles/node-iter %.0f :", po[10], po[9], to / std::max(1ull, po[9]));
-        for (int q = 0; q < 9; ++q) std::fprintf(stderr, " %s %.1f%% (%.0f)", no[q], 100.0 * po[q] / to, (double)po[q] / std::max(1ull, po[9]));
-        std::fprintf(stderr, "; inside bw.TS, the stage-Hessian chain: weights + staging %.0f, single-entry rows %.0f, MFMA loop %.0f, reductions + diagonal %.0f", (double)po[12] / std::max(1ull, po[9]), (double)po[13] / std::max(1ull, po[9]), (double)po[14] / std::max(1ull, po[9]), (double)po[15] / std::max(1ull, po[9]));
-        std::fprintf(stderr, "\n"); } }
-    std::fprintf(stderr, "[miqp_gpu profile] on-chip nodes %llu iters %llu cycles/node-iter %.0f :", pf[11], pf[10], tot / std::max(1ull, pf[10]));
-    for (int q = 0; q < 10; ++q) std::fprintf(stderr, " %s %.1f%% (%.0f)", nm[q], 100.0 * pf[q] / tot, (double)pf[q] / std::max(1ull, pf[10]));
-    std::fprintf(stderr, "\n");
-    { unsigned long long pa[14]; HIP_OK(hipMemcpy(pa, B.prof + 80, 14 * 8, hipMemcpyDeviceToHost));
-      const char* na[9] = {"decode", "gains + first iterate", "scan", "response of the row", "q", "directions + ratio test + M update", "iterate refresh", "results", "warm start"};
-      double ta = 0; for (int q = 0; q < 9; ++q) ta += (double)pa[q];
-      if (pa[10]) { std::fprintf(stderr, "[miqp_gpu profile] active-set kernel nodes %llu steps %llu cycles/node %.0f :", pa[10], pa[11], ta / (double)pa[10]);
-        for (int q = 0; q < 9; ++q) std::fprintf(stderr, " %s %.1f%% (%.0f)", na[q], 100.0 * pa[q] / ta, (double)pa[q] / (double)pa[10]);
-        std::fprintf(stderr, "; inside the decode: bound classes %.0f, general-row pass %.0f", (double)pa[12] / (double)pa[10], (double)pa[13] / (double)pa[10]);
-        std::fprintf(stderr, "\n");
-        unsigned long long pw[3], pl[6]; HIP_OK(hipMemcpy(pw, B.prof + 94, 3 * 8, hipMemcpyDeviceToHost)); HIP_OK(hipMemcpy(pl, B.prof + 120, 6 * 8, hipMemcpyDeviceToHost));
-        if (pw[2] && pw[1] && pl[5]) std::fprintf(stderr, "[miqp_gpu profile] standard active-set launches: %llu wavefronts resident %.0f shader cycles = %.1f us each (shader clock %.0f MHz); per launch (%llu folded): span %.3f ms, from the first wavefront out of work to the last end %.3f ms, wavefronts %.0f, resident wavefront time / (span x wavefronts) %.3f\n",
-          pw[2], (double)pw[0] / pw[2], (double)pw[1] / pw[2] / 100.0, 100.0 * (double)pw[0] / (double)pw[1], pl[5], (double)pl[3] / pl[5] / 1e5, (double)pl[4] / pl[5] / 1e5, (double)pw[2] / pl[5], ((double)pw[1]) / ((double)pl[3] * ((double)pw[2] / pl[5])));
-        unsigned long long ph[16]; HIP_OK(hipMemcpy(ph, B.prof + 128, 16 * 8, hipMemcpyDeviceToHost));
-        if (pw[2]) { std::fprintf(stderr, "[miqp_gpu profile] standard active-set wavefronts by their start after the launch's first (< 0.05 / 0.2 / 0.5 / 1 / 2 / 4 / 8 ms / later), %% :");
-          for (int q = 0; q < 8; ++q) std::fprintf(stderr, " %.1f", 100.0 * ph[q] / pw[2]);
-          std::fprintf(stderr, "; by the nodes they solved (0 / <= 4 / <= 16 / <= 32 / <= 64 / more), %% :");
-          for (int q = 8; q < 14; ++q) std::fprintf(stderr, " %.1f", 100.0 * ph[q] / pw[2]);
-          std::fprintf(stderr, "\n"); }
-        if (const char* wd = KNOB_T("MIQP_WAVE_DUMP")) {
-          std::vector<unsigned long long> w(4 * 4 * 4096); HIP_OK(hipMemcpy(w.data(), B.prof + 160, w.size() * 8, hipMemcpyDeviceToHost));
-          if (FILE* f = std::fopen(wd, "w")) { for (int q = 0; q < 4 * 4096; ++q) if (w[4 * q]) std::fprintf(f, "%d %llu %llu %u %u %llu %d\n", q & 4095, w[4 * q], w[4 * q + 1], (unsigned)(w[4 * q + 2] >> 32), (unsigned)w[4 * q + 2], w[4 * q + 3], q >> 12); std::fclose(f); } } } }
-    { unsigned long long pe[8]; HIP_OK(hipMemcpy(pe, B.prof + 100, 8 * 8, hipMemcpyDeviceToHost));
-      const char* ne[6] = {"load", "regions", "leaf disjunctions", "branching", "lifting + reservation", "records"};
-      double te = 0; for (int q = 0; q < 6; ++q) te += (double)pe[q];
-      if (pe[6]) { std::fprintf(stderr, "[miqp_gpu profile] eval_kernel, %llu branched nodes, cycles/node %.0f :", pe[6], te / (double)pe[6]);
-        for (int q = 0; q < 6; ++q) std::fprintf(stderr, " %s %.1f%% (%.0f)", ne[q], 100.0 * pe[q] / te, (double)pe[q] / (double)pe[6]);
-        std::fprintf(stderr, "\n"); } }
-    { unsigned long long ps[10]; HIP_OK(hipMemcpy(ps, B.prof + 110, 10 * 8, hipMemcpyDeviceToHost));
-      const char* ns[8] = {"incumbent copy / kill", "setup", "pass 1 (prune, keys)", "far refill", "bound reduce + spill select", "focus + window + share", "radix select + ties", "pass 3 (emit, compact)"};
-      double ts = 0; for (int q = 0; q < 8; ++q) ts += (double)ps[q];
-      if (ps[8]) { std::fprintf(stderr, "[miqp_gpu profile] select_kernel, %llu workgroups that reached the end (thread 0's clock), mean list %.0f entries, cycles each %.0f :", ps[8], (double)ps[9] / (double)ps[8], ts / (double)ps[8]);
-        for (int q = 0; q < 8; ++q) std::fprintf(stderr, " %s %.1f%% (%.0f)", ns[q], 100.0 * ps[q] / ts, (double)ps[q] / (double)ps[8]);
-        std::fprintf(stderr, "\n"); } }
-    HIP_OK(hipMemset(B.prof, 0, 160 * 8)); }
-#endif
-  if (B.stats) {
-    unsigned long long hs[256]; HIP_OK(hipMemcpy(hs, B.stats, sizeof(hs), hipMemcpyDeviceToHost)); HIP_OK(hipMemset(B.stats, 0, sizeof(hs)));
-    const double nn_ = (double)std::max(1ull, hs[0]);
-    std::fprintf(stderr, "[miqp_gpu stats] on-chip nodes %llu (general rows %.1f, coefficients %.1f, box keys %.1f, iterations %.1f per node), handed over %llu; general rows / 32 histogram:", hs[0], hs[1] / nn_, hs[4] / nn_, hs[2] / nn_, hs[5] / nn_, hs[3]);
-    for (int q = 0; q < 16; ++q) std::fprintf(stderr, " %llu", hs[8 + q]);
-    std::fprintf(stderr, "\n");
-    std::fprintf(stderr, "[miqp_gpu stats] node outcomes: infeasible %llu (%.1f it), cut off %llu (%.1f it), not converged %llu (%.1f it), solved %llu (%.1f it) of which: bound >= incumbent %llu, within gap %llu, integer feasible %llu, branched %llu (%.2f children; by kind region/env/obstacle/car-car: %llu x %.1f, %llu x %.1f, %llu x %.1f, %llu x %.1f)\n",
-                 hs[32], hs[36] / (double)std::max(1ull, hs[32]), hs[33], hs[37] / (double)std::max(1ull, hs[33]), hs[34], hs[38] / (double)std::max(1ull, hs[34]), hs[35], hs[39] / (double)std::max(1ull, hs[35]),
-                 hs[40], hs[41], hs[42], hs[43], hs[44] / (double)std::max(1ull, hs[43]), hs[48], hs[52] / (double)std::max(1ull, hs[48]), hs[49], hs[53] / (double)std::max(1ull, hs[49]),
-                 hs[50], hs[54] / (double)std::max(1ull, hs[50]), hs[51], hs[55] / (double)std::max(1ull, hs[51]));
-    std::fprintf(stderr, "[miqp_gpu stats] region sets: tightened at %llu (car, step) sites, %llu nodes closed because a step had no region left; children not created because of their lifted bound %llu (multi-row lift larger than the single-row one: %llu), car/car sets tightened at %llu groups\n", hs[58], hs[59], hs[56], hs[57], hs[61]);
-    std::fprintf(stderr, "[miqp_gpu stats] region branchings flagged by: own rows %llu (worst class acc box %llu, jerk box %llu, sector %llu, half-plane %llu, curvature %llu, slow square %llu), environment front rows %llu, obstacle front rows %llu, car/car front rows %llu; by step:",
-                 hs[64], hs[70], hs[71], hs[72], hs[73], hs[74], hs[75], hs[65], hs[66], hs[67]);
-    for (int q = 0; q < 32 && q < Y.N; ++q) std::fprintf(stderr, " %llu", hs[160 + q]);
-    std::fprintf(stderr, "\n[miqp_gpu stats] node outcomes by origin (processed: infeasible / cut off / not converged / solved):");
-    const char* on_[16] = {"root|reg-ref", "reg-adjacent", "reg-other", "reg-slow", "env-ref", "env-other", "-", "-", "obs-ref", "obs-other", "-", "-", "c2c-ref", "c2c-other", "-", "probe"};
-    for (int q = 0; q < 16; ++q) if (hs[80 + q]) std::fprintf(stderr, " %s %llu: %llu / %llu / %llu / %llu;", on_[q], hs[80 + q], hs[96 + q], hs[112 + q], hs[128 + q], hs[144 + q]);
-    std::fprintf(stderr, "\n[miqp_gpu stats] infeasible rounding probes re-rounded: %llu", hs[62]);
-    std::fprintf(stderr, "\n[miqp_gpu stats] handed-over nodes with >= 480 general rows: %llu, mean %.0f, most %llu general rows", hs[7], (double)hs[6] / std::max(1ull, hs[7]), hs[5]);
-    std::fprintf(stderr, "\n[miqp_gpu stats] rounding probes by iterations / 3 (0-2, 3-5, ..., 45+):");
-    { const char* oc_n[4] = {"infeasible", "cut off", "not converged", "solved"};
-      for (int o = 0; o < 4; ++o) { std::fprintf(stderr, " %s", oc_n[o]); for (int q = 0; q < 16; ++q) std::fprintf(stderr, " %llu", hs[192 + 16 * o + q]); std::fprintf(stderr, ";"); } }
-    std::fprintf(stderr, "\n");
-  }
-  if (round_log) { std::fprintf(stderr, "[rounds]"); for (int v : round_bc) std::fprintf(stderr, " %d", v); std::fprintf(stderr, "\n"); }
-  double ms_ipm = 0;
-  for (size_t e = 0; e + 1 < nev; e += 2) { float ms = 0; HIP_OK(hipEventElapsedTime(&ms, X.ipm_ev[e], X.ipm_ev[e + 1])); ms_ipm += ms; }
-  double ms_std = 0; const bool std_timed = use_par;   // (the event is recorded in the concurrent launch path only)
-  if (std_timed) for (size_t e = 0; e + 1 < nev; e += 2) { float ms = 0; if (hipEventElapsedTime(&ms, X.ipm_ev[e], X.std_ev[e / 2]) == hipSuccess) ms_std += ms; }
-  double t_solve = wall_s() - t0;
+  HIP_OK(hipEventElapsedTime(&ms_all, X.ev0, X.ev1));
+  return true;
+}
 
-  // ---- results
-  std::vector<double> h_inc(n), h_lb(n); std::vector<int> h_flags(n), h_ninc(n), h_oc(n), h_dn(n); std::vector<long long> h_nodes(n), h_iters(n);
-  std::vector<unsigned long long> h_key(n);
-  unsigned long long rowiters = 0;
-  HIP_OK(hipMemcpy(h_inc.data(), B.inc_obj, n * 8, hipMemcpyDeviceToHost));
-  HIP_OK(hipMemcpy(h_key.data(), B.inc_key, n * 8, hipMemcpyDeviceToHost));
-  HIP_OK(hipMemcpy(h_lb.data(), B.lower_bound, n * 8, hipMemcpyDeviceToHost));
-  HIP_OK(hipMemcpy(h_flags.data(), B.inst_flags, n * 4, hipMemcpyDeviceToHost));
-  HIP_OK(hipMemcpy(h_ninc.data(), B.inst_ninc, n * 4, hipMemcpyDeviceToHost));
-  HIP_OK(hipMemcpy(h_oc.data(), B.open_count, n * 4, hipMemcpyDeviceToHost));
-  HIP_OK(hipMemcpy(h_dn.data(), B.inst_done, n * 4, hipMemcpyDeviceToHost));
-  HIP_OK(hipMemcpy(h_nodes.data(), B.inst_nodes, n * 8, hipMemcpyDeviceToHost));
-  HIP_OK(hipMemcpy(h_iters.data(), B.inst_iters, n * 8, hipMemcpyDeviceToHost));
-  HIP_OK(hipMemcpy(&rowiters, B.stat_rowiters, 8, hipMemcpyDeviceToHost));
-  unsigned long long h_as[32] = {0};
-  HIP_OK(hipMemcpy(h_as, B.as_stats, 256, hipMemcpyDeviceToHost));
-  if (B.stats && h_as[0] + h_as[2] > 0)
-    std::fprintf(stderr, "[miqp_gpu stats] active-set launch: %llu nodes (%.1f steps, %.1f drops, %.1f rows from the parent's active set, %.1f active rows at the end per node; %llu infeasible, %llu cut off; %llu started from the parent's M, %llu fell back to a cold start), %llu handed to the interior point (no free slot %llu, step cap %llu, curvature %llu, down-date pivot %llu, rows off their equalities %llu, other %llu); M rebuilt because: the parent left none %llu, the ring had come round %llu, another row count %llu; in the larger block %llu nodes (%.1f steps), of them leaves of the local search %llu (%.1f steps), rounding probes %llu; by their general rows (<= 64 / 96 / 128 / 192 / more) %llu / %llu / %llu / %llu / %llu\n",
-                 h_as[0], h_as[1] / (double)std::max(1ull, h_as[0]), h_as[3] / (double)std::max(1ull, h_as[0]), h_as[7] / (double)std::max(1ull, h_as[0]), h_as[6] / (double)std::max(1ull, h_as[0]), h_as[4], h_as[5], h_as[8], h_as[9], h_as[2], h_as[11], h_as[12], h_as[13], h_as[14], h_as[15], h_as[10], h_as[17], h_as[18], h_as[19], h_as[20], h_as[21] / (double)std::max(1ull, h_as[20]), h_as[22], h_as[23] / (double)std::max(1ull, h_as[22]), h_as[29], h_as[24], h_as[25], h_as[26], h_as[27], h_as[28]);
-  std::vector<signed char> h_fix((size_t)n * Y.fixlen); std::vector<double> h_Z((size_t)n * Y.N * Y.nz);
-  HIP_OK(hipMemcpy(h_fix.data(), B.inc_fix, h_fix.size(), hipMemcpyDeviceToHost));
-  HIP_OK(hipMemcpy(h_Z.data(), B.inc_Z, h_Z.size() * 8, hipMemcpyDeviceToHost));
+// what the device knows of every instance at the end of the call
+struct Results {
+  std::vector<double> inc, lb, Z; std::vector<int> flags, ninc, oc, dn; std::vector<long long> nodes, iters;
+  std::vector<signed char> fix; unsigned long long rowiters = 0, as[32] = {0};
+};
+bool read_back(const DevCtx& X, int n, Results& R) {
+  const DevBuf& B = X.B; const Layout& Y = X.Y;
+  R.inc.resize(n); R.lb.resize(n); R.flags.resize(n); R.ninc.resize(n); R.oc.resize(n); R.dn.resize(n); R.nodes.resize(n); R.iters.resize(n);
+  HIP_OK(hipMemcpy(R.inc.data(), B.inc_obj, n * 8, hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(R.lb.data(), B.lower_bound, n * 8, hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(R.flags.data(), B.inst_flags, n * 4, hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(R.ninc.data(), B.inst_ninc, n * 4, hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(R.oc.data(), B.open_count, n * 4, hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(R.dn.data(), B.inst_done, n * 4, hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(R.nodes.data(), B.inst_nodes, n * 8, hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(R.iters.data(), B.inst_iters, n * 8, hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(&R.rowiters, B.stat_rowiters, 8, hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(R.as, B.as_stats, 256, hipMemcpyDeviceToHost));
+  if (B.stats && R.as[0] + R.as[2] > 0) print_as_stats(R.as);
+  R.fix.resize((size_t)n * Y.fixlen); R.Z.resize((size_t)n * Y.N * Y.nz);
+  HIP_OK(hipMemcpy(R.fix.data(), B.inc_fix, R.fix.size(), hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(R.Z.data(), B.inc_Z, R.Z.size() * 8, hipMemcpyDeviceToHost));
+  return true;
+}
+// ... of which the polished solution replaces the incumbent's where the polish converged
+bool take_polished(const DevCtx& X, miqp_solver_t* const* S, int n, const HostTables& H, const Polished& P, Results& R) {
+  const DevBuf& B = X.B; const Layout& Y = X.Y;
   std::vector<double> h_pZ((size_t)n * Y.N * Y.nz);
   HIP_OK(hipMemcpy(h_pZ.data(), B.batch_Z, h_pZ.size() * 8, hipMemcpyDeviceToHost));
   for (int k = 0; k < n; ++k) {
-    if (!(h_inc[k] < 1e299)) continue;
-    if (h_pviol[k] <= FEAS_TOL && (h_pok[k] || h_pit[k] >= 10)) {
-      int nign = 0; for (int q = 0; q < Y.C * Y.O * Y.N * 5; ++q) nign += h_fix[(size_t)k * Y.fixlen + Y.f_obs + q] >= Y.L;
-      h_inc[k] = h_pobj[k] + h_const[k] + nign * S[k]->inst.w_slack_obs;
-      std::copy(h_pZ.begin() + (size_t)k * Y.N * Y.nz, h_pZ.begin() + (size_t)(k + 1) * Y.N * Y.nz, h_Z.begin() + (size_t)k * Y.N * Y.nz);
+    if (!(R.inc[k] < 1e299)) continue;
+    if (P.viol[k] <= FEAS_TOL && (P.ok[k] || P.it[k] >= 10)) {
+      int nign = 0; for (int q = 0; q < Y.C * Y.O * Y.N * 5; ++q) nign += R.fix[(size_t)k * Y.fixlen + Y.f_obs + q] >= Y.L;
+      R.inc[k] = P.obj[k] + H.h_const[k] + nign * S[k]->inst.w_slack_obs;
+      std::copy(h_pZ.begin() + (size_t)k * Y.N * Y.nz, h_pZ.begin() + (size_t)(k + 1) * Y.N * Y.nz, R.Z.begin() + (size_t)k * Y.N * Y.nz);
     }
   }
-  if (split) {
-    // the owner of the best incumbent hands its polished solution to every rank: {objective, states, completed record}
-    std::vector<unsigned char> buf(8 + h_Z.size() * 8 + h_fix.size());
-    unsigned long long w[2] = {h_inc[0] < 1e299 ? ((host_d2key(h_inc[0]) & ~0xFFFFFull) | (unsigned long long)split->rank) : ~0ull, ~0ull};
-    if (split->fn(split->user, 0, w, 2, 0) != 0) return fail_all("incumbent exchange failed");
-    if (w[0] < 0xFFF0000000000000ull) {
-      const int owner = (int)(w[0] & 0xFFFFFull);
-      if (owner == split->rank) { std::memcpy(buf.data(), &h_inc[0], 8); std::memcpy(buf.data() + 8, h_Z.data(), h_Z.size() * 8); std::memcpy(buf.data() + 8 + h_Z.size() * 8, h_fix.data(), h_fix.size()); }
-      if (split->fn(split->user, 1, buf.data(), (int)buf.size(), owner) != 0) return fail_all("solution broadcast failed");
-      std::memcpy(&h_inc[0], buf.data(), 8); std::memcpy(h_Z.data(), buf.data() + 8, h_Z.size() * 8); std::memcpy(h_fix.data(), buf.data() + 8 + h_Z.size() * 8, h_fix.size());
-      h_lb[0] = std::min(sp_lb, h_inc[0]);
-    }
-    h_flags[0] = sp_finished ? 0 : 1; h_oc[0] = 0; h_dn[0] = 1;   // the verdict of the whole job, the same on every rank
+  return true;
+}
+
+// tree split: the owner of the best incumbent hands its polished solution to every rank: {objective, states, completed record};
+// the verdict of the whole job is the same on every rank
+bool split_broadcast(const SplitCtx* split, const SplitState& sp, Results& R) {
+  std::vector<unsigned char> buf(8 + R.Z.size() * 8 + R.fix.size());
+  unsigned long long w[2] = {R.inc[0] < 1e299 ? ((host_d2key(R.inc[0]) & ~0xFFFFFull) | (unsigned long long)split->rank) : ~0ull, ~0ull};
+  if (split->fn(split->user, 0, w, 2, 0) != 0) { std::fprintf(stderr, "[miqp_gpu] incumbent exchange failed\n"); return false; }
+  if (w[0] < 0xFFF0000000000000ull) {
+    const int owner = (int)(w[0] & 0xFFFFFull);
+    if (owner == split->rank) { std::memcpy(buf.data(), &R.inc[0], 8); std::memcpy(buf.data() + 8, R.Z.data(), R.Z.size() * 8); std::memcpy(buf.data() + 8 + R.Z.size() * 8, R.fix.data(), R.fix.size()); }
+    if (split->fn(split->user, 1, buf.data(), (int)buf.size(), owner) != 0) { std::fprintf(stderr, "[miqp_gpu] solution broadcast failed\n"); return false; }
+    std::memcpy(&R.inc[0], buf.data(), 8); std::memcpy(R.Z.data(), buf.data() + 8, R.Z.size() * 8); std::memcpy(R.fix.data(), buf.data() + 8 + R.Z.size() * 8, R.fix.size());
+    R.lb[0] = std::min(sp.lb, R.inc[0]);
   }
-  long long tot_iters = 0; for (int k = 0; k < n; ++k) tot_iters += h_iters[k];
+  R.flags[0] = sp.finished ? 0 : 1; R.oc[0] = 0; R.dn[0] = 1;
+  return true;
+}
+
+// host and device times of a call, as the handles report them (miqp_solver_last_timing / _last_active_set / _last_setup)
+struct CallTimes { double t_setup = 0, t_ctx = 0, t_tables = 0, t_solve = 0, ms_ipm = 0, ms_std = 0; float ms_all = 0; bool ctx_built = false, std_timed = false; };
+
+// status, properties and solution of every handle
+void report(miqp_solver_t* const* S, int* statuses, const Layout& Y, const HostTables& H, const Rounds& L, const Results& R, const CallTimes& T, bool split) {
+  const int n = L.n;
+  long long tot_iters = 0; for (int k = 0; k < n; ++k) tot_iters += R.iters[k];
   for (int k = 0; k < n; ++k) {
     miqp_solver* s = S[k];
-    bool have = h_inc[k] < 1e299;
-    bool unfinished = (h_flags[k] & 3) || h_oc[k] > 0 || !h_dn[k];   // bit 0: a list or the record pool overflowed, bit 1: retired at its time limit
-    if (!split && k >= next_q && !h_done[k]) {   // never admitted (the round loop was abandoned): the solver did not run on it - not a time-limit verdict
+    bool have = R.inc[k] < 1e299;
+    bool unfinished = (R.flags[k] & 3) || R.oc[k] > 0 || !R.dn[k];   // bit 0: a list or the record pool overflowed, bit 1: retired at its time limit
+    if (!split && k >= L.next_q && !H.h_done[k]) {   // never admitted (the round loop was abandoned): the solver did not run on it - not a time-limit verdict
       s->status = MIQP_STATUS_FAILED_SEG_FAULT; s->has_sol = false; s->props.objective = NAN; s->props.gap = NAN; s->props.best_bound = NAN; s->props.status = 0; s->props.time = 0.0;
       s->err = "the queue was abandoned before this instance was admitted";
       statuses[k] = s->status; continue;
     }
-    s->props.time = h_tdone[k] >= 0 ? h_tdone[k] : std::max(0.0, t_solve - t_admit[k]);   // from the instance's admission to its proof (or to the end of the call)
-    s->admit_s = t_admit[k];
-    s->props.NrIterations = (int)std::min<long long>(h_iters[k], 2147483647LL); s->props.nodes = h_nodes[k];
-    s->props.NrSolutionPool = h_ninc[k];
-    s->timing[0] = ms_all * 1e-3; s->timing[1] = ms_ipm * 1e-3; s->timing[2] = (double)(nev / 2); s->timing[3] = (double)launched_nodes;
-    s->timing[4] = (double)tot_iters; s->timing[5] = (double)rowiters;
-    s->as_timing[0] = (double)h_as[0]; s->as_timing[1] = (double)h_as[1]; s->as_timing[2] = (double)h_as[2]; s->as_timing[3] = (double)h_as[3];
-    s->as_timing[4] = (double)h_as[6]; s->as_timing[5] = (double)h_as[7]; s->as_timing[6] = ms_std * 1e-3; s->as_timing[7] = std_timed ? (double)(nev / 2) : 0.0;
-    s->setup[0] = t_setup; s->setup[1] = t_ctx; s->setup[2] = ctx_built ? 1.0 : 0.0;
+    s->props.time = L.t_done[k] >= 0 ? L.t_done[k] : std::max(0.0, T.t_solve - L.t_admit[k]);   // from the instance's admission to its proof (or to the end of the call)
+    s->admit_s = L.t_admit[k];
+    s->props.NrIterations = (int)std::min<long long>(R.iters[k], 2147483647LL); s->props.nodes = R.nodes[k];
+    s->props.NrSolutionPool = R.ninc[k];
+    s->timing[0] = T.ms_all * 1e-3; s->timing[1] = T.ms_ipm * 1e-3; s->timing[2] = (double)(L.nev / 2); s->timing[3] = (double)L.launched_nodes;
+    s->timing[4] = (double)tot_iters; s->timing[5] = (double)R.rowiters;
+    s->as_timing[0] = (double)R.as[0]; s->as_timing[1] = (double)R.as[1]; s->as_timing[2] = (double)R.as[2]; s->as_timing[3] = (double)R.as[3];
+    s->as_timing[4] = (double)R.as[6]; s->as_timing[5] = (double)R.as[7]; s->as_timing[6] = T.ms_std * 1e-3; s->as_timing[7] = T.std_timed ? (double)(L.nev / 2) : 0.0;
+    s->setup[0] = T.t_setup; s->setup[1] = T.t_ctx; s->setup[2] = T.ctx_built ? 1.0 : 0.0;
     s->err.clear();
-    if (h_stalled[k] && unfinished) s->err = "retired without a proof: no progress for 64 branch-and-bound rounds (not a time-limit verdict)";
+    if (L.stalled[k] && unfinished) s->err = "retired without a proof: no progress for 64 branch-and-bound rounds (not a time-limit verdict)";
     if (have) {
       s->status = MIQP_STATUS_SUCCESS; s->has_sol = true;
-      s->props.objective = h_inc[k];
-      double lb = std::min(h_lb[k], h_inc[k]);
+      s->props.objective = R.inc[k];
+      double lb = std::min(R.lb[k], R.inc[k]);
       // nodes within the gap of the incumbent are dropped without being refined: what is proven is the smaller of the open
       // list's best bound and incumbent - gap*|incumbent| (CPLEX reports the bound of its remaining nodes the same way)
-      lb = std::min(lb, h_inc[k] - h_gap[k] * std::fabs(h_inc[k]));
-      s->props.best_bound = lb; s->props.gap = std::fabs(lb - h_inc[k]) / (1e-10 + std::fabs(h_inc[k]));
+      lb = std::min(lb, R.inc[k] - H.h_gap[k] * std::fabs(R.inc[k]));
+      s->props.best_bound = lb; s->props.gap = std::fabs(lb - R.inc[k]) / (1e-10 + std::fabs(R.inc[k]));
       s->props.status = unfinished ? MIQP_CPX_STAT_TIME_LIM_FEAS : (s->props.gap <= 1e-9 ? MIQP_CPX_STAT_OPTIMAL : MIQP_CPX_STAT_OPTIMAL_TOL);
-      s->Z.assign(h_Z.begin() + (size_t)k * Y.N * Y.nz, h_Z.begin() + (size_t)(k + 1) * Y.N * Y.nz);
-      s->comp.assign(h_fix.begin() + (size_t)k * Y.fixlen, h_fix.begin() + (size_t)(k + 1) * Y.fixlen);
+      s->Z.assign(R.Z.begin() + (size_t)k * Y.N * Y.nz, R.Z.begin() + (size_t)(k + 1) * Y.N * Y.nz);
+      s->comp.assign(R.fix.begin() + (size_t)k * Y.fixlen, R.fix.begin() + (size_t)(k + 1) * Y.fixlen);
     } else {
-      s->status = unfinished ? (h_stalled[k] ? MIQP_STATUS_FAILED_SEG_FAULT : MIQP_STATUS_FAILED_TIMEOUT) : MIQP_STATUS_FAILED_NO_SOLUT;   // (a stalled instance did not run out of time: the solver could not go on)
-      s->props.objective = NAN; s->props.gap = NAN; s->props.best_bound = h_lb[k];
+      s->status = unfinished ? (L.stalled[k] ? MIQP_STATUS_FAILED_SEG_FAULT : MIQP_STATUS_FAILED_TIMEOUT) : MIQP_STATUS_FAILED_NO_SOLUT;   // (a stalled instance did not run out of time: the solver could not go on)
+      s->props.objective = NAN; s->props.gap = NAN; s->props.best_bound = R.lb[k];
       s->props.status = unfinished ? MIQP_CPX_STAT_TIME_LIM_INFEAS : MIQP_CPX_STAT_INFEASIBLE;
     }
     statuses[k] = s->status;
   }
-  if (abandoned) std::fprintf(stderr, "[miqp_gpu] the round loop was abandoned with %d of %d instances never admitted: they report FAILED_SEG_FAULT, the call fails\n", n - next_q, n);
-  if (KNOB_P("MIQP_STATS")) std::fprintf(stderr, "[miqp_gpu stats] reachable-set diameter (L1) of instance 0: %.1f\n", hD[Y.d_misc + 2]);
-  if (KNOB_P("MIQP_STATS")) std::fprintf(stderr, "[miqp_gpu stats] host: setup %.3f s (device context %.3f, instance tables and presolve %.3f, upload %.3f), rounds %.3f s (%d), results %.3f s\n", t_setup, t_ctx, t_tables, t_setup - t_ctx - t_tables, t_solve, rounds, wall_s() - t0 - t_solve);
-  return !abandoned;
+  if (L.abandoned) std::fprintf(stderr, "[miqp_gpu] the round loop was abandoned with %d of %d instances never admitted: they report FAILED_SEG_FAULT, the call fails\n", n - L.next_q, n);
+}
+
+// ---------------------------------------------------------------- the batch solve
+bool solve_batch_impl(miqp_solver_t* const* S, int n, int* statuses, const SplitCtx* split = nullptr, int inflight = 0, int lane = 0, int lanes = 1) {
+  // every way out of this function that is not report() at its end (a failed HIP call, a failed exchange) leaves "the solver could not
+  // run" behind: a caller's zero-filled status array would otherwise read as SUCCESS for instances that were never solved.  Every phase
+  // returns false on such a failure (HIP_OK does, after naming the call) and nothing before report() touches `statuses`
+  for (int k = 0; k < n; ++k) { statuses[k] = MIQP_STATUS_FAILED_SEG_FAULT; if (S[k]) { S[k]->status = MIQP_STATUS_FAILED_SEG_FAULT; S[k]->has_sol = false; S[k]->rescache.reset(); } }
+  if (split && n != 1) return false;
+  BatchShape bs = batch_layout(S, n);
+  if (!bs.ok) { for (int k = 0; k < n; ++k) { if (S[k]) S[k]->err = bs.err; statuses[k] = MIQP_STATUS_FAILED_SEG_FAULT; } std::fprintf(stderr, "[miqp_gpu] %s\n", bs.err.c_str()); return false; }
+  const Layout& Y = bs.Y;
+  const miqp_solver_opts& O0 = S[0]->opts;
+  auto fail_all = [&](const char* why) { if (why) std::fprintf(stderr, "[miqp_gpu] %s\n", why); for (int k = 0; k < n; ++k) statuses[k] = MIQP_STATUS_FAILED_SEG_FAULT; return false; };
+  for (int k = 1; k < n; ++k) if (S[k]->opts.device != O0.device) return fail_all("instances of one batch must name the same device (use miqp_solver_solve_batch_multi to span devices)");
+  const double t_enter = wall_s();
+  DevCtx* Xp = ctx_for_device(O0.device, lane);
+  if (!Xp) return fail_all(nullptr);
+  warn_ignored_switches();
+  DevCtx& X = *Xp;
+  std::lock_guard<std::mutex> ctx_lock(X.mu);
+  if (hipSetDevice(X.device) != hipSuccess) return fail_all("hipSetDevice failed");
+  const CallSwitches sw = read_call_switches();
+  const CallShape sh = plan_call(Y, O0, n, inflight, lanes, split != nullptr, sw);
+  const size_t l_ipm = ipm_lds_bytes(Y), l_eval = eval_lds_bytes(Y, sw.seq_kinds);
+  CallTimes T;
+  {
+    // the fallible part of the set-up (device buffers, kernel attributes).  In a tree split the ranks agree on its outcome with
+    // one exchange before the first round: a rank that failed alone would otherwise leave its peers waiting in their all-reduce
+    bool setup_ok = ctx_prepare(X, Y, n, sh.NS, sh.open_cap, sh.npr, sh.MAXR, sh.clamp_open, lanes, &T.ctx_built);
+    if (setup_ok && (l_ipm > 160 * 1024 || l_eval > 160 * 1024)) { std::fprintf(stderr, "[miqp_gpu] instance too large for LDS (%zu bytes)\n", l_ipm); setup_ok = false; }
+    if (setup_ok && !set_kernel_lds(Y, l_ipm, l_eval)) setup_ok = false;
+    if (split) {
+      unsigned long long w = setup_ok ? 1ull : 0ull;
+      if (split->fn(split->user, 0, &w, 1, 0) != 0) return fail_all("set-up exchange failed");
+      if (setup_ok && w == 0ull) return fail_all("another rank of the tree split failed its set-up");
+    }
+    if (!setup_ok) return fail_all(nullptr);
+  }
+  T.t_ctx = wall_s() - t_enter;
+  HostTables H;
+  prepare_instances(S, Y, sh, split, H);
+  T.t_tables = wall_s() - t_enter - T.t_ctx;
+  apply_call_switches(X, sh, sw, H.h_gap);
+  if (!upload_and_reset(X, H, sh)) return fail_all(nullptr);
+
+  Rounds L(X, sh, H, split, O0.verbose, l_eval);
+  if (!L.run()) return fail_all(nullptr);
+  T.t_setup = L.t0 - t_enter;
+  if (sw.dump_open && !dump_open_list(X, sw.dump_open, L.rounds, sh.NS, H.h_const[0])) return fail_all(nullptr);
+
+  Polished P;
+  if (!polish(X, n, P, T.ms_all)) return fail_all(nullptr);
+#ifdef MIQP_PROFILE
+  if (!print_profile(X)) return fail_all(nullptr);
+#endif
+  if (X.B.stats && !print_stats(X)) return fail_all(nullptr);
+  if (process_switches().round_log) { std::fprintf(stderr, "[rounds]"); for (int v : L.round_bc) std::fprintf(stderr, " %d", v); std::fprintf(stderr, "\n"); }
+  for (size_t e = 0; e + 1 < L.nev; e += 2) { float ms = 0; HIP_OK(hipEventElapsedTime(&ms, X.ipm_ev[e], X.ipm_ev[e + 1])); T.ms_ipm += ms; }
+  T.std_timed = L.use_par;   // (the event is recorded in the concurrent launch path only)
+  if (T.std_timed) for (size_t e = 0; e + 1 < L.nev; e += 2) { float ms = 0; if (hipEventElapsedTime(&ms, X.ipm_ev[e], X.std_ev[e / 2]) == hipSuccess) T.ms_std += ms; }
+  T.t_solve = wall_s() - L.t0;
+
+  Results R;
+  if (!read_back(X, n, R) || !take_polished(X, S, n, H, P, R)) return fail_all(nullptr);
+  if (split && !split_broadcast(split, L.sp, R)) return fail_all(nullptr);
+  report(S, statuses, Y, H, L, R, T, split != nullptr);
+  if (sw.stats) std::fprintf(stderr, "[miqp_gpu stats] reachable-set diameter (L1) of instance 0: %.1f\n", H.D[Y.d_misc + 2]);
+  if (sw.stats) std::fprintf(stderr, "[miqp_gpu stats] host: setup %.3f s (device context %.3f, instance tables and presolve %.3f, upload %.3f), rounds %.3f s (%d), results %.3f s\n", T.t_setup, T.t_ctx, T.t_tables, T.t_setup - T.t_ctx - T.t_tables, T.t_solve, L.rounds, wall_s() - L.t0 - T.t_solve);
+  return !L.abandoned;
 }
 
 }  // namespace
@@ -1638,7 +1695,7 @@ int miqp_solver_solve_batch(miqp_solver_t* const* solvers, int n, int* statuses)
 // longer than the slots.
 int miqp_solver_solve_stream(miqp_solver_t* const* solvers, int n, int inflight, int* statuses) {
   if (!solvers || n < 1 || !statuses) return -1;
-  int lanes = KNOB_P("MIQP_LANES") ? std::atoi(KNOB_P("MIQP_LANES")) : 1;
+  int lanes = knob_int(KNOB_P("MIQP_LANES"), 1);
   if (lanes > 8) lanes = 8;
   while (lanes > 1 && (inflight <= 0 || inflight >= n || inflight / lanes < 128)) lanes--;
   if (lanes <= 1) return solve_batch_impl(solvers, n, statuses, nullptr, inflight) ? 0 : -2;
@@ -2064,7 +2121,7 @@ int miqp_solver_solve_fixed(miqp_solver_t* s, const miqp_raw_results_c* fixed, m
   DevCtx& X = *Xp;
   std::lock_guard<std::mutex> ctx_lock(X.mu);
   if (!ctx_prepare(X, Y, 1, 1, 64, 16, 3)) return -3;
-  if (!set_kernel_lds(Y, ipm_lds_bytes(Y), eval_lds_bytes(Y))) return -3;
+  if (!set_kernel_lds(Y, ipm_lds_bytes(Y), eval_lds_bytes(Y, read_call_switches().seq_kinds))) return -3;
   std::vector<double> D(Y.dstride); std::vector<int> T(Y.istride);
   compile_instance(s->inst, Y, D.data(), T.data());
   std::vector<signed char> fix;

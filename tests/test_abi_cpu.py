@@ -359,6 +359,14 @@ def test_environment_switches_of_the_shipped_library_are_the_documented_ones():
     sec = doc[doc.index("## 5. Environment switches"):]
     table = set(re.findall(r"^\| `(MIQP_[A-Z0-9_]+)` \|", sec, re.M))
     assert table == prod, (sorted(table - prod), sorted(prod - table))
+    # warn_ignored_switches() must not report a variable that the repository itself reads: its list holds the KNOB_P names and every
+    # MIQP_* variable that bench.py and the Python package read from the environment
+    known = set(re.findall(r'"(MIQP_[A-Z0-9_]+)"', re.search(r"known\[\] = \{(.*?)\};", src, re.S).group(1)))
+    pyread = set()
+    for f in [os.path.join(root, "bench.py")] + sorted(os.path.join(root, "planner_miqp_amd", g) for g in os.listdir(os.path.join(root, "planner_miqp_amd")) if g.endswith(".py")):
+        pyread |= set(re.findall(r'environ(?:\.get\(|\.setdefault\(|\[)\s*["\'](MIQP_[A-Z0-9_]+)["\']', open(f).read()))
+    assert {"MIQP_GPU_LIB", "MIQP_BENCH_MAT_THREADS"} <= pyread, pyread
+    assert prod | pyread <= known, sorted((prod | pyread) - known)
     lib = P.library_path()
     if os.path.exists(lib):
         blob = open(lib, "rb").read()
