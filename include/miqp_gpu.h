@@ -176,7 +176,7 @@ int miqp_solver_solve_fixed(miqp_solver_t* s, const miqp_raw_results_c* fixed, m
  * out[3] = node relaxations solved, out[4] = IPM iterations (summed over nodes), out[5] = rows x iterations */
 int miqp_solver_last_timing(const miqp_solver_t* s, double* out6);
 
-/* the dual active-set launches of the last solve / batch (two cars: the node relaxations of a round; the reference's counterpart is CPLEX's dual
+/* the dual active-set launches of the last solve / batch (one and two cars of up to 20 steps, miqp_gpu_has_active_set: the node relaxations of a round; the reference's counterpart is CPLEX's dual
  * simplex re-solve of a child node inside cplex.solve(), src/cplex_wrapper.cpp:158-185): out[0] = node relaxations they solved,
  * out[1] = their steps (rows added + rows dropped; they are part of out[4] of miqp_solver_last_timing and of NrIterations),
  * out[2] = nodes they could not finish (returned unsolved, solved by the interior point a round later), out[3] = rows dropped,
@@ -184,6 +184,10 @@ int miqp_solver_last_timing(const miqp_solver_t* s, double* out6);
  * out[6] = seconds of the STANDARD active-set launches alone (HIP events on the solver stream: from the start of a round's launch group
  * to the end of that kernel; the other three launches of the group run beside it on their own streams), out[7] = number of those launches */
 int miqp_solver_last_active_set(const miqp_solver_t* s, double* out8);
+
+/* 1 when instances of this shape (NrCars, N) have the dual active-set launches - one or two cars, a horizon of up to 20 steps - else 0 (their node
+ * relaxations are interior point solves).  Pure host code: no device is needed or touched.  A call switches the launches off with MIQP_AS=0 */
+int miqp_gpu_has_active_set(int num_cars, int num_steps);
 
 /* host set-up of the last solve / batch / stream call this handle took part in: out[0] = seconds from the entry of the call to
  * the first round, out[1] = of which building the device context (pools, lists: reused by a call of the same shape with no more

@@ -1,6 +1,6 @@
 // as_onchip.hip - dual active-set solve of a node relaxation, whole working set on chip (included by kernels.hip behind ipm_onchip.hip).
 //
-// What it replaces: the interior point of ipm_onchip_kernel<2, ...> for the ordinary nodes of a round (everything but the rounding probes, the
+// What it replaces: the interior point of ipm_onchip_kernel<C, ...>, C = 1 or 2 cars (as_shape_ok below), for the ordinary nodes of a round (everything but the rounding probes, the
 // local-search leaves and the marked large records, which stay with the larger interior point variant: their infeasible relaxations are
 // re-rounded from the least-violation point only an elastic interior point delivers).  Region of the reference this stands for:
 // cplex.solve()'s node re-solves, src/cplex_wrapper.cpp:158-185 (CPLEX re-solves a child by dual simplex pivots from the parent's basis).
@@ -22,6 +22,13 @@
 //
 // Layout: the LDS block of ipm_onchip_kernel (oc_lds_layout: same decode, same capacities, 8 wavefronts per CU); the region of the decode
 // scratch becomes the substitution vector V | the chain gains, the region of the box keys the feed-forward terms.
+//
+// One source for both car counts.  What depends on C: the column map (as_col), the number of chains the substitution runs on (2C lanes of the 64),
+// how the host's regulator tables - packed over the 2C chains - are spread to the kernel's fixed strides, and where the owner lanes' activity words
+// live.  Everything else is the car count's through NZ alone: a stage keeps 16 columns, the gains and feed-forward terms four chain slots, the lane
+// map (column, side, parity of the stage) 64 owners - one car uses columns 0 .. 7, so the lanes of columns 8 .. 15 own no box row and chains 2, 3
+// are never walked; M, the scans and the ratio tests run over 64 lanes either way.  The one-car model has no car/car rows (NP = 0: decode classes 6
+// and 7 are empty), and its max_vel rows keep the reference's quirk per car as two cars do (vel_x bounded on both sides, vel_y from below only).
 namespace miqp {
 
 #ifdef MIQP_PROFILE
@@ -37,17 +44,24 @@ constexpr double AS_DEP = 1.0e-8;
 constexpr int AS_MT = 64;               // active sets of up to this many rows hand their M to the children (56 until the last day of round 6: the children of the 57 - 64 row nodes rebuilt theirs with a substitution per row)
 constexpr int AS_MSTR = AS_MT * (AS_MT + 1) / 2;   // doubles per slot of the ring (packed triangle)      // curvature g P g' below this share of g H^-1 g': the row depends on the active ones
 
+// The shapes that have the active-set launches, decided HERE and nowhere else (the context's capacities, the launches, the kernels' LDS attributes,
+// the ring and miqp_gpu_has_active_set all ask this): one or two cars - a stage of up to 16 columns, an active set of up to 64 rows per wavefront -
+// and a horizon within the box-row slots of a lane.  (A context adds what only it knows: that the on-chip grid exists, CtxSizes::as_cap.)
+__host__ __device__ constexpr bool as_shape_ok(int C, int N) { return (C == 1 || C == 2) && N >= 1 && N <= 2 * OC_NSL; }
+
 // Column order inside this kernel: CHAIN-CONTIGUOUS - (position, velocity, acceleration, jerk) of chain ch = 2 car + axis at 4 ch .. 4 ch + 3 (the
-// transpose of ipm_onchip_kernel's chain-major 4 k + ch; an involution), so that the lane of a chain reads and writes its stage entries as two
-// 16-byte LDS accesses
-__device__ inline int as_col(int pq) { return ((pq & 3) << 2) | (pq >> 2); }
+// transpose of ipm_onchip_kernel's chain-major 2C k + ch: an involution for two cars, whose 4 x 4 it transposes; for one car the 4 x 2 of its two
+// chains goes to columns 0 .. 7 and as_pcol is the way back), so that the lane of a chain reads and writes its stage entries as two 16-byte LDS
+// accesses.  A stage keeps 16 columns for either car count: one car leaves columns 8 .. 15 - and the lanes that own them - empty
+template <int C> __device__ inline int as_col(int pq) { return C == 2 ? ((pq & 3) << 2) | (pq >> 2) : ((pq & 1) << 2) | (pq >> 1); }
+template <int C> __device__ inline int as_pcol(int q) { return C == 2 ? ((q & 3) << 2) | (q >> 2) : ((q & 3) << 1) | (q >> 2); }   // kernel column -> chain-major column
 
 // GCAP = OC_GCAP: the ordinary nodes of a round (8 wavefronts per CU).  GCAP = OC_GCAP_BIG: the nodes known to be large before the round - rounding
 // probes, local-search leaves, marked records - beside it on a third stream (4 wavefronts per CU), except the ones large_class() leaves to the
 // interior point chain on the second stream (records the method failed on before or that exceed even this block, probes that may be re-rounded)
 template <int C, int NSL, int GCAP = miqp::OC_GCAP>
 __global__ void __launch_bounds__(64, (GCAP > 128 ? 1 : 2)) as_onchip_kernel(DevBuf B) {
-  static_assert(C == 2, "chain-major columns of two cars");
+  static_assert(C == 1 || C == 2, "a stage of 16 columns holds the chains of up to two cars");
   constexpr bool CM = true;
   constexpr bool BIG = GCAP > 128;
   constexpr int OC_GCAP = GCAP, OC_GSLOTS = OC_GCAP / 64, OC_GCOEF = oc_gcoef_of(OC_GCAP);
@@ -125,7 +139,7 @@ __global__ void __launch_bounds__(64, (GCAP > 128 ? 1 : 2)) as_onchip_kernel(Dev
     {
       const signed char* src = B.pool_fix + (size_t)B.batch_node[node] * Y.fixlen;
       for (int k = tid; k < Y.fixlen; k += 64) fix[k] = src[k];
-      if (tid < 16) Wd[tid] = tid < NZ ? D[Y.d_wd + oc_lcol<C, CM>(as_col(tid))] : 0.0;
+      if (tid < 16) Wd[tid] = tid < NZ ? D[Y.d_wd + oc_lcol<C, CM>(as_pcol<C>(tid))] : 0.0;
       for (int k = tid; k < N * 32; k += 64) bkey[k] = ~0ull;
       for (int k = tid; k <= N + 1; k += 64) sstart[k] = 0;
     }
@@ -158,7 +172,7 @@ __global__ void __launch_bounds__(64, (GCAP > 128 ? 1 : 2)) as_onchip_kernel(Dev
       auto take = [&](int i, int slot) {
         if (decode_row<C, false>(Y, D, T, fix, i, slot, nullptr).active) {
           int col; double sg, rh;
-          if (box_of_slot<C>(Y, D, T, fix, i, slot, col, sg, rh)) atomicMin(&bkey[(i * 2 + (sg < 0.0 ? 1 : 0)) * 16 + as_col(oc_pcol<C, CM>(col))], d2key(rh));
+          if (box_of_slot<C>(Y, D, T, fix, i, slot, col, sg, rh)) atomicMin(&bkey[(i * 2 + (sg < 0.0 ? 1 : 0)) * 16 + as_col<C>(oc_pcol<C, CM>(col))], d2key(rh));
           else { const int pcode = i * NSLOT + slot; atomicOr(&bmp[pcode >> 6], 1ull << (pcode & 63)); }
         }
       };
@@ -183,7 +197,7 @@ __global__ void __launch_bounds__(64, (GCAP > 128 ? 1 : 2)) as_onchip_kernel(Dev
           const unsigned int skip = i >= 1 ? (unsigned int)T[Y.i_boxskip + c * N + i] : 0x7Fu;   // (stage 0: no state rows)
           const double* rt = code >= 0 ? D + Y.d_reg + (c * Y.P + (code >> 2)) * REGSZ : nullptr;
           const double* Hc = (!rt && i >= 1) ? region_hull(Y, D, T, fix, c, i) : nullptr;
-          auto put = [&](int col, bool neg, double rh) { atomicMin(&bkey[(i * 2 + (neg ? 1 : 0)) * 16 + as_col(oc_pcol<C, CM>(col))], d2key(rh)); };
+          auto put = [&](int col, bool neg, double rh) { atomicMin(&bkey[(i * 2 + (neg ? 1 : 0)) * 16 + as_col<C>(oc_pcol<C, CM>(col))], d2key(rh)); };
           if (i >= 1) {
             const double a_lo_x = rt ? rt[11] : Hc[0], a_hi_x = rt ? rt[12] : Hc[1], a_lo_y = rt ? rt[13] : Hc[2], a_hi_y = rt ? rt[14] : Hc[3];
             if (!(skip & 1u)) put(6 * c + 1, true, -G[0]);
@@ -259,7 +273,7 @@ __global__ void __launch_bounds__(64, (GCAP > 128 ? 1 : 2)) as_onchip_kernel(Dev
           if (v != 0.0 && nn < 6) {
 #pragma unroll
             for (int k = 0; k < 6; ++k) if (k == nn) v6[k] = v;
-            const int pq = as_col(oc_pcol<C, CM>(q));
+            const int pq = as_col<C>(oc_pcol<C, CM>(q));
             map |= (unsigned long long)(nn + 1) << (4 * pq); cols |= (unsigned int)pq << (4 * nn); nn++;
           }
         }
@@ -317,8 +331,13 @@ __global__ void __launch_bounds__(64, (GCAP > 128 ? 1 : 2)) as_onchip_kernel(Dev
     // (gains, the objective's feed-forward and the unconstrained optimum are the same for every node of an instance: host tables, host_inst.hpp::as_tables)
     const double h1 = ts, h2 = 0.5 * ts * ts, h3 = ts * ts * ts / 6.0;
     const double* const tb = D + Y.d_astab;
-    for (int k = tid; k < N * 16; k += 64) KS[k] = tb[k];
-    for (int k = tid; k < N * 4; k += 64) kref[k] = tb[N * 16 + k];
+    if constexpr (C == 2) {
+      for (int k = tid; k < N * 16; k += 64) KS[k] = tb[k];
+      for (int k = tid; k < N * 4; k += 64) kref[k] = tb[N * 16 + k];
+    } else {   // (one car: the host tables are packed over its two chains, the kernel's keep the stride of four)
+      for (int k = tid; k < N * 8; k += 64) KS[(k >> 3) * 16 + (k & 7)] = tb[k];
+      for (int k = tid; k < N * 2; k += 64) kref[(k >> 1) * 4 + (k & 1)] = tb[N * 8 + k];
+    }
     OC_WAVE_SYNC();
     // one substitution: V holds a stage-wise vector v (zero above stage itop) on entry; `out` receives, for the stages up to iend, the minimiser of
     // 1/2 z' H z + v' z over the trajectories of the dynamics from x_0 = 0 (fromx0 false: a response, -H^-1 v), or the minimiser of the
@@ -386,7 +405,7 @@ __global__ void __launch_bounds__(64, (GCAP > 128 ? 1 : 2)) as_onchip_kernel(Dev
     auto zeroV = [&]() { for (int k = tid; k < N * 16; k += 64) V[k] = 0.0; OC_WAVE_SYNC(); };
     auto objective = [&]() -> double {
       double o = 0.0;
-      for (int k = tid; k < N * 16; k += 64) { const int q = k & 15; if (q < NZ) { const double d = Z[k] - Rf[(k >> 4) * NZ + oc_lcol<C, CM>(as_col(q))]; o += Wd[q] * d * d; } }
+      for (int k = tid; k < N * 16; k += 64) { const int q = k & 15; if (q < NZ) { const double d = Z[k] - Rf[(k >> 4) * NZ + oc_lcol<C, CM>(as_pcol<C>(q))]; o += Wd[q] * d * d; } }
       return wave_sum(o);
     };
 
@@ -430,7 +449,8 @@ __global__ void __launch_bounds__(64, (GCAP > 128 ? 1 : 2)) as_onchip_kernel(Dev
       OC_WAVE_SYNC();
       subst(true, amax, N - 1, Z);
     };
-    for (int k = tid; k < N * 16; k += 64) Z[k] = tb[N * 20 + k];   // lambda = 0: the unconstrained optimum
+    if constexpr (C == 2) { for (int k = tid; k < N * 16; k += 64) Z[k] = tb[N * 20 + k]; }   // lambda = 0: the unconstrained optimum
+    else { for (int k = tid; k < N * 16; k += 64) Z[k] = (k & 15) < NZ ? tb[N * 10 + (k >> 4) * NZ + (k & 15)] : 0.0; }
     OC_WAVE_SYNC();
     ASP_T(ta2); ASP_ACC(1, ta1, ta2);
     int steps = 0, ndrop = 0, ok = 1, nwarm = 0, nfast = 0, ncold = 0;
@@ -618,8 +638,9 @@ __global__ void __launch_bounds__(64, (GCAP > 128 ? 1 : 2)) as_onchip_kernel(Dev
           for (int b = 0; b < 64; ++b) M[b] = 0.0;
           refresh();
         } else {
-          // the owner lanes learn which of their rows are active (one LDS word per owner lane, in the spent region of the fix record)
-          unsigned int* const inab = (unsigned int*)fix;
+          // the owner lanes learn which of their rows are active (one LDS word per owner lane, in the spent region of the fix record; one car: in the
+          // substitution vector, spent since refresh() as well - its fix record, 160 B at N = 20 without obstacles, is shorter than the 64 words)
+          unsigned int* const inab = C == 2 ? (unsigned int*)fix : (unsigned int*)V;
           inab[tid] = 0u;
           OC_WAVE_SYNC();
           if (arow >= 0) {
@@ -765,7 +786,7 @@ __global__ void __launch_bounds__(64, (GCAP > 128 ? 1 : 2)) as_onchip_kernel(Dev
     }
     const double obj = (infeas || ok == 2) ? Dval : objective() + scost;
     double* Zo = B.batch_Z + (size_t)node * N * NZ;
-    for (int k = tid; k < N * 16; k += 64) { const int q = k & 15; if (q < NZ) Zo[(k >> 4) * NZ + oc_lcol<C, CM>(as_col(q))] = Z[k]; }
+    for (int k = tid; k < N * 16; k += 64) { const int q = k & 15; if (q < NZ) Zo[(k >> 4) * NZ + oc_lcol<C, CM>(as_pcol<C>(q))] = Z[k]; }
     if (B.batch_A) {   // the final active set, by row identity, for the children's starts
       unsigned short enc = 0xFFFFu;
       if (!fail && !infeas && ok == 1 && arow >= 0) enc = arow < 1024 ? (unsigned short)arow : (unsigned short)(1024 + (int)cand[arow - 1024]);

@@ -336,7 +336,7 @@ struct DevCtx {
   int ocb_grid = 0;  // resident wavefronts of its larger variant (OC_GCAP_BIG general rows, one wavefront per SIMD; 0: not in use)
   bool as_on = false, as_cap = false; unsigned long long* as_stats = nullptr;
   int* cls_list = nullptr; int cls_n[3] = {-1, -1, -1};   // the round's class lists and (read back with the batch count) their lengths; -1: not known, the launches scan the batch
-  unsigned short* as_batch_A = nullptr; unsigned short* as_pool_A = nullptr;   // (kept here: a call with MIQP_AS=0 runs with the DevBuf pointers nulled)   // dual active-set launch in front of the standard interior point launch (two cars; MIQP_AS=0: off)
+  unsigned short* as_batch_A = nullptr; unsigned short* as_pool_A = nullptr;   // (kept here: a call with MIQP_AS=0 runs with the DevBuf pointers nulled)   // dual active-set launch in front of the standard interior point launch (the shapes of as_shape_ok; MIQP_AS=0: off)
   DevBuf B{};
   CallSwitches sw;   // of the call that holds the context (apply_call_switches)
   std::vector<void*> allocs;
@@ -453,12 +453,16 @@ CtxSizes ctx_sizes(const Layout& Y, int n_inst, int n_slots, int open_cap, int n
     size_t zc = std::max<size_t>((size_t)2 << 20, (size_t)n_slots * 16384);
     Z.z_cap = (int)std::min(zc, std::min<size_t>((size_t)Z.pool_cap, free_b / 8 / zb));
   }
-  Z.as_cap = Y.C == 2 && Z.oc_grid > 0;   // the shape has the active-set launches (whether a call uses them: MIQP_AS, read per call)
+  Z.as_cap = as_shape_ok(Y.C, Y.N) && Z.oc_grid > 0;   // the shape has the active-set launches (whether a call uses them: MIQP_AS, read per call)
   Z.as_starts = Z.as_cap && Z.z_cap > 0 && Y.N * Y.NSLOT + 1024 < 65535;   // the parents' active sets for the children's starts (128 B per record)
   if (Z.as_starts) {
     // ... and the ring their M travels through (4 KB per node on average, at most 12.8): a quarter of the free memory, at most 96 GB
-    const size_t rd = std::min<size_t>(std::min<size_t>((size_t)12 << 30, free_b / 4 / 8), std::max<size_t>((size_t)1 << 30, (size_t)n_slots * ((size_t)8 << 20)));   // doubles: 64 MB per instance in flight, at least 8 GB (a single solve: hundreds of its rounds; a large allocation costs seconds when the context is built)
     const size_t margin = (size_t)batch_alloc * AS_MSTR + ((size_t)1 << 20);   // what one round's launches can allocate, and more
+    // two cars: 64 MB per instance in flight, at least 8 GB (a single solve: hundreds of its rounds; a large allocation costs seconds when the context is built).
+    // One car - the single planning call, whose context should stay small: four times what a round of batch_alloc nodes can write if every one of them
+    // left a full triangle (an M stays whole for three such rounds at the least; at the ~20 active rows of a node, 1.7 KB of the 16.6 KB, for tens)
+    const size_t rd = Y.C == 1 ? std::min<size_t>(free_b / 4 / 8, 4 * margin)
+                               : std::min<size_t>(std::min<size_t>((size_t)12 << 30, free_b / 4 / 8), std::max<size_t>((size_t)1 << 30, (size_t)n_slots * ((size_t)8 << 20)));   // doubles
     if (rd >= 2 * margin) { Z.ring_doubles = rd; Z.ring_margin = margin; }
   }
   // buffers of the concurrent probe launch (two cars and fewer, on-chip kernel in use): 1024 resident blocks
@@ -518,7 +522,7 @@ bool ctx_alloc(DevCtx& X, const CtxSizes& Z, const CtxSwitches& cs, int n_call, 
   if (!X.alloc(&B.inc_ext, n_inst)) return false;
   if (!X.alloc(&B.inc_fix, (size_t)n_inst * Y.fixlen)) return false;
   if (!X.alloc(&B.inc_Z, (size_t)n_inst * Y.N * Y.nz)) return false;
-  if (Y.C == 2) { if (!X.alloc(&B.inc_A, (size_t)n_inst * 64) || !X.alloc(&B.inc_Mtag, (size_t)n_inst)) return false; } else { B.inc_A = nullptr; B.inc_Mtag = nullptr; }
+  if (as_shape_ok(Y.C, Y.N)) { if (!X.alloc(&B.inc_A, (size_t)n_inst * 64) || !X.alloc(&B.inc_Mtag, (size_t)n_inst)) return false; } else { B.inc_A = nullptr; B.inc_Mtag = nullptr; }
   if (!X.alloc(&B.lower_bound, n_inst)) return false;
   if (!X.alloc(&B.inst_done, n_inst)) return false;
   if (!X.alloc(&B.inst_flags, n_inst)) return false;
@@ -687,7 +691,7 @@ void launch_ipm_batch(DevCtx& X, const DevBuf& B, int bc, hipStream_t st, bool o
   if (X.oc_grid > 0) {
     const size_t l_oc = (size_t)oc_lds_layout(Y.N, Y.fixlen).total;
     const size_t l_ocb = (size_t)oc_lds_layout(Y.N, Y.fixlen, OC_GCAP_BIG).total;
-    const size_t l_ocb_as = Y.C == 2 && X.sw.big_pad ? oc_big_lds_beside_as(Y) : l_ocb;
+    const size_t l_ocb_as = as_shape_ok(Y.C, Y.N) && X.sw.big_pad ? oc_big_lds_beside_as(Y) : l_ocb;
     const bool big = X.ocb_grid > 0;
     const bool ov = overlap && X.probe_grid > 0 && X.stream2 && bc <= 4096;   // (a full batch keeps the device busy on its own: measured no gain there, 5.4 against 5.1 s on a 2048-instance queue; single solves: median 6.0 instead of 7.0 ms)
     DevBuf Bc = B;
@@ -706,7 +710,7 @@ void launch_ipm_batch(DevCtx& X, const DevBuf& B, int bc, hipStream_t st, bool o
       DevBuf Bp = Bc; Bp.ovf_mode = 2; Bp.work_counter = pc ? cs + 4 : X.work_counter2; Bp.rowstate = X.rowstate2; Bp.rowcache = X.rowcache2; Bp.kgain = X.kgain2;
       const ProcessSwitches& ps = process_switches();
       const int gb = std::min(std::min(bc, ps.big_grid_cap), std::min(X.probe_grid, X.ocb_grid));
-      const bool as2 = X.as_on && pc && Y.C == 2 && X.stream3;
+      const bool as2 = X.as_on && pc && X.stream3;   // (as_on: the shape has the launches - as_shape_ok - and the call has not switched them off)
       const bool lists = as2 && X.stream4 && B.cls_list && X.cls_n[0] >= 0;
       // With the class lists the larger launches get the SHARE of the device their work is of the round's, not all of it: their wavefronts take a SIMD
       // each (450 / 424 registers) and are enqueued first - a full grid of them held every SIMD until the larger active-set launch was through
@@ -726,11 +730,11 @@ void launch_ipm_batch(DevCtx& X, const DevBuf& B, int bc, hipStream_t st, bool o
         DevBuf Bq = Bp; Bq.work_counter = cs + 6;
         if (lists) Bq.cls_take = 1;
         const int g1 = lists ? std::min(std::min(gb, g1s), X.cls_n[0]) : gb;   // (with the class lists: as many workgroups as the class has nodes, none when it is empty)
-        if (g1 > 0) hipLaunchKernelGGL((as_onchip_kernel<2, OC_NSL, OC_GCAP_BIG>), dim3(g1), dim3(64), l_ocb_as, X.stream3, Bq);
+        if (g1 > 0) hipLaunchKernelGGL((Y.C == 1 ? as_onchip_kernel<1, OC_NSL, OC_GCAP_BIG> : as_onchip_kernel<2, OC_NSL, OC_GCAP_BIG>), dim3(g1), dim3(64), l_ocb_as, X.stream3, Bq);
         (void)hipEventRecord(X.ev_join3, X.stream3);
         Bp.as_split = 1;
       }
-      if (lists) { Bp.cls_take = 2; const int g2 = std::min(std::min(gb, g2s), X.cls_n[1]); if (g2 > 0) launch_ipm_oc_big<2>(Bp, g2, l_ocb_as, X.stream2, false); Bp.cls_take = 0; }
+      if (lists) { Bp.cls_take = 2; const int g2 = std::min(std::min(gb, g2s), X.cls_n[1]); if (g2 > 0) { if (Y.C == 1) launch_ipm_oc_big<1>(Bp, g2, l_ocb_as, X.stream2, false); else launch_ipm_oc_big<2>(Bp, g2, l_ocb_as, X.stream2, false); } Bp.cls_take = 0; }
       else
       if (Y.C == 1) launch_ipm_oc_big<1>(Bp, gb, l_ocb, X.stream2, !pc); else launch_ipm_oc_big<2>(Bp, gb, l_ocb, X.stream2, !pc);
       DevBuf Bm = Bp; Bm.ovf_mode = 1; Bm.ovf_count = Bc.ovf2_count; Bm.ovf_list = B.ovf2_list; if (pc) Bm.work_counter = cs + 5;
@@ -745,14 +749,14 @@ void launch_ipm_batch(DevCtx& X, const DevBuf& B, int bc, hipStream_t st, bool o
       launch_ipm_c(Y.C, Bm, std::min(bc, X.probe_grid), l_ipm, X.stream2, !pc);
       (void)hipEventRecord(X.ev_join, X.stream2);
       Bc.skip_probes = 1; Bc.bounce = 1;
-      if (X.as_on && pc && Y.C == 2) {
+      if (X.as_on && pc) {
         // the ordinary nodes of the round: dual active-set solves (as_onchip.hip) in place of the standard interior point launch; a node that
         // launch cannot finish comes back marked, like a node that is too large, and the larger interior point variant takes it next round
         DevBuf Ba = Bc; Ba.work_counter = cs + 1;
         const size_t l_as = (size_t)oc_lds_layout(Y.N, Y.fixlen, OC_GCAP, true).total;
         const int ch_ = std::max(1, Ba.as_chunk);
         const int ga = Ba.as_quota > 0 ? std::max(1, (bc + Ba.as_quota * ch_ - 1) / (Ba.as_quota * ch_)) : std::min(bc, X.oc_grid);
-        hipLaunchKernelGGL((as_onchip_kernel<2, OC_NSL>), dim3(ga), dim3(64), l_as, st, Ba);
+        hipLaunchKernelGGL((Y.C == 1 ? as_onchip_kernel<1, OC_NSL> : as_onchip_kernel<2, OC_NSL>), dim3(ga), dim3(64), l_as, st, Ba);
       } else if (Y.C == 1) launch_ipm_oc<1>(Bc, std::min(bc, X.oc_grid), l_oc, st, !pc); else launch_ipm_oc<2>(Bc, std::min(bc, X.oc_grid), l_oc, st, !pc);
       if (X.ev_mid) (void)hipEventRecord(X.ev_mid, st);
       if (ev_std_end) (void)hipEventRecord(ev_std_end, st);   // (where the standard launch of the round ends: the dominant kernel's own time)
@@ -794,8 +798,8 @@ void launch_eval_c(int C, const DevBuf& B, int nblocks, size_t lds, hipStream_t 
 template <int C> bool set_kernel_lds_oc(size_t lds, size_t lds_big) {
   HIP_OK(hipFuncSetAttribute((const void*)ipm_onchip_kernel<C, OC_NSL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   HIP_OK(hipFuncSetAttribute((const void*)ipm_onchip_kernel<C, OC_NSL, 0, OC_GCAP_BIG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_big));
-  if constexpr (C == 2) { HIP_OK(hipFuncSetAttribute((const void*)as_onchip_kernel<2, OC_NSL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    HIP_OK(hipFuncSetAttribute((const void*)as_onchip_kernel<2, OC_NSL, OC_GCAP_BIG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_big)); }
+  if constexpr (as_shape_ok(C, 2 * OC_NSL)) { HIP_OK(hipFuncSetAttribute((const void*)as_onchip_kernel<C, OC_NSL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIP_OK(hipFuncSetAttribute((const void*)as_onchip_kernel<C, OC_NSL, OC_GCAP_BIG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_big)); }
   return true;
 }
 template <int C> bool set_kernel_lds_c(size_t ipm_lds, size_t eval_lds) {
@@ -805,7 +809,7 @@ template <int C> bool set_kernel_lds_c(size_t ipm_lds, size_t eval_lds) {
 }
 bool set_kernel_lds(const Layout& Y, size_t ipm_lds, size_t eval_lds) {
   if (Y.C <= 2 && Y.N <= 2 * OC_NSL) {
-    const size_t l = (size_t)oc_lds_layout(Y.N, Y.fixlen).total, lb = std::max((size_t)oc_lds_layout(Y.N, Y.fixlen, OC_GCAP_BIG).total, Y.C == 2 ? oc_big_lds_beside_as(Y) : (size_t)0);
+    const size_t l = (size_t)oc_lds_layout(Y.N, Y.fixlen).total, lb = std::max((size_t)oc_lds_layout(Y.N, Y.fixlen, OC_GCAP_BIG).total, as_shape_ok(Y.C, Y.N) ? oc_big_lds_beside_as(Y) : (size_t)0);
     if (l <= 160 * 1024 && !(Y.C == 1 ? set_kernel_lds_oc<1>(l, lb) : set_kernel_lds_oc<2>(l, lb))) return false;
   }
   switch (Y.C) { case 1: return set_kernel_lds_c<1>(ipm_lds, eval_lds); case 2: return set_kernel_lds_c<2>(ipm_lds, eval_lds);
@@ -1531,8 +1535,12 @@ void report(miqp_solver_t* const* S, int* statuses, const Layout& Y, const HostT
       double lb = std::min(R.lb[k], R.inc[k]);
       // nodes within the gap of the incumbent are dropped without being refined: what is proven is the smaller of the open
       // list's best bound and incumbent - gap*|incumbent| (CPLEX reports the bound of its remaining nodes the same way)
-      lb = std::min(lb, R.inc[k] - H.h_gap[k] * std::fabs(R.inc[k]));
+      const double lb_tol = R.inc[k] - H.h_gap[k] * std::fabs(R.inc[k]);
+      lb = std::min(lb, lb_tol);
       s->props.best_bound = lb; s->props.gap = std::fabs(lb - R.inc[k]) / (1e-10 + std::fabs(R.inc[k]));
+      // (a proof closed to the tolerance reports a gap of at most the tolerance: the rounding of the subtraction above put the quotient 1e-16 over it
+      // for every second incumbent at tolerances of 1e-6 and below - whether `gap <= tolerance` held depended on the last bit of the objective)
+      if (lb == lb_tol && s->props.gap > H.h_gap[k]) s->props.gap = H.h_gap[k];
       s->props.status = unfinished ? MIQP_CPX_STAT_TIME_LIM_FEAS : (s->props.gap <= 1e-9 ? MIQP_CPX_STAT_OPTIMAL : MIQP_CPX_STAT_OPTIMAL_TOL);
       s->Z.assign(R.Z.begin() + (size_t)k * Y.N * Y.nz, R.Z.begin() + (size_t)(k + 1) * Y.N * Y.nz);
       s->comp.assign(R.fix.begin() + (size_t)k * Y.fixlen, R.fix.begin() + (size_t)(k + 1) * Y.fixlen);
@@ -1932,6 +1940,8 @@ int miqp_solver_last_active_set(const miqp_solver_t* s, double* out8) {
   for (int k = 0; k < 8; ++k) out8[k] = s->as_timing[k];
   return 0;
 }
+
+int miqp_gpu_has_active_set(int num_cars, int num_steps) { return miqp::as_shape_ok(num_cars, num_steps) ? 1 : 0; }
 
 int miqp_solver_last_setup(const miqp_solver_t* s, double* out3) {
   if (!s || !out3) return -1;

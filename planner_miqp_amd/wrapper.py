@@ -90,6 +90,7 @@ def load_library():
     L.miqp_solver_certify_batch.restype = C.c_int; L.miqp_solver_certify_batch.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(CertificateC)]
     L.miqp_gpu_certificate_size.restype = C.c_int; L.miqp_gpu_certificate_size.argtypes = []
     L.miqp_gpu_certify_last_timing.restype = C.c_int; L.miqp_gpu_certify_last_timing.argtypes = [C.POINTER(C.c_double)]
+    L.miqp_gpu_has_active_set.restype = C.c_int; L.miqp_gpu_has_active_set.argtypes = [C.c_int, C.c_int]
     L.miqp_gpu_version.restype = C.c_char_p
     _LIB = L
     return L
@@ -107,7 +108,14 @@ EXPORTED_SYMBOLS = ["miqp_solver_create", "miqp_solver_destroy", "miqp_solver_se
                     "miqp_solver_solve_split", "miqp_solver_solve_split_rccl", "miqp_solver_split_roots", "miqp_comm_unique_id",
                     "miqp_comm_init", "miqp_comm_finalize", "miqp_comm_selftest", "miqp_solver_solve_stream", "miqp_solver_materialize_results",
                     "miqp_initial_pose_check", "miqp_select_environment", "miqp_obstacle_intersects_environment", "miqp_obstacles_roi", "miqp_bark_trajectory", "miqp_obstacle_intersects_environment_roi", "miqp_environment_warmstart",
-                    "miqp_solver_certify", "miqp_solver_certify_batch", "miqp_gpu_certificate_size", "miqp_gpu_certify_last_timing"]
+                    "miqp_solver_certify", "miqp_solver_certify_batch", "miqp_gpu_certificate_size", "miqp_gpu_certify_last_timing",
+                    "miqp_gpu_has_active_set"]
+
+
+def has_active_set(cars, steps):
+    """1 when instances of `cars` cars and `steps` steps have the dual active-set launches for their node relaxations (one or two
+    cars, up to 20 steps), else 0: those shapes stay with the interior point.  Host code of the library; needs no device."""
+    return int(load_library().miqp_gpu_has_active_set(int(cars), int(steps)))
 
 
 class OptimizationStatus(enum.IntEnum):  # src/cplex_wrapper.hpp:54-59
