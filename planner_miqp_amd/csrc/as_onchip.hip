@@ -1,4 +1,4 @@
-// as_onchip.hip - dual active-set solve of a node relaxation, whole working set on chip (included by kernels.hip behind ipm_onchip.hip).
+// as_onchip.hip - dual active-set solve of a node relaxation, whole working set on chip (included by kernels.hip behind oc_decode.hip and ipm_onchip.hip).
 //
 // What it replaces: the interior point of ipm_onchip_kernel<C, ...>, C = 1 or 2 cars (as_shape_ok below), for the ordinary nodes of a round (everything but the rounding probes, the
 // local-search leaves and the marked large records, which stay with the larger interior point variant: their infeasible relaxations are
@@ -20,8 +20,9 @@
 // A node the method cannot finish (64 active rows, step cap, loss of precision) is marked and returned unsolved; the larger interior point
 // variant takes it in its concurrent launch of the next round (the same path as a node with more rows than the LDS block holds).
 //
-// Layout: the LDS block of ipm_onchip_kernel (oc_lds_layout: same decode, same capacities, 8 wavefronts per CU); the region of the decode
-// scratch becomes the substitution vector V | the chain gains, the region of the box keys the feed-forward terms.
+// Layout: the LDS block of ipm_onchip_kernel (oc_lds_layout: same capacities, 8 wavefronts per CU), filled by the decode both kernels call
+// (oc_decode.hip; what this kernel asks of it differently is AsDecode below); the region of the decode scratch becomes the substitution vector
+// V | the chain gains, the region of the box keys the feed-forward terms.
 //
 // One source for both car counts.  What depends on C: the column map (as_col), the number of chains the substitution runs on (2C lanes of the 64),
 // how the host's regulator tables - packed over the 2C chains - are spread to the kernel's fixed strides, and where the owner lanes' activity words
@@ -55,6 +56,12 @@ __host__ __device__ constexpr bool as_shape_ok(int C, int N) { return (C == 1 ||
 // accesses.  A stage keeps 16 columns for either car count: one car leaves columns 8 .. 15 - and the lanes that own them - empty
 template <int C> __device__ inline int as_col(int pq) { return C == 2 ? ((pq & 3) << 2) | (pq >> 2) : ((pq & 1) << 2) | (pq >> 1); }
 template <int C> __device__ inline int as_pcol(int q) { return C == 2 ? ((q & 3) << 2) | (q >> 2) : ((q & 3) << 1) | (q >> 2); }   // kernel column -> chain-major column
+// what this kernel asks of the decode (oc_decode.hip): its own column order, the state / input bounds by one lane per (car, stage), the identity of
+// every packed row (a child maps its parent's active rows to its own through them), the two clock readings of the profile build
+template <int C> struct AsDecode {
+  static constexpr bool LANE_BOUNDS = true, ROW_IDENTITY = true, MARKS = true;
+  static __device__ int col(int l) { return as_col<C>(oc_pcol<C, true>(l)); }
+};
 
 // GCAP = OC_GCAP: the ordinary nodes of a round (8 wavefronts per CU).  GCAP = OC_GCAP_BIG: the nodes known to be large before the round - rounding
 // probes, local-search leaves, marked records - beside it on a third stream (4 wavefronts per CU), except the ones large_class() leaves to the
@@ -140,17 +147,16 @@ __global__ void __launch_bounds__(64, (GCAP > 128 ? 1 : 2)) as_onchip_kernel(Dev
       const signed char* src = B.pool_fix + (size_t)B.batch_node[node] * Y.fixlen;
       for (int k = tid; k < Y.fixlen; k += 64) fix[k] = src[k];
       if (tid < 16) Wd[tid] = tid < NZ ? D[Y.d_wd + oc_lcol<C, CM>(as_pcol<C>(tid))] : 0.0;
-      for (int k = tid; k < N * 32; k += 64) bkey[k] = ~0ull;
-      for (int k = tid; k <= N + 1; k += 64) sstart[k] = 0;
+      for (int k = tid; k < N * 32; k += 64) bkey[k] = ~0ull;    // (what the decode expects on entry: no box row on any key,
+      for (int k = tid; k <= N + 1; k += 64) sstart[k] = 0;      //  no general row counted)
     }
     __syncthreads();
     const double* Rf = D + Y.d_ref;
+    // the rule of node_cutoff (kernels.hip), with the loads of the gap in front of the test as this kernel has always had them: through the helper every
+    // instantiation of this kernel comes out with other code (the standard two-car one 300 instructions longer, profiles/decode_shared_isa.txt)
     double cutoff = 1e300;
     {
       const double inc0 = fmin(inc_from_key(*(volatile unsigned long long*)&B.inc_key[inst]), B.inc_ext[inst]);
-      // (a heuristic leaf - rounding probe, neighbour of the local search - is cut off at the incumbent itself, not a gap below it: a leaf that is
-      // better by less than the gap IS the next incumbent, and the local search climbs in such steps.  The interior point never met this: it tests
-      // the cutoff only once it is nearly stationary, and a leaf started from the incumbent's solution has converged by then)
       const double gap_ = is_probe_word(B.batch_depth[node]) ? 0.0 : B.inst_gap[inst];
       if (B.use_cutoff && inc0 < 1e300) cutoff = inc0 - gap_ * (1e-10 + fabs(inc0)) - B.inst_const[inst];
     }
@@ -159,145 +165,10 @@ __global__ void __launch_bounds__(64, (GCAP > 128 ? 1 : 2)) as_onchip_kernel(Dev
     unsigned long long asp_[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #endif
     ASP_T(ta0);
-    // ---- decode (the two passes of ipm_onchip_kernel, unchanged: box rows to their (stage, side, column) key, general rows packed per stage)
-    int ngen = 0;
-    {
-      unsigned long long* const bmp = (unsigned long long*)scr;
-      const int nw = (N * NSLOT + 63) >> 6;
-      unsigned short* const pre = (unsigned short*)(bmp + nw);
-      for (int k = tid; k < nw; k += 64) bmp[k] = 0ull;
-      OC_WAVE_SYNC();
-      const int cls_off[8] = {0, 7, 11, 16, 16 + Y.EL, 16 + 5 * Y.EL, C * Y.SC, C * Y.SC + 8 * Y.NP};
-      const int cls_cnt[8] = {7, 4, 5, Y.EL, 4 * Y.EL, 5 * Y.O, 8 * Y.NP, 16 * Y.NP};
-      auto take = [&](int i, int slot) {
-        if (decode_row<C, false>(Y, D, T, fix, i, slot, nullptr).active) {
-          int col; double sg, rh;
-          if (box_of_slot<C>(Y, D, T, fix, i, slot, col, sg, rh)) atomicMin(&bkey[(i * 2 + (sg < 0.0 ? 1 : 0)) * 16 + as_col<C>(oc_pcol<C, CM>(col))], d2key(rh));
-          else { const int pcode = i * NSLOT + slot; atomicOr(&bmp[pcode >> 6], 1ull << (pcode & 63)); }
-        }
-      };
-      unsigned short* const plist = pre + ((nw + 1 + 3) & ~3);
-      const int LCAP = (int)(((char*)(L0 + LL.r) - (char*)plist) / 2) - 64;
-      int nlist = 0;
-      auto flush = [&]() {
-        OC_WAVE_SYNC();
-        for (int j0 = 0; j0 < nlist; j0 += 64) if (j0 + tid < nlist) { const int pc = plist[j0 + tid]; const int i = pc / NSLOT; take(i, pc - i * NSLOT); }
-        OC_WAVE_SYNC();
-        nlist = 0;
-      };
-      // The state / input bounds (slots 0..10 of every car and stage: decode_row's cases rr < 11 with box_of_slot's right-hand sides) - three
-      // quarters of a node's rows - one LANE PER (car, stage): its skip word, its region code and the eight box values (the region's table or the
-      // hull of the region set) are loaded once for the eleven rows, instead of eleven walks through decode_row and box_of_slot in eight passes
-      for (int e0 = 0; e0 < C * N; e0 += 64) {
-        const int e = e0 + tid;
-        if (e < C * N) {
-          const int c = e / N, i = e - c * N;
-          const double* G = D + Y.d_glob;
-          const int code = i >= 1 ? (int)fix[Y.f_reg + c * N + i] : -1;
-          const unsigned int skip = i >= 1 ? (unsigned int)T[Y.i_boxskip + c * N + i] : 0x7Fu;   // (stage 0: no state rows)
-          const double* rt = code >= 0 ? D + Y.d_reg + (c * Y.P + (code >> 2)) * REGSZ : nullptr;
-          const double* Hc = (!rt && i >= 1) ? region_hull(Y, D, T, fix, c, i) : nullptr;
-          auto put = [&](int col, bool neg, double rh) { atomicMin(&bkey[(i * 2 + (neg ? 1 : 0)) * 16 + as_col<C>(oc_pcol<C, CM>(col))], d2key(rh)); };
-          if (i >= 1) {
-            const double a_lo_x = rt ? rt[11] : Hc[0], a_hi_x = rt ? rt[12] : Hc[1], a_lo_y = rt ? rt[13] : Hc[2], a_hi_y = rt ? rt[14] : Hc[3];
-            if (!(skip & 1u)) put(6 * c + 1, true, -G[0]);
-            if (!(skip & 2u)) put(6 * c + 4, true, -G[0]);
-            if (!(skip & 4u)) put(6 * c + 1, false, G[1]);
-            if (!(skip & 8u)) put(6 * c + 2, false, a_hi_x);
-            if (!(skip & 16u)) put(6 * c + 2, true, -a_lo_x);
-            if (!(skip & 32u)) put(6 * c + 5, false, a_hi_y);
-            if (!(skip & 64u)) put(6 * c + 5, true, -a_lo_y);
-          }
-          if (i <= N - 2) {
-#pragma unroll
-            for (int s_ = 0; s_ < 2; ++s_) {
-              double lo, hi;
-              if (i == 0) { lo = D[Y.d_u0box + c * 4 + 2 * s_]; hi = D[Y.d_u0box + c * 4 + 2 * s_ + 1]; }
-              else if (rt) { lo = rt[15 + 2 * s_]; hi = rt[16 + 2 * s_]; }
-              else { lo = Hc[4 + 2 * s_]; hi = Hc[5 + 2 * s_]; }
-              put(6 * C + 2 * c + s_, false, hi); put(6 * C + 2 * c + s_, true, -lo);
-            }
-          }
-        }
-      }
-#pragma unroll 1
-      for (int cl = 0; cl < 8; ++cl) {
-#ifdef MIQP_PROFILE
-        if (cl == 2) { const long long tq_ = clock64(); asp_[9] += (unsigned long long)(tq_ - ta0); }
-#endif
-        const int cnt = cls_cnt[cl], off = cls_off[cl];
-        const bool percar = cl < 6;
-        const int per = percar ? C * cnt : cnt, total = N * per;
-        for (int e0 = 0; e0 < total; e0 += 64) {
-          const int e = e0 + tid;
-          int i = 0, slot = 0; bool in = e < total;
-          if (in) { i = e / per; const int rem = e - i * per; slot = percar ? (rem / cnt) * Y.SC + off + rem % cnt : off + rem; }
-          if (cl < 2) continue;   // (the velocity / acceleration / jerk bounds: decoded per (car, stage) below)
-          const bool cnd = in && slot_maybe<C>(Y, fix, i, slot);
-          const unsigned long long mk = __ballot(cnd);
-          if (cnd) plist[nlist + __popcll(mk & lt)] = (unsigned short)(i * NSLOT + slot);
-          nlist += __popcll(mk);
-          if (nlist > LCAP) flush();
-        }
-      }
-      flush();
-      if (tid == 0) { int a = 0; for (int k = 0; k < nw; ++k) { pre[k] = (unsigned short)(a < 65535 ? a : 65535); a += __popcll(bmp[k]); } pre[nw] = (unsigned short)(a < 65535 ? a : 65535); }
-      OC_WAVE_SYNC();
-      ngen = pre[nw];
-      if (ngen <= OC_GCAP)
-        for (int k = tid; k < nw; k += 64) {
-          unsigned long long bits = bmp[k]; int pos = pre[k];
-          while (bits) { const int b = __ffsll((long long)bits) - 1; cand[pos++] = (unsigned short)(k * 64 + b); bits &= bits - 1ull; }
-        }
-      OC_WAVE_SYNC();
-    }
-#ifdef MIQP_PROFILE
-    const long long tq1_ = clock64();
-#endif
-    bool overflow = ngen > OC_GCAP;
-    int ncoef = 0;
-    for (int c0 = 0; c0 < ngen && !overflow; c0 += OC_SCR) {
-      double* g = scr + (tid & (OC_SCR - 1)) * OC_SSTR;
-      RowOut r; r.active = false; r.rhs = 0; r.aq = 0;
-      int i = 0, nn = 0;
-      const bool mine = tid < OC_SCR && c0 + tid < ngen;
-      int slot_ = 0;
-      if (mine) { const int pcode = cand[c0 + tid]; i = pcode / NSLOT; slot_ = pcode - i * NSLOT; r = decode_row<C, true>(Y, D, T, fix, i, slot_, g); }
-      unsigned long long map = 0ull; unsigned int cols = 0u;
-      double v6[6];
-#pragma unroll
-      for (int k = 0; k < 6; ++k) v6[k] = 0.0;
-      if (mine) {
-        for (int q = 0; q < NZ; ++q) {
-          const double v = g[q];
-          if (v != 0.0 && nn < 6) {
-#pragma unroll
-            for (int k = 0; k < 6; ++k) if (k == nn) v6[k] = v;
-            const int pq = as_col<C>(oc_pcol<C, CM>(q));
-            map |= (unsigned long long)(nn + 1) << (4 * pq); cols |= (unsigned int)pq << (4 * nn); nn++;
-          }
-        }
-      }
-      const bool keep = mine && nn > 0;
-      const unsigned long long mk = __ballot(keep);
-      const unsigned long long b0 = __ballot(keep && (nn & 1)), b1 = __ballot(keep && (nn & 2)), b2 = __ballot(keep && (nn & 4));
-      const int tot = __popcll(b0) + 2 * __popcll(b1) + 4 * __popcll(b2);
-      if (ncoef + tot > OC_GCOEF) { overflow = true; break; }
-      if (keep) {
-        const int idx = sstart[N + 1] + __popcll(mk & lt);
-        const int off = ncoef + __popcll(b0 & lt) + 2 * __popcll(b1 & lt) + 4 * __popcll(b2 & lt);
-#pragma unroll
-        for (int k = 0; k < 6; ++k) if (k < nn) gcoef[off + k] = v6[k];
-        uint4 m4; m4.x = (unsigned int)map; m4.y = (unsigned int)(map >> 32);
-        m4.z = (unsigned int)off | ((unsigned int)nn << 16) | ((unsigned int)i << 20) | (r.aq > 0.0 ? 0x80000000u : 0u); m4.w = cols;
-        gmeta[idx] = m4; grhs[idx] = r.rhs;
-        cand[idx] = (unsigned short)(i * NSLOT + slot_);   // identity of the packed row (idx <= its position in the candidate list: in-place compaction)
-      }
-      OC_WAVE_SYNC();
-      if (tid == 0) sstart[N + 1] += __popcll(mk);
-      ncoef += tot;
-      OC_WAVE_SYNC();
-    }
+    // ---- decode: box rows to their (stage, side, column) key, general rows packed in (stage, slot) order, their identities in cand
+#define OC_DECODE_POLICY AsDecode<C>
+#include "oc_decode_body.inc"
+#undef OC_DECODE_POLICY
     if (overflow) {   // marked and returned unsolved: next round the larger block takes the record - or, from there, the interior point chain
       if (B.batch_A) B.batch_A[(size_t)node * 64 + tid] = 0xFFFFu;
       if (tid == 0) {
@@ -311,7 +182,7 @@ __global__ void __launch_bounds__(64, (GCAP > 128 ? 1 : 2)) as_onchip_kernel(Dev
 
     ASP_T(ta1); ASP_ACC(0, ta0, ta1);
 #ifdef MIQP_PROFILE
-    asp_[11] += (unsigned long long)(ta1 - tq1_);
+    asp_[9] += (unsigned long long)(ocd_t_sparse - ta0); asp_[11] += (unsigned long long)(ta1 - ocd_t_rows);
 #endif
     // ---- the box rows of this lane (column lc, side, stages 2 k + par) into registers
     double brhs[NSL];

@@ -18,17 +18,13 @@
 //     shifts and [A B]' T into sums over a lane's registers; the input block is eliminated by Gauss-Jordan on the four
 //     input rows of the tile (row_newbcast / permlane swaps), one MFMA forms the Schur complement and the next vector.
 // Nodes with more general rows than the on-chip capacity are queued for ipm_kernel (the general, memory-backed kernel).
+// The LDS block and the decode of a node's fix record into these rows are shared with as_onchip_kernel: oc_decode.hip (included in front of this file).
 #ifndef MIQP_PHI_BRANCH
 #define MIQP_PHI_BRANCH 1   // 1: the second group of four general rows of a stage only when the stage has more than four (a branch in the sweep)
 #endif
 namespace miqp {
 
-constexpr int OC_GCAP = 128;      // general rows kept on chip (2 register slots per lane)
 constexpr int OC_GSLOTS = OC_GCAP / 64;
-constexpr int OC_GCOEF = 432;     // their packed coefficients (with N = 20 and a 480-byte fix record the block stays within 160 KB / 8: 2 wavefronts per SIMD)
-constexpr int OC_SCR = 32;        // rows decoded per round through the dense scratch rows
-constexpr int OC_SSTR = 17;       // stride of a scratch row (conflict free)
-constexpr int OC_KL0 = 6;         // stages whose gains stay in LDS
 #ifndef MIQP_OC_PF
 #define MIQP_OC_PF 4
 #endif
@@ -38,31 +34,6 @@ constexpr int OC_PF = MIQP_OC_PF;          // prefetch distance (stages) of the 
 #endif
 constexpr int OC_GRP = MIQP_OC_GRP;         // box slots whose chains are interleaved in the row passes
 constexpr int OC_NSL = 10;        // box-row slots per lane: horizons of up to 2 * OC_NSL steps
-
-struct OcLds { int z, u, r, gmeta, gcoef, grhs, wd, sstart, cand, fix, total; };   // byte offsets
-// capacity of the larger variant of the kernel (the nodes the standard one hands on: rounding probes and the other nodes with up
-// to OC_GCAP_BIG general rows): 5 register slots per lane, one wavefront per SIMD, 4 blocks of ~34 KB per CU
-constexpr int OC_GCAP_BIG = 320;
-__host__ __device__ constexpr int oc_gcoef_of(int gcap) { return gcap == 128 ? 432 : gcap * 7 / 2; }
-// (as_std: the block of the standard active-set launch - its second region holds one stage vector and the decode scratch, its third the box keys
-// alone: 768 B less at N = 20, so that eight blocks leave 6 KB of a CU's 160 KB free instead of none - with none, the holes the larger launches'
-// 34 KB blocks leave behind kept every CU at six or seven blocks, tools/wave_dump.py)
-__host__ __device__ inline OcLds oc_lds_layout(int N, int fixlen, int OC_GCAP = miqp::OC_GCAP, bool as_std = false) {
-  const int OC_GCOEF = oc_gcoef_of(OC_GCAP);
-  OcLds L; int o = 0;
-  L.z = o; o += N * 16 * 8;
-  L.u = o; { int a = as_std ? N * 16 * 8 : N * 32 * 8, b = OC_SCR * OC_SSTR * 8; o += a > b ? a : b; }    // D | Gd  /  dZ | gains  /  decode scratch
-  L.r = o; { int a = N * 32 * 8, b = as_std ? 0 : OC_GCAP * 16 + OC_KL0 * 64 * 8; o += a > b ? a : b; }   // box right-hand side keys (decode) / (sqrt(w), f) of the general rows + gains of the first stages
-  L.gmeta = o; o += OC_GCAP * 16;
-  L.gcoef = o; o += OC_GCOEF * 8;
-  L.grhs = o; o += OC_GCAP * 8;
-  L.wd = o; o += 16 * 8;
-  L.sstart = o; o += ((N + 2) * 4 + 7) & ~7;
-  L.cand = o; o += (OC_GCAP + 64) * 2;
-  L.fix = o; o += (fixlen + 15) & ~15;
-  L.total = (o + 15) & ~15;
-  return L;
-}
 
 #ifdef MIQP_PROFILE
 #define OCP_T(var) const long long var = clock64()
@@ -75,69 +46,6 @@ __host__ __device__ inline OcLds oc_lds_layout(int N, int fixlen, int OC_GCAP = 
 #define OCP_ACC(k, t0, t1)
 #endif
 __host__ __device__ inline int oc_gain_doubles(int N) { return N * 64; }
-#define OC_WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
-
-// box row of (stage, slot), if that slot carries a row with a single coefficient +-1: column, sign, right-hand side
-// (the cases of decode_row whose row touches one stage variable)
-template <int C>
-__device__ inline bool box_of_slot(const Layout& Y, const double* D, const int* T, const signed char* fix, int i, int slot, int& col, double& sgn, double& rhs) {
-  if (slot >= C * Y.SC) return false;
-  const int N = Y.N;
-  const double* G = D + Y.d_glob;
-  const int c = slot / Y.SC, rr = slot - c * Y.SC;
-  const int code = i >= 1 ? (int)fix[Y.f_reg + c * N + i] : -1;
-  const double* rt = code >= 0 ? D + Y.d_reg + (c * Y.P + (code >> 2)) * REGSZ : nullptr;
-  if (rr < 7) {
-    const double* Hc = (rt || rr < 3) ? D : region_hull(Y, D, T, fix, c, i);   // (only read when the region is undecided)
-    switch (rr) {
-      case 0: col = 6 * c + 1; sgn = -1; rhs = -G[0]; break;
-      case 1: col = 6 * c + 4; sgn = -1; rhs = -G[0]; break;
-      case 2: col = 6 * c + 1; sgn = 1; rhs = G[1]; break;
-      case 3: col = 6 * c + 2; sgn = 1; rhs = rt ? rt[12] : Hc[1]; break;
-      case 4: col = 6 * c + 2; sgn = -1; rhs = -(rt ? rt[11] : Hc[0]); break;
-      case 5: col = 6 * c + 5; sgn = 1; rhs = rt ? rt[14] : Hc[3]; break;
-      default: col = 6 * c + 5; sgn = -1; rhs = -(rt ? rt[13] : Hc[2]); break;
-    }
-    return true;
-  }
-  if (rr < 11) {
-    const int s = (rr - 7) >> 1; const bool up = ((rr - 7) & 1) == 0;
-    double lo, hi;
-    if (i == 0) { lo = D[Y.d_u0box + c * 4 + 2 * s]; hi = D[Y.d_u0box + c * 4 + 2 * s + 1]; }
-    else if (rt) { lo = rt[15 + 2 * s]; hi = rt[16 + 2 * s]; }
-    else { const double* Hc = region_hull(Y, D, T, fix, c, i); lo = Hc[4 + 2 * s]; hi = Hc[5 + 2 * s]; }
-    col = 6 * C + 2 * c + s; sgn = up ? 1.0 : -1.0; rhs = up ? hi : -lo;
-    return true;
-  }
-  if (rr < 16) {
-    if (code < 0) return false;   // the hull rows of an undecided region are general rows
-    const int h = code & 3, k = rr - 11;
-    if (h == 3) { col = 6 * c + (k < 2 ? 1 : 4); sgn = (k & 1) ? -1.0 : 1.0; rhs = G[6]; return true; }
-    if (k == 2) {
-      const int* hs = T + Y.i_hs + ((c * Y.P + (code >> 2)) * 2 + h) * 2;
-      col = 6 * c + (hs[0] == 0 ? 1 : 4); sgn = -(double)hs[1]; rhs = -G[6];
-      return true;
-    }
-    return false;
-  }
-  int q = rr - 16;
-  const double* ed;
-  if (q < 5 * Y.EL) {
-    const int pt = q / Y.EL, k = q - pt * Y.EL;
-    if (pt != 0) return false;
-    const int e = Y.E == 1 ? 0 : (int)fix[Y.f_env + (c * N + i) * 5];
-    ed = D + Y.d_env + (e * Y.EL + k) * 3;
-  } else {
-    q -= 5 * Y.EL;
-    const int o = q / 5, pt = q - o * 5;
-    if (pt != 0) return false;
-    const int kk = (int)fix[Y.f_obs + ((c * Y.O + o) * N + i) * 5];
-    ed = D + Y.d_obs + ((o * N + i) * Y.L + kk) * 3;
-  }
-  if (ed[1] == 0.0 && fabs(ed[0]) == 1.0) { col = 6 * c; sgn = ed[0]; rhs = ed[2]; return true; }
-  if (ed[0] == 0.0 && fabs(ed[1]) == 1.0) { col = 6 * c + 3; sgn = ed[1]; rhs = ed[2]; return true; }
-  return false;
-}
 
 // Column order of the stage vector inside the on-chip kernel.  Two cars: CHAIN-MAJOR - the four triple integrator chains
 // (car, axis) side by side per derivative, column 4 k + chain for (position, velocity, acceleration) = k = 0, 1, 2 and
@@ -147,6 +55,12 @@ __device__ inline bool box_of_slot(const Layout& Y, const double* D, const int* 
 // i.e. the two products of the Riccati step need no MFMA and no LDS.  One car keeps the model's order and the MFMA form.
 template <int C, bool CM> __device__ inline int oc_pcol(int l) { return (CM && l < 6 * C) ? 2 * C * (l % 3) + l / 3 : l; }   // model column -> kernel column
 template <int C, bool CM> __device__ inline int oc_lcol(int p) { return (CM && p < 6 * C) ? 3 * (p % (2 * C)) + p / (2 * C) : p; }   // and back
+// what this kernel asks of the decode (oc_decode.hip): its own column order, every slot of the state / input bounds through the full test, the
+// general rows counted per stage (the sweep walks them stage by stage); its cycle marks (OCP_T) stand around the decode
+template <int C, bool CM> struct IpmDecode {
+  static constexpr bool LANE_BOUNDS = false, ROW_IDENTITY = false, MARKS = false;
+  static __device__ int col(int l) { return oc_pcol<C, CM>(l); }
+};
 // value of the lane CTRL columns to the left / right inside the row of 16 lanes (row_shr : 0x110 + n, row_shl : 0x100 + n), 0 outside
 template <int CTRL> __device__ inline double dpp_shift0(double x) {
   int lo = __double2loint(x), hi = __double2hiint(x);
@@ -162,37 +76,6 @@ __device__ inline int fresh_lane() {
   int l;
   asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
   return l;
-}
-
-// cheap necessary condition for slot (i, slot) to carry a row, from the fix record alone (the first tests of decode_row; no
-// table loads): the decode walks all N x NSLOT slots with this and runs the full test only on the few hundred survivors
-template <int C>
-__device__ inline bool slot_maybe(const Layout& Y, const signed char* fix, int i, int slot) {
-  const int N = Y.N;
-  if (slot < C * Y.SC) {
-    const int c = slot / Y.SC, rr = slot - c * Y.SC;
-    if (rr < 11) return true;
-    if (i < 1) return false;
-    const int code = (int)fix[Y.f_reg + c * N + i];
-    if (rr < 16) return code >= 0 ? ((code & 3) != 3 || rr - 11 <= 3) : rr - 11 <= 1;
-    int q = rr - 16;
-    if (q < 5 * Y.EL) {
-      if (Y.E < 1) return false;
-      const int pt = q / Y.EL;
-      const int e = Y.E == 1 ? 0 : (int)fix[Y.f_env + (c * N + i) * 5 + pt];
-      return e >= 0 && (pt == 0 || code >= 0);
-    }
-    q -= 5 * Y.EL;
-    const int o = q / 5, pt = q - o * 5;
-    const int kk = (int)fix[Y.f_obs + ((c * Y.O + o) * N + i) * 5 + pt];
-    return kk >= 0 && kk < Y.L && (pt == 0 || code >= 0);
-  }
-  if (C < 2 || i < 1) return false;
-  const int q = slot - C * Y.SC;
-  if (q < Y.NP * 8) { const int p = q >> 3, grp = (q & 7) >> 1; return (int)fix[Y.f_c2c + (p * N + i) * 4 + grp] >= 0; }
-  const int q2 = q - Y.NP * 8, p = q2 >> 4, grp = (q2 >> 2) & 3, alt = q2 & 3;
-  const int m = (int)fix[Y.f_c2n + (p * N + i) * 4 + grp];
-  return m > 0 && ((m >> alt) & 1);
 }
 
 // lambda + kappa and w of one row for the Newton system of the next iteration (see row_step)
@@ -242,7 +125,7 @@ __global__ void __launch_bounds__(64, (GCAP > 128 ? 1 : 2)) ipm_onchip_kernel(De
   constexpr int GS = (CM && MIQP_KL0_PACK) ? 1 : 2;          // doubles per general row in gswfs
   constexpr int KL0N = OC_KL0 + (GS == 1 ? OC_GCAP / 64 : 0);   // stages whose gains stay in LDS
   double* const KL0 = gswfs + GS * OC_GCAP;                  // [KL0N][64] gains of the first stages (computed last, used first): they stay on chip
-  uint4* const gmeta = (uint4*)(L0 + LL.gmeta);             // x,y: column map (nibble c = 1 + index of the coefficient of column c), z: coefficient offset | nn << 16 | stage << 20 | soft << 31, w: columns (4 bits each)
+  uint4* const gmeta = (uint4*)(L0 + LL.gmeta);             // the general rows as the decode packs them (oc_decode.hip)
   double* const gcoef = (double*)(L0 + LL.gcoef);
   double* const grhs = (double*)(L0 + LL.grhs);
   double* const Wd = (double*)(L0 + LL.wd);
@@ -283,8 +166,8 @@ __global__ void __launch_bounds__(64, (GCAP > 128 ? 1 : 2)) ipm_onchip_kernel(De
       for (int k = tid; k < Y.fixlen; k += 64) fix[k] = src[k];
       if (tid < 16) Wd[tid] = tid < NZ ? D[Y.d_wd + oc_lcol<C, CM>(tid)] : 0.0;
       for (int k = tid; k < N * 16; k += 64) Z[k] = 0.0;
-      for (int k = tid; k < N * 32; k += 64) bkey[k] = ~0ull;
-      for (int k = tid; k <= N + 1; k += 64) sstart[k] = 0;
+      for (int k = tid; k < N * 32; k += 64) bkey[k] = ~0ull;    // (what the decode expects on entry: no box row on any key,
+      for (int k = tid; k <= N + 1; k += 64) sstart[k] = 0;      //  no general row counted)
     }
     const bool warm = B.ws_on == 2 || (B.ws_on && B.pool_Z && (B.batch_depth[node] >> 6) >= 1 && B.batch_node[node] < B.z_cap);   // roots start cold; 2: the polish starts from the incumbent's solution
     __syncthreads();
@@ -306,11 +189,7 @@ __global__ void __launch_bounds__(64, (GCAP > 128 ? 1 : 2)) ipm_onchip_kernel(De
     }
     }
     const double* Rf = D + Y.d_ref;
-    double cutoff = 1e300;
-    {
-      const double inc0 = fmin(inc_from_key(*(volatile unsigned long long*)&B.inc_key[inst]), B.inc_ext[inst]);
-      if (B.use_cutoff && inc0 < 1e300) cutoff = inc0 - (is_probe_word(B.batch_depth[node]) ? 0.0 : B.inst_gap[inst]) * (1e-10 + fabs(inc0)) - B.inst_const[inst];   // (a heuristic leaf is cut off at the incumbent itself: as_onchip.hip)
-    }
+    const double cutoff = node_cutoff(B, inst, node);
 #ifdef MIQP_PROFILE
     unsigned long long ocp_[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #endif
@@ -319,110 +198,10 @@ __global__ void __launch_bounds__(64, (GCAP > 128 ? 1 : 2)) ipm_onchip_kernel(De
 #pragma unroll
     for (int kb = 0; kb < KB; ++kb) abr[kb] = (!CM && 4 * kb + lg < NX && lc < NZ) ? ab_entry<C>(4 * kb + lg, lc, ts) : 0.0;
 
-    // ---- decode, pass A: which (stage, slot) pairs carry a row; box rows go straight to their key, general rows are marked in a
-    // bitmap over (stage, slot).  The pairs are walked class by class (velocity / acceleration bounds, jerk bounds, region
-    // rows, rear-point edges, front-point edges, obstacles, car/car, car/car exclusions), so that the lanes of one pass take
-    // the same branch of the decoder and their table loads go out together; the bitmap restores the (stage, slot) order.
-    int ngen = 0;
-    {
-      unsigned long long* const bmp = (unsigned long long*)scr;          // [nw] one bit per (stage, slot)
-      const int nw = (N * NSLOT + 63) >> 6;
-      unsigned short* const pre = (unsigned short*)(bmp + nw);           // [nw] general rows before every word
-      for (int k = tid; k < nw; k += 64) bmp[k] = 0ull;
-      OC_WAVE_SYNC();
-      const int cls_off[8] = {0, 7, 11, 16, 16 + Y.EL, 16 + 5 * Y.EL, C * Y.SC, C * Y.SC + 8 * Y.NP};
-      const int cls_cnt[8] = {7, 4, 5, Y.EL, 4 * Y.EL, 5 * Y.O, 8 * Y.NP, 16 * Y.NP};
-      auto take = [&](int i, int slot) {   // full test of one (stage, slot); box rows to their key, general rows to the bitmap
-        if (decode_row<C, false>(Y, D, T, fix, i, slot, nullptr).active) {
-          int col; double sg, rh;
-          if (box_of_slot<C>(Y, D, T, fix, i, slot, col, sg, rh)) atomicMin(&bkey[(i * 2 + (sg < 0.0 ? 1 : 0)) * 16 + oc_pcol<C, CM>(col)], d2key(rh));
-          else { const int pcode = i * NSLOT + slot; atomicOr(&bmp[pcode >> 6], 1ull << (pcode & 63)); }
-        }
-      };
-      // the candidates of the sparse classes (everything but the state / input bounds) are collected first with the cheap test
-      unsigned short* const plist = pre + ((nw + 1 + 3) & ~3);
-      const int LCAP = (int)(((char*)(L0 + LL.r) - (char*)plist) / 2) - 64;
-      int nlist = 0;
-      auto flush = [&]() {
-        OC_WAVE_SYNC();
-        for (int j0 = 0; j0 < nlist; j0 += 64) if (j0 + tid < nlist) { const int pc = plist[j0 + tid]; const int i = pc / NSLOT; take(i, pc - i * NSLOT); }
-        OC_WAVE_SYNC();
-        nlist = 0;
-      };
-#pragma unroll 1
-      for (int cl = 0; cl < 8; ++cl) {
-        const int cnt = cls_cnt[cl], off = cls_off[cl];
-        const bool percar = cl < 6;
-        const int per = percar ? C * cnt : cnt, total = N * per;
-        for (int e0 = 0; e0 < total; e0 += 64) {
-          const int e = e0 + tid;
-          int i = 0, slot = 0; bool in = e < total;
-          if (in) { i = e / per; const int rem = e - i * per; slot = percar ? (rem / cnt) * Y.SC + off + rem % cnt : off + rem; }
-          if (cl < 2) { if (in) take(i, slot); continue; }
-          const bool cnd = in && slot_maybe<C>(Y, fix, i, slot);
-          const unsigned long long mk = __ballot(cnd);
-          if (cnd) plist[nlist + __popcll(mk & lt)] = (unsigned short)(i * NSLOT + slot);
-          nlist += __popcll(mk);
-          if (nlist > LCAP) flush();
-        }
-      }
-      flush();
-      if (tid == 0) { int a = 0; for (int k = 0; k < nw; ++k) { pre[k] = (unsigned short)(a < 65535 ? a : 65535); a += __popcll(bmp[k]); } pre[nw] = (unsigned short)(a < 65535 ? a : 65535); }
-      OC_WAVE_SYNC();
-      ngen = pre[nw];
-      if (ngen <= OC_GCAP)
-        for (int k = tid; k < nw; k += 64) {
-          unsigned long long bits = bmp[k]; int pos = pre[k];
-          while (bits) { const int b = __ffsll((long long)bits) - 1; cand[pos++] = (unsigned short)(k * 64 + b); bits &= bits - 1ull; }
-        }
-      OC_WAVE_SYNC();
-    }
-    // ---- pass B: the general rows, OC_SCR at a time through dense scratch rows; packed into LDS in (stage, slot) order
-    bool overflow = ngen > OC_GCAP;
-    int ncoef = 0;
-    for (int c0 = 0; c0 < ngen && !overflow; c0 += OC_SCR) {
-      double* g = scr + (tid & (OC_SCR - 1)) * OC_SSTR;
-      RowOut r; r.active = false; r.rhs = 0; r.aq = 0;
-      int i = 0, nn = 0;
-      const bool mine = tid < OC_SCR && c0 + tid < ngen;
-      int slot_ = 0;
-      if (mine) { const int pcode = cand[c0 + tid]; i = pcode / NSLOT; slot_ = pcode - i * NSLOT; r = decode_row<C, true>(Y, D, T, fix, i, slot_, g); }
-      unsigned long long map = 0ull; unsigned int cols = 0u;
-      double v6[6];
-#pragma unroll
-      for (int k = 0; k < 6; ++k) v6[k] = 0.0;
-      if (mine) {
-        for (int q = 0; q < NZ; ++q) {
-          const double v = g[q];
-          if (v != 0.0 && nn < 6) {
-#pragma unroll
-            for (int k = 0; k < 6; ++k) if (k == nn) v6[k] = v;
-            const int pq = oc_pcol<C, CM>(q);
-            map |= (unsigned long long)(nn + 1) << (4 * pq); cols |= (unsigned int)pq << (4 * nn); nn++;
-          }
-        }
-      }
-      const bool keep = mine && nn > 0;   // a row without coefficients constrains nothing
-      // prefix sums over the lanes: row index and coefficient offset
-      const unsigned long long mk = __ballot(keep);
-      const unsigned long long b0 = __ballot(keep && (nn & 1)), b1 = __ballot(keep && (nn & 2)), b2 = __ballot(keep && (nn & 4));
-      const int tot = __popcll(b0) + 2 * __popcll(b1) + 4 * __popcll(b2);
-      if (ncoef + tot > OC_GCOEF) { overflow = true; break; }
-      if (keep) {
-        const int idx = sstart[N + 1] + __popcll(mk & lt);   // sstart[N + 1]: rows so far (lane-uniform value read before the update below)
-        const int off = ncoef + __popcll(b0 & lt) + 2 * __popcll(b1 & lt) + 4 * __popcll(b2 & lt);
-#pragma unroll
-        for (int k = 0; k < 6; ++k) if (k < nn) gcoef[off + k] = v6[k];
-        uint4 m4; m4.x = (unsigned int)map; m4.y = (unsigned int)(map >> 32);
-        m4.z = (unsigned int)off | ((unsigned int)nn << 16) | ((unsigned int)i << 20) | (r.aq > 0.0 ? 0x80000000u : 0u); m4.w = cols;
-        gmeta[idx] = m4; grhs[idx] = r.rhs;
-        atomicAdd(&sstart[i + 1], 1);
-      }
-      OC_WAVE_SYNC();
-      if (tid == 0) sstart[N + 1] += __popcll(mk);
-      ncoef += tot;
-      OC_WAVE_SYNC();
-    }
+    // ---- decode: box rows to their (stage, side, column) key, general rows packed per stage
+#define OC_DECODE_POLICY IpmDecode<C, CM>
+#include "oc_decode_body.inc"
+#undef OC_DECODE_POLICY
     if (overflow && !BIG && B.bounce) {   // found too large here: marked and returned unsolved; the concurrent launch of the larger variant takes it next round
       if (tid == 0) { B.batch_ok[node] = 5; B.pool_big[B.batch_node[node]] |= 1; if (B.stats) { atomicAdd(&B.stats[3], 1ull); atomicAdd(&B.stats[8 + (ngen >= 512 ? 15 : ngen / 32)], 1ull); } }
       continue;

@@ -3,6 +3,8 @@
 //   select_kernel     one workgroup per instance: prune the near list against the incumbent, pick the `take` best
 //                     bounds by an 8-bit radix select (dives: deepest first), spill to / refill from the far tier of
 //                     the open list in HBM, lower bound over both tiers, termination.
+//   the decode        (oc_decode.hip, oc_decode_body.inc) of a node's fix record into keyed box rows and packed general rows, and the LDS block,
+//                     of the two on-chip node kernels: ipm_onchip_kernel and as_onchip_kernel (as_onchip.hip, the dual active-set method).
 //   ipm_onchip_kernel<C>  (ipm_onchip.hip, C <= 2, N <= 20) one 64-lane wavefront per B&B node, the whole working set in
 //                     registers and LDS: box rows keyed by (stage, column, side) in registers, general rows compacted in
 //                     LDS, Riccati recursion in the MFMA tile layout with shift-form products and Gauss-Jordan elimination.
@@ -89,8 +91,11 @@ __host__ __device__ inline int ipm_scratch_doubles(int N, int C) {
 typedef double d4_t __attribute__((ext_vector_type(4)));
 
 enum { PT_R = 0, PT_U = 1, PT_L = 2 };
-__device__ __constant__ int ENV_PT_D[5][2] = {{PT_R, PT_R}, {PT_U, PT_U}, {PT_L, PT_U}, {PT_U, PT_L}, {PT_L, PT_L}};
-__device__ __constant__ int OBS_PT_D[5][2] = {{PT_R, PT_R}, {PT_L, PT_L}, {PT_U, PT_L}, {PT_L, PT_U}, {PT_U, PT_U}};
+// the corner tables, written once: the device keeps them in constant memory, the host side of the library (miqp_gpu.hip) a copy of its own
+#define MIQP_ENV_PT {{PT_R, PT_R}, {PT_U, PT_U}, {PT_L, PT_U}, {PT_U, PT_L}, {PT_L, PT_L}}
+#define MIQP_OBS_PT {{PT_R, PT_R}, {PT_L, PT_L}, {PT_U, PT_L}, {PT_L, PT_U}, {PT_U, PT_U}}
+__device__ __constant__ int ENV_PT_D[5][2] = MIQP_ENV_PT;
+__device__ __constant__ int OBS_PT_D[5][2] = MIQP_OBS_PT;
 
 struct DevBuf {
   Layout Y;
@@ -317,6 +322,17 @@ __device__ inline int fix_stage(const Layout& Y, int k) {
   return -1;
 }
 __device__ inline bool is_probe_word(int dw) { return (dw & 63) == 63 && (dw >> 6) >= 1; }
+// Cutoff of a node relaxation (the rule of all three node kernels; the interior point kernels call this, as_onchip_kernel states it in its own order of loads): a node whose dual bound already exceeds what can still improve the incumbent by more than
+// the gap is abandoned (weak duality on the penalised QP; also catches infeasible nodes, whose penalty term is huge).  1e300: no incumbent, or no cutoff.
+// A heuristic leaf - rounding probe, neighbour of the local search - is cut off at the incumbent itself, not a gap below it: a leaf that is better by
+// less than the gap IS the next incumbent, and the local search climbs in such steps.  (It matters to the active-set kernel, which tests the cutoff
+// after every step.  The interior point never met it: it tests the cutoff only once it is nearly stationary, and a leaf started from the
+// incumbent's solution has converged by then.)
+__device__ __forceinline__ double node_cutoff(const DevBuf& B, int inst, int node) {
+  const double inc0 = fmin(inc_from_key(*(volatile unsigned long long*)&B.inc_key[inst]), B.inc_ext[inst]);
+  if (!(B.use_cutoff && inc0 < 1e300)) return 1e300;
+  return inc0 - (is_probe_word(B.batch_depth[node]) ? 0.0 : B.inst_gap[inst]) * (1e-10 + fabs(inc0)) - B.inst_const[inst];
+}
 // The nodes of a round go to one of four concurrent launches, and which one is decided ONCE, by select_kernel / lns_kernel when they write the batch
 // (batch_large: nothing a launch of the round writes - the marks on the records, the incumbents - can then change the split while the launches
 // run beside each other; a decision read live from pool_big made the iteration counts of repeated solves differ):
@@ -748,13 +764,7 @@ __global__ void __launch_bounds__(NT, (C <= 2 ? MIQP_IPM_WPE : (NT > 64 ? MIQP_W
   }
   }
   const double* Rf = D + Y.d_ref;
-  // cutoff: a node whose dual bound already exceeds what can still improve the incumbent by more than the gap is
-  // abandoned (weak duality on the penalised QP; also catches infeasible nodes, whose penalty term is huge)
-  double cutoff = 1e300;
-  {
-    const double inc0 = fmin(inc_from_key(*(volatile unsigned long long*)&B.inc_key[inst]), B.inc_ext[inst]);
-    if (B.use_cutoff && inc0 < 1e300) cutoff = inc0 - (is_probe_word(B.batch_depth[node]) ? 0.0 : B.inst_gap[inst]) * (1e-10 + fabs(inc0)) - B.inst_const[inst];   // (a heuristic leaf is cut off at the incumbent itself: as_onchip.hip)
-  }
+  const double cutoff = node_cutoff(B, inst, node);
   double tsum = 0.0;   // sum of the elastic slacks of the current iterate
   double abr[KB];  // [A B] as MFMA operand: lane (g, c) holds AB[4kb + g][c]
 #pragma unroll
@@ -1431,6 +1441,7 @@ __global__ void __launch_bounds__(NT, (C <= 2 ? MIQP_IPM_WPE : (NT > 64 ? MIQP_W
 }
 
 }  // namespace miqp
+#include "oc_decode.hip"
 #include "ipm_onchip.hip"
 #include "as_onchip.hip"
 namespace miqp {

@@ -107,9 +107,9 @@ struct miqp_solver {
   std::string err;
 };
 
-// host copies of the corner tables (kernels.hip keeps them in constant memory)
-static const int ENV_PT_H[5][2] = {{PT_R, PT_R}, {PT_U, PT_U}, {PT_L, PT_U}, {PT_U, PT_L}, {PT_L, PT_L}};
-static const int OBS_PT_H[5][2] = {{PT_R, PT_R}, {PT_L, PT_L}, {PT_U, PT_L}, {PT_L, PT_U}, {PT_U, PT_U}};
+// host copies of the corner tables (kernels.hip: the same initialisers as the device's constant memory)
+static const int ENV_PT_H[5][2] = MIQP_ENV_PT;
+static const int OBS_PT_H[5][2] = MIQP_OBS_PT;
 
 namespace {
 
