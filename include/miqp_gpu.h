@@ -185,6 +185,13 @@ int miqp_solver_last_timing(const miqp_solver_t* s, double* out6);
  * to the end of that kernel; the other three launches of the group run beside it on their own streams), out[7] = number of those launches */
 int miqp_solver_last_active_set(const miqp_solver_t* s, double* out8);
 
+/* which launch of the interior-point chain solved the node of the last miqp_solver_solve_fixed call of this handle (read back from the
+ * hand-over counters the chain keeps; a diagnostic for tests that pin each kernel): 0 = the standard on-chip kernel, 1 = its larger
+ * variant (the node has more general rows than the standard block holds), 2 = the memory-backed kernel (more than the larger block
+ * holds), 3 = the memory-backed kernel because the shape has no on-chip kernel (three or four cars, more than 20 steps);
+ * -1 = the handle's last such call did not get through its launches (refused record, no device), or there was none */
+int miqp_solver_last_fixed_route(const miqp_solver_t* s);
+
 /* 1 when instances of this shape (NrCars, N) have the dual active-set launches - one or two cars, a horizon of up to 20 steps - else 0 (their node
  * relaxations are interior point solves).  Pure host code: no device is needed or touched.  A call switches the launches off with MIQP_AS=0 */
 int miqp_gpu_has_active_set(int num_cars, int num_steps);

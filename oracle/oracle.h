@@ -76,6 +76,10 @@ int orc_solve(const oinst* I, const orc_opts* o, miqp_raw_results_c* res, miqp_s
  * used to pin the QP machinery against K3.  Returns 0 when feasible. */
 int orc_solve_fixed(const oinst* I, const miqp_raw_results_c* fixed, miqp_raw_results_c* res, double* objective,
                     int* iters);
+/* the same with the interior point's final tolerance given (orc_solve_fixed: QP_TOL_FINAL = 1e-13): how far a record's
+ * answer moves with the tolerance tells a degenerate QP from a wrong one */
+int orc_solve_fixed_tol(const oinst* I, const miqp_raw_results_c* fixed, miqp_raw_results_c* res, double* objective,
+                        int* iters, double qp_tol);
 
 /* result buffers */
 miqp_raw_results_c* orc_results_alloc(int C, int N, int R, int E, int O, int L);

@@ -1038,6 +1038,10 @@ int orc_solve(const oinst* I, const orc_opts* o, miqp_raw_results_c* res, miqp_s
 
 /* ------------------------------------------------------------------ fixed-binary QP (pins the QP machinery on K3) */
 int orc_solve_fixed(const oinst* I, const miqp_raw_results_c* f, miqp_raw_results_c* res, double* objective, int* iters) {
+  return orc_solve_fixed_tol(I, f, res, objective, iters, QP_TOL_FINAL);
+}
+
+int orc_solve_fixed_tol(const oinst* I, const miqp_raw_results_c* f, miqp_raw_results_c* res, double* objective, int* iters, double qp_tol) {
   dmodel* M = dm_new(I); int C = I->C, N = I->N, R = I->R, E = I->E, O = I->O, L = I->L, K = I->K;
   rowvec rows = {0, 0, 0};
   signed char* comp = (signed char*)malloc(M->fixlen); memset(comp, -1, M->fixlen);
@@ -1087,8 +1091,9 @@ int orc_solve_fixed(const oinst* I, const miqp_raw_results_c* f, miqp_raw_result
           }
     }
   }
-  qpres q; qp_solve_tol(M, rows.r, rows.n, &q, QP_TOL_FINAL);
-  if (objective) *objective = q.obj;
+  qpres q; qp_solve_tol(M, rows.r, rows.n, &q, qp_tol);
+  double cobj0 = 0; (void)step0_check(M, &cobj0); /* the constant cost of step 0 (car/car slack of the initial state), as orc_solve and the device report it */
+  if (objective) *objective = q.obj + cobj0;
   if (iters) *iters = q.it;
   int rc = (q.ok && q.viol <= FEAS_TOL) ? 0 : 1;
   if (res && rc == 0) {

@@ -95,6 +95,7 @@ struct miqp_solver {
   Layout lay{};
   double timing[6] = {0, 0, 0, 0, 0, 0};
   double as_timing[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // active-set launches of the last call (miqp_solver_last_active_set)
+  int fixed_route = -1;   // which launch of the serial chain solved the last miqp_solver_solve_fixed node (miqp_solver_last_fixed_route); -1: no such call yet
   double setup[3] = {0, 0, 0};   // host set-up of the last call: seconds, of which the device context, 1 when the context was (re)built
   double admit_s = 0.0;          // when the last batch / stream call admitted this instance, in seconds after the first round of that call started
   // MIP starts (each tried as an additional root: binaries fixed, QP solved, accepted as incumbent when feasible).
@@ -1941,6 +1942,8 @@ int miqp_solver_last_active_set(const miqp_solver_t* s, double* out8) {
   return 0;
 }
 
+int miqp_solver_last_fixed_route(const miqp_solver_t* s) { return s ? s->fixed_route : -1; }
+
 int miqp_gpu_has_active_set(int num_cars, int num_steps) { return miqp::as_shape_ok(num_cars, num_steps) ? 1 : 0; }
 
 int miqp_solver_last_setup(const miqp_solver_t* s, double* out3) {
@@ -2120,6 +2123,7 @@ int miqp_solver_read_mst(miqp_solver_t* s, const char* path) {
 }
 
 int miqp_solver_solve_fixed(miqp_solver_t* s, const miqp_raw_results_c* fixed, miqp_raw_results_c* out, double* objective, int* iterations) {
+  if (s) s->fixed_route = -1;   // (a call that returns before its launches leaves no route of an earlier one behind)
   if (!s || !s->has_inst || !fixed) return -1;
   miqp_solver_t* one[1] = {s};
   BatchShape bs = batch_layout(one, 1);
@@ -2153,7 +2157,14 @@ int miqp_solver_solve_fixed(miqp_solver_t* s, const miqp_raw_results_c* fixed, m
   (void)hipMemcpyAsync(&viol, B.batch_viol, 8, hipMemcpyDeviceToHost, st);
   (void)hipMemcpyAsync(&ok, B.batch_ok, 4, hipMemcpyDeviceToHost, st);
   (void)hipMemcpyAsync(&it, B.batch_it, 4, hipMemcpyDeviceToHost, st);
+  // the hand-over counters of the serial chain say which of its launches solved the node (with one node in the batch each is 0 or 1)
+  int ovf = 0, ovf2 = 0;
+  if (X.oc_grid > 0) {
+    (void)hipMemcpyAsync(&ovf, B.ovf_count, 4, hipMemcpyDeviceToHost, st);
+    if (X.ocb_grid > 0) (void)hipMemcpyAsync(&ovf2, B.ovf2_count, 4, hipMemcpyDeviceToHost, st);
+  }
   if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) return -3;
+  s->fixed_route = X.oc_grid <= 0 ? 3 : ovf == 0 ? 0 : (X.ocb_grid > 0 && ovf2 == 0) ? 1 : 2;
   HostGeo G{s->inst, Y, D.data(), T.data()}; double cobj = 0; (void)step0_check(G, cobj);
   if (objective) *objective = obj + cobj;
   if (iterations) *iterations = it;

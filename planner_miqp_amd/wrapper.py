@@ -84,6 +84,7 @@ def load_library():
     L.miqp_solver_last_timing.restype = C.c_int; L.miqp_solver_last_timing.argtypes = [vp, C.POINTER(C.c_double)]
     L.miqp_solver_last_setup.restype = C.c_int; L.miqp_solver_last_setup.argtypes = [vp, C.POINTER(C.c_double)]
     L.miqp_solver_last_active_set.restype = C.c_int; L.miqp_solver_last_active_set.argtypes = [vp, C.POINTER(C.c_double)]
+    L.miqp_solver_last_fixed_route.restype = C.c_int; L.miqp_solver_last_fixed_route.argtypes = [vp]
     L.miqp_solver_last_error.restype = C.c_char_p; L.miqp_solver_last_error.argtypes = [vp]
     L.miqp_solver_last_admission.restype = C.c_int; L.miqp_solver_last_admission.argtypes = [vp, C.POINTER(C.c_double)]
     L.miqp_solver_certify.restype = C.c_int; L.miqp_solver_certify.argtypes = [vp, C.POINTER(RawResultsC), C.POINTER(CertificateC)]
@@ -109,7 +110,7 @@ EXPORTED_SYMBOLS = ["miqp_solver_create", "miqp_solver_destroy", "miqp_solver_se
                     "miqp_comm_init", "miqp_comm_finalize", "miqp_comm_selftest", "miqp_solver_solve_stream", "miqp_solver_materialize_results",
                     "miqp_initial_pose_check", "miqp_select_environment", "miqp_obstacle_intersects_environment", "miqp_obstacles_roi", "miqp_bark_trajectory", "miqp_obstacle_intersects_environment_roi", "miqp_environment_warmstart",
                     "miqp_solver_certify", "miqp_solver_certify_batch", "miqp_gpu_certificate_size", "miqp_gpu_certify_last_timing",
-                    "miqp_gpu_has_active_set"]
+                    "miqp_gpu_has_active_set", "miqp_solver_last_fixed_route"]
 
 
 def has_active_set(cars, steps):
@@ -374,6 +375,11 @@ class CplexWrapper:
         it = C.c_int(0)
         rc = self._L.miqp_solver_solve_fixed(self._h, C.byref(fc), C.byref(oc), C.byref(obj), C.byref(it))
         return rc, out, obj.value, it.value
+
+    def lastFixedRoute(self):
+        """which launch solved the node of the last solveFixed(): 0 the standard on-chip kernel, 1 its larger variant, 2 the
+        memory-backed kernel behind them, 3 the memory-backed kernel of a shape without an on-chip kernel; -1 before any"""
+        return int(self._L.miqp_solver_last_fixed_route(self._h))
 
     def liftTables(self):
         """response tables of the bound lifting, array [car][axis][step][4][4] (diagnostic, no device needed)"""

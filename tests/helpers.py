@@ -42,3 +42,213 @@ def k3_results():
     for n in ["slackvarsObstacle", "slackvarsObstacle_front"]:
         getattr(r, n)[...] = 0
     return r, g
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# node records: partial fix records of one instance, for the tests that compare the device's solveFixed with the oracle's
+# solve_fixed node by node (test_node_records_cpu.py, test_node_qp_gpu.py)
+ENV_FIELDS = ["notWithinEnvironmentRear", "notWithinEnvironmentFrontUbUb", "notWithinEnvironmentFrontLbUb",
+              "notWithinEnvironmentFrontUbLb", "notWithinEnvironmentFrontLbLb"]   # point 0 (rear) and front points 1..4, the order of deltacc_front's last axis
+# name: (synthetic.generate config, seed, tweak_instance arguments).  The tweaks put the obstacle, the other cars and the border of the environment pieces
+# where the leaf rows of these short horizons BIND: on every shape with leaf disjunctions the complete record costs more than its regions alone, and
+# every row class binds on its own on some shape (test_node_records_cpu.py asserts both) - a row that stays slack would pass with a wrong sign.  On
+# two and three steps the initial state pins the positions to centimetres, hence the obstacle distances given to a millimetre.
+# One car: the short horizons (N = 2: stage 0 has no state rows and stage N - 1 no input rows) on the 16- and 32-region tables with and without an
+# obstacle, a hexagon (four edges that are general rows and two that are box rows; a rectangle's are all box rows) and the 64-region tables; N = 21
+# and 40 are beyond the on-chip kernels (2 * OC_NSL = 20).  Two cars: car/car rows, two environment pieces of which the second is narrower, a
+# pentagon; "c2n20*" are cfg4's shape, the only one with enough rows to cross both on-chip capacities.  Three and four cars: the wide memory-backed kernel.
+# Seeds: the oracle's own answer on every level of a shape moves by less than 1e-5 in the states between QP_TOL_FINAL and a tolerance 100 times looser
+# (test_node_records_cpu.py asserts it).  Replaced as degenerate by that rule, with the largest spread over their levels: cfg4 seeds 1000 (1.9e-4),
+# 1001 (2.4e-4), 1002 (1.1e-4), 0 (4e-5), 1012 (2e-4); (1, 40, 32, 1, 0) seeds 0 (7.3e-5), 1 (3.2e-5) - a 40-step horizon without an obstacle;
+# mini3 seed 0 with spacing 4 (1e-4); mini4 seed 0 with spacing 3 (3e-4) and 5 (7e-5).
+NODE_SHAPES = {
+    "c1n2r16": ((1, 2, 16, 1, 0), 0, {}), "c1n2r32o": ((1, 2, 32, 1, 1), 0, {"ahead": 7.5687}), "c1n3r16o": ((1, 3, 16, 1, 1), 1, {"ahead": 9.5871}), "c1n3r32": ((1, 3, 32, 1, 0), 1, {}),
+    "c1n6r16hex": ((1, 6, 16, 1, 1, 6), 2, {"ahead": 11.75}), "c1n6r32o": ((1, 6, 32, 1, 1), 1, {"ahead": 14.0}), "c1n6r64o": ((1, 6, 64, 1, 1), 0, {"ahead": 12.0}), "mini1": ("mini1", 0, {"ahead": 14.0}),
+    "c1n21o": ((1, 21, 32, 1, 1), 3, {}), "c1n40o": ((1, 40, 32, 1, 1), 1, {}),
+    "c2n3": ((2, 3, 32, 1, 0), 0, {"spacing": 5.0}), "mini": ("mini", 0, {"spacing": 5.0}),
+    "c2n6e2pent": ((2, 6, 32, 2, 1, 5), 0, {"ahead": 10.0, "spacing": 6.0, "shift": 66.0, "piece1_top": 0.5}),
+    "c2n20a": ("cfg4", 10, {}), "c2n20b": ("cfg4", 4, {}), "c2n20c": ("cfg4", 1013, {}),
+    "mini3": ("mini3", 1, {"spacing": 6.0}), "mini4": ("mini4", 0, {"spacing": 4.0}),
+}
+# the shape on which each class of leaf rows binds on its own: with only that class decided the oracle's objective lies above the regions-only one
+CLASS_BINDS_ON = {"env_front": ["c2n6e2pent"], "obs_rear": ["c1n6r16hex", "c1n21o", "c2n20a"], "obs_front": ["c1n2r32o", "c1n6r16hex", "c2n6e2pent", "c2n20b"],
+                  "c2c": ["c2n6e2pent", "c2n20a"]}
+RELAX_SEED = {name: 113 for name in NODE_SHAPES}   # seed of numpy.random.default_rng for the shape's relax levels (cfg4 seed 4 with 114: 1.7e-5 on 'third', replaced)
+
+
+def copy_record(r):
+    from planner_miqp_amd.ctypes_types import _RES_D, _RES_I
+    out = RawResults(*r.dims)
+    for n in list(_RES_D) + list(_RES_I) + ["slackvars_real"]:
+        getattr(out, n)[...] = getattr(r, n)
+    return out
+
+
+def _c2c_view(r):
+    a = r.car2car_collision
+    return a.reshape(a.shape[:3] + (4, 4))   # [car, other car - 1, step, group, alternative] (a view: the array is contiguous)
+
+
+def _first_zero_only(a, axis):
+    z = a == 0
+    a[z & (np.cumsum(z, axis=axis) > 1)] = 1
+
+
+def canonical_record(r):
+    """A copy of a complete record with exactly one 0 per leaf disjunction: the first.  Delivered records carry a 0 on EVERY satisfied side; the
+    oracle's solve_fixed enforces every 0 and the device's fix_from_results takes the first, so only on such a record do the two solve one QP."""
+    out = copy_record(r)
+    for n in ENV_FIELDS:
+        _first_zero_only(getattr(out, n), 1)        # [car, piece, step]
+    _first_zero_only(out.deltacc, 3)                # [car, obstacle, step, edge]
+    _first_zero_only(out.deltacc_front, 3)          # [car, obstacle, step, edge, front point]
+    _first_zero_only(_c2c_view(out), 4)
+    return out
+
+
+def leaf_disjunctions(r):
+    """(class, key) of every decided leaf disjunction of a canonical record at the steps >= 1 (step 0 is constant and carries no rows)"""
+    C_, N, R, E, O, L = r.dims
+    out = []
+    for c in range(C_):
+        for i in range(1, N):
+            if E > 1:   # (one piece: see relax)
+                out += [("env_rear" if pt == 0 else "env_front", (pt, c, i)) for pt in range(5) if (getattr(r, ENV_FIELDS[pt])[c, :, i] == 0).any()]
+            for o in range(O):
+                if (r.deltacc[c, o, i] == 0).any():
+                    out.append(("obs_rear", (c, o, i)))
+                out += [("obs_front", (c, o, i, pt)) for pt in range(4) if (r.deltacc_front[c, o, i, :, pt] == 0).any()]
+    v = _c2c_view(r)
+    for c1 in range(C_):
+        for c2 in range(c1 + 1, C_):
+            out += [("c2c", (c1, c2 - 1, i, g)) for i in range(1, N) for g in range(4) if (v[c1, c2 - 1, i, g] == 0).any()]
+    return out
+
+
+def set_leaf(r, cls, key, alt=None):
+    """in place: disjunction (cls, key) undecided (every binary 1), or decided for alternative ``alt`` alone"""
+    if cls.startswith("env"):
+        a = getattr(r, ENV_FIELDS[key[0]])[key[1], :, key[2]]
+    elif cls == "obs_rear":
+        a = r.deltacc[key]
+    elif cls == "obs_front":
+        a = r.deltacc_front[key[0], key[1], key[2], :, key[3]]
+    else:
+        a = _c2c_view(r)[key]
+    a[...] = 1
+    if alt is not None:
+        a[alt] = 0
+
+
+def relax(r, disjunctions):
+    """A copy of a canonical record with the given leaf disjunctions undecided.  Regions always stay decided (the oracle's solve_fixed refuses a
+    record without them, and the front-point rows need the region).  An environment of ONE piece is never relaxed: the device - and the oracle's own
+    node_rows - keep the rows of a single piece on whatever the record says, while orc_solve_fixed builds rows only for binaries that are 0 and
+    would drop them.  That difference lies in the reference path, not in the kernels; leaf_disjunctions does not list those disjunctions."""
+    out = copy_record(r)
+    for cls, key in disjunctions:
+        assert not (cls.startswith("env") and r.dims[3] == 1)
+        set_leaf(out, cls, key)
+    return out
+
+
+def shape_dims(name):
+    """(cars, steps, regions, pieces, obstacles, edges) of NODE_SHAPES[name], without generating it"""
+    from planner_miqp_amd import synthetic
+    cfg = NODE_SHAPES[name][0]
+    cfg = synthetic.CONFIGS[cfg] if isinstance(cfg, str) else tuple(cfg)
+    return tuple(cfg[:5]) + ((cfg[5] if len(cfg) > 5 else 4) if cfg[4] > 0 else 0,)
+
+
+def level_names(dims):
+    """relax levels of a shape: complete, a seeded third and two thirds of the leaf disjunctions undecided, regions only, and - where the shape
+    has more than one class of leaf rows - one level per class in which only that class stays decided (a failure there names the class)"""
+    C_, N, R, E, O, L = dims
+    classes = (["env_front"] if E > 1 else []) + (["obs_rear", "obs_front"] if O > 0 else []) + (["c2c"] if C_ > 1 else [])
+    if not classes:
+        return ["complete"]
+    return ["complete", "third", "two_thirds", "regions_only"] + (["only_" + c for c in classes] if len(classes) > 1 else [])
+
+
+def relax_levels(r, seed):
+    """{level name: (record, number of decided leaf disjunctions)} of a canonical record, for level_names(r.dims)"""
+    D = leaf_disjunctions(r)
+    order = np.random.default_rng(seed).permutation(len(D))
+    out = {}
+    for name in level_names(r.dims):
+        if name == "complete":
+            drop = []
+        elif name == "third":
+            drop = [D[k] for k in order[:(len(D) + 2) // 3]]
+        elif name == "two_thirds":
+            drop = [D[k] for k in order[:(2 * len(D) + 2) // 3]]
+        elif name == "regions_only":
+            drop = D
+        else:
+            drop = [d for d in D if d[0] != name[5:]]
+        out[name] = (relax(r, drop), len(D) - len(drop))
+    return out
+
+
+# Infeasible nodes: (shape, class, key, alternative) - the canonical complete record with that one disjunction of step 1, where the initial state pins the
+# position, decided for another side than the chosen one.  Each is infeasible for the oracle (test_node_records_cpu.py).
+INFEASIBLE_NODES = [
+    ("c1n6r32o", "obs_rear", (0, 0, 1), 1), ("c1n6r32o", "obs_rear", (0, 0, 1), 0), ("c1n6r32o", "obs_front", (0, 0, 1, 2), 0),
+    ("mini", "c2c", (0, 0, 1, 0), 1), ("mini", "c2c", (0, 0, 1, 1), 1), ("mini", "c2c", (0, 0, 1, 2), 3), ("mini", "c2c", (0, 0, 1, 3), 0),
+    ("c2n20a", "obs_rear", (0, 0, 1), 0), ("c2n20a", "obs_rear", (1, 1, 1), 1), ("c2n20a", "obs_front", (1, 0, 1, 1), 1),
+    ("c2n20a", "c2c", (0, 0, 1, 0), 1), ("c2n20a", "c2c", (0, 0, 1, 2), 0),
+]
+
+
+def infeasible_record(r, cls, key, alt):
+    out = copy_record(r)
+    set_leaf(out, cls, key, alt)
+    return out
+
+
+_INCUMBENTS = {}
+NODE_LIMIT = 800   # nodes of the oracle's dive for the incumbent; nothing else ends it (no time limit), so the record is the same on every machine
+
+
+def tweak_instance(p, ahead=None, spacing=None, shift=None, piece1_top=None):
+    """in place, what synthetic.generate cannot be asked for - so that the leaf rows of a short horizon BIND:
+    ahead: obstacle 0 is moved into the first car's lane, its centre that far ahead of the car (the generator puts it 20 to 80 m ahead);
+    spacing: car c starts c * spacing ahead of car 0 instead of 8 m apart (the car/car rows);
+    shift: cars, references and obstacles are moved that far along the road, towards the border of the two environment pieces (65 to 75 m);
+    piece1_top: the second environment piece reaches only up to this y (the first car has to have left its lane when it leaves the first piece)"""
+    x0 = np.array(p.IntitialState, float)
+    xr = np.array(p.x_ref, float)
+    if spacing is not None:
+        for c in range(1, p.NumCars):
+            d = x0[0, 0] + c * spacing - x0[c, 0]
+            x0[c, 0] += d; xr[c] += d
+    if shift is not None:
+        x0[:, 0] += shift; xr += shift
+        p.ObstacleConvexPolygon = [[q + np.array([shift, 0.0]) for q in poly] for poly in p.ObstacleConvexPolygon]
+    p.IntitialState, p.x_ref = x0, xr
+    if ahead is not None:
+        poly = p.ObstacleConvexPolygon[0]
+        d = np.array([x0[0, 0] + ahead, x0[0, 3]]) - poly[0].mean(0)
+        p.ObstacleConvexPolygon[0] = [q + d for q in poly]
+    if piece1_top is not None:
+        e = np.array(p.MultiEnvironmentConvexPolygon[1], float)
+        e[e[:, 1] > piece1_top, 1] = piece1_top
+        p.MultiEnvironmentConvexPolygon[1] = e
+
+
+def node_instance(oracle, name):
+    """(parameters, oracle handle, dims, canonical complete record) of NODE_SHAPES[name]: a feasible record from a short oracle solve - the first
+    incumbents of its dive (loose gap, ended by NODE_LIMIT nodes and by no clock: the same record on every machine, which the expected-route
+    table of test_node_qp_gpu.py relies on), not an optimum - canonicalised.  Kept for the session."""
+    if name not in _INCUMBENTS:
+        from planner_miqp_amd import synthetic
+        cfg, seed, tweaks = NODE_SHAPES[name]
+        p = synthetic.generate(cfg, seed, gap=1e-7, max_time=30)
+        tweak_instance(p, **tweaks)
+        h = oracle.from_params(p, 10)
+        dims = oracle.dims(p)
+        st, res, props = oracle.solve(h, dims, gap=0.5, time_limit=1e9, max_nodes=NODE_LIMIT)
+        assert st == 0, (name, st)
+        _INCUMBENTS[name] = (p, h, dims, canonical_record(res))
+    return _INCUMBENTS[name]
+

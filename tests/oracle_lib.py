@@ -28,6 +28,8 @@ class Oracle:
         L.orc_solve.argtypes = [vp, C.POINTER(OrcOpts), C.POINTER(RawResultsC), C.POINTER(SolutionPropertiesC)]
         L.orc_solve_fixed.restype = C.c_int
         L.orc_solve_fixed.argtypes = [vp, C.POINTER(RawResultsC), C.POINTER(RawResultsC), C.POINTER(C.c_double), C.POINTER(C.c_int)]
+        L.orc_solve_fixed_tol.restype = C.c_int
+        L.orc_solve_fixed_tol.argtypes = L.orc_solve_fixed.argtypes + [C.c_double]
         self.L = L
 
     # ---- instances
@@ -72,11 +74,15 @@ class Oracle:
         st = self.L.orc_solve(h, C.byref(o), C.byref(rc), C.byref(p))
         return st, res, p
 
-    def solve_fixed(self, h, dims, fixed: RawResults):
+    def solve_fixed(self, h, dims, fixed: RawResults, qp_tol=None):
+        """qp_tol None: the oracle's final tolerance (QP_TOL_FINAL)"""
         res = RawResults(*dims)
         rc = res.to_c()
         fc = fixed.to_c()
         obj = C.c_double(0)
         it = C.c_int(0)
-        st = self.L.orc_solve_fixed(h, C.byref(fc), C.byref(rc), C.byref(obj), C.byref(it))
+        if qp_tol is None:
+            st = self.L.orc_solve_fixed(h, C.byref(fc), C.byref(rc), C.byref(obj), C.byref(it))
+        else:
+            st = self.L.orc_solve_fixed_tol(h, C.byref(fc), C.byref(rc), C.byref(obj), C.byref(it), float(qp_tol))
         return st, res, obj.value, it.value
