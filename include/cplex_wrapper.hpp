@@ -159,6 +159,32 @@ class CplexWrapper {
     if (miqp_solver_certify(h_, &p.c, &c) != 0) c.status = -1;
     return c;
   }
+  // The continuous QPs of many records of the loaded instance in one device call (miqp_solver_solve_fixed_batch; no reference counterpart - the
+  // reference walks its alternative start configurations one cplex.solve() after the other, src/miqp_planner.cpp:694-749).  The instance is the
+  // one of the last callCplex.  One result per record (status 0 feasible, 1 infeasible, 2 refused / not run); `best` receives the feasible entry
+  // with the lowest objective, -1 when there is none.  Returns the library's code (0; -3: no device).
+  int solveFixedBatch(const std::vector<std::shared_ptr<RawResults>>& records, std::vector<miqp_fixed_result_c>& results, int* best = nullptr) {
+    results.assign(records.size(), miqp_fixed_result_c{2, -1, 0, 0, std::nan(""), std::nan("")});
+    if (best) *best = -1;
+    if (!h_ || records.empty()) return -1;
+    std::vector<std::unique_ptr<Pod>> pods; std::vector<const miqp_raw_results_c*> ptrs;
+    for (const auto& r : records) {
+      if (!r || r->N <= 0 || r->NrCars <= 0) { ptrs.push_back(nullptr); continue; }
+      pods.emplace_back(new Pod(r->NrCars, r->N, r->NrRegions, r->NrEnvironments, r->NrObstacles, r->MaxLinesObstacles));
+      fillPod(*r, *pods.back()); ptrs.push_back(&pods.back()->c);
+    }
+    return miqp_solver_solve_fixed_batch(h_, ptrs.data(), (int)ptrs.size(), results.data(), best);
+  }
+  // ... and the record of entry k of that call, as callCplex delivers a solution's; null when the entry was not feasible or there is no such entry
+  std::shared_ptr<RawResults> fixedBatchRecord(int k) {
+    int d[6];
+    if (!h_ || miqp_solver_get_dims(h_, d) != 0) return nullptr;
+    Pod p(d[0], d[1], d[2], d[3], d[4], d[5]);
+    if (miqp_solver_fixed_batch_record(h_, k, &p.c) != 0) return nullptr;
+    auto out = std::make_shared<RawResults>();
+    unpackPod(p, *out);
+    return out;
+  }
   SolutionProperties getSolutionProperties() const { return solutionProperties_; }
   void setDebugOutputPrint(bool v) { print_debug_outputs_ = v; }
   void setDebugOutputFilePath(std::string in) { debugOutputFilePath_ = in; }
@@ -253,10 +279,12 @@ class CplexWrapper {
   }
   void pullResults() {
     int dm[6]; miqp_solver_get_dims(h_, dm);
-    const int C = dm[0], N = dm[1], R = dm[2], E = dm[3], O = dm[4], L = dm[5], K = C - 1;
-    Pod p(C, N, R, E, O, L);
+    Pod p(dm[0], dm[1], dm[2], dm[3], dm[4], dm[5]);
     miqp_solver_get_results(h_, &p.c);
-    RawResults& r = *rawResults_;
+    unpackPod(p, *rawResults_);
+  }
+  static void unpackPod(const Pod& p, RawResults& r) {
+    const int C = p.c.NrCars, N = p.c.N, R = p.c.NrRegions, E = p.c.NrEnvironments, O = p.c.NrObstacles, L = p.c.MaxLinesObstacles, K = C - 1;
     r.N = N; r.NrEnvironments = E; r.NrRegions = R; r.NrObstacles = O; r.MaxLinesObstacles = L; r.NrCarToCarCollisions = K; r.NrCars = C;
     Eigen::Tensor<double, 2>* d2[12] = {&r.u_x, &r.u_y, &r.pos_x, &r.vel_x, &r.acc_x, &r.pos_y, &r.vel_y, &r.acc_y, &r.pos_x_front_UB, &r.pos_x_front_LB, &r.pos_y_front_UB, &r.pos_y_front_LB};
     for (int k = 0; k < 12; ++k) toTensor<double, 2>(p.d[k].data(), *d2[k], {C, N});

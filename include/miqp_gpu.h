@@ -192,6 +192,32 @@ int miqp_solver_last_active_set(const miqp_solver_t* s, double* out8);
  * -1 = the handle's last such call did not get through its launches (refused record, no device), or there was none */
 int miqp_solver_last_fixed_route(const miqp_solver_t* s);
 
+/* n fix records of the instance loaded in s, solved as nodes of common launches: what miqp_solver_solve_fixed answers for one record, for
+ * many in one device call - one compilation of the instance, one upload of its tables, one device lock.  No reference counterpart: the
+ * reference walks its alternative start configurations one after the other, a cplex.solve() each (src/miqp_planner.cpp:694-749).
+ * The entries go through the serial interior point chain of the single call in launch groups of miqp_gpu_fixed_batch_chunk nodes, with its
+ * settings, and every entry is answered bit for bit as the single call answers it alone, whatever its place and its neighbours.
+ * out[n] receives one result each.  *best (may be NULL) = index of the feasible entry with the lowest objective, ties to the lower index,
+ * -1 when none is feasible.  n is at most 65536.
+ * Returns 0, -1 invalid arguments / no instance (n <= 0, NULL arrays), -2 shape refused (as the solve refuses it),
+ * -3 no device / kernel image / HIP error (every entry then has status 2: not run), -5 n above 65536.
+ * A refused ENTRY - NULL record, NULL array in it, sizes that differ from the instance - is status 2 of that entry and does not fail the call.
+ * The handle keeps the trajectories and fix records of the call for miqp_solver_fixed_batch_record until its next such call or its next
+ * parameters.  Needs a device context of its own sizes: it rebuilds the one a solve or a single call left, and they rebuild theirs after it.
+ * miqp_solver_last_timing then reports out[0] = the whole call, out[1] = of which on the device (first launch group to last kernel),
+ * out[2] = launch groups, out[3] = entries run, out[4] = their iterations. */
+int miqp_solver_solve_fixed_batch(miqp_solver_t* s, const miqp_raw_results_c* const* fixed, int n, miqp_fixed_result_c* out, int* best);
+
+/* the RawResults record of entry k of the handle's last miqp_solver_solve_fixed_batch call (no reference counterpart): built from the kept
+ * trajectory and fix record with the canonical completion of the binaries, as the single call builds its `out`.
+ * 0, 1 when entry k was not feasible (or refused), -1 bad k / no batch held, -2 sizes of out differ from the instance. */
+int miqp_solver_fixed_batch_record(miqp_solver_t* s, int k, miqp_raw_results_c* out);
+
+/* sizeof(miqp_fixed_result_c) of the built library (binding check; no reference counterpart) */
+int miqp_gpu_fixed_result_size(void);
+/* nodes per launch group of miqp_solver_solve_fixed_batch: a constant of the build (no reference counterpart; no device is needed or touched) */
+int miqp_gpu_fixed_batch_chunk(void);
+
 /* 1 when instances of this shape (NrCars, N) have the dual active-set launches - one or two cars, a horizon of up to 20 steps - else 0 (their node
  * relaxations are interior point solves).  Pure host code: no device is needed or touched.  A call switches the launches off with MIQP_AS=0 */
 int miqp_gpu_has_active_set(int num_cars, int num_steps);

@@ -153,6 +153,17 @@ typedef struct miqp_certificate_c {
   int    status;               /* 0 evaluated; 1 the handle holds no solution (doubles NaN, ints -1) */
 } miqp_certificate_c;
 
+/* Outcome of one entry of miqp_solver_solve_fixed_batch: the continuous QP under the integer decisions of one record. */
+typedef struct miqp_fixed_result_c {
+  int status;       /* 0 feasible, 1 infeasible (as miqp_solver_solve_fixed returns 1), 2 entry refused - NULL record, NULL array in it,
+                       sizes that differ from the instance - or not run (the call failed before its launches) */
+  int route;        /* as miqp_solver_last_fixed_route for that node: 0..3; -1 for a refused entry */
+  int iterations;   /* interior point iterations of the node */
+  int reserved;     /* 0 */
+  double objective; /* with the constant cost of step 0, as the single call reports it; NaN for status 2 */
+  double violation; /* worst elastic violation of the node's rows at its solution (feasible: <= 1e-6); NaN for status 2 */
+} miqp_fixed_result_c;
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,7 @@ host-side mirror of the reference's operator interface for that path (CplexWrapp
 RawResults, SolutionProperties) over that C ABI.  There is no CPU fallback: importing works anywhere,
 solving requires the built library and a HIP device.
 """
-from .ctypes_types import ModelParameters, RawResults, Certificate, CertificateC  # noqa: F401
+from .ctypes_types import ModelParameters, RawResults, Certificate, CertificateC, FixedResultC  # noqa: F401
 from .wrapper import (CplexWrapper, OptimizationStatus, SolutionProperties, WarmstartType, ParameterSource,  # noqa: F401
                       solve_batch, prepare_batch, materialize_results, certify_batch, certify_last_timing, load_library, library_path, build_library,
-                      has_active_set)
+                      has_active_set, fixed_batch_chunk)

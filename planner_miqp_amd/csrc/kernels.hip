@@ -1165,7 +1165,14 @@ __global__ void __launch_bounds__(NT, (C <= 2 ? MIQP_IPM_WPE : (NT > 64 ? MIQP_W
       lds_barrier();
       PROF_T(tw1); PROF_ACC(3, tw0, tw1);
       const int nmj = sstart[j + 1] - sstart[j], nsj = sst[j + 1] - sst[j];
-      for (int r0 = tid; r0 < nmj + nsj; r0 += NT) {
+      // The rows add into S and the gradient with LDS atomics.  Within a wavefront their order is the lane order; between the wavefronts of the
+      // workgroup it would be whichever reaches the instruction first - the last bits of a node with more than 64 rows in a stage then depended on
+      // what else ran on the device (a batch of such nodes against the node alone).  So the runs of 64 rows take their turns: row r0 stays with
+      // thread r0 % NT as before, a barrier separates one wavefront's run from the next one's, and a stage of up to 64 rows pays nothing.
+      for (int c0 = 0; c0 < nmj + nsj; c0 += 64) {
+        if (c0 > 0) lds_barrier();
+        const int r0 = c0 + (tid & 63);
+        if (((c0 >> 6) % (NT / 64)) != (tid >> 6) || r0 >= nmj + nsj) continue;
         const bool sgl = r0 >= nmj;
         const int r = sgl ? Y.ROWCAP - 1 - (sst[j] + r0 - nmj) : sstart[j] + r0;
         RowRegs R = pre;

@@ -105,6 +105,11 @@ struct miqp_solver {
   // result record of the last solve, built by miqp_solver_materialize_results (host threads, inside a batch call's timing) and
   // handed out by miqp_solver_get_results; dropped whenever the solution or the instance changes
   std::unique_ptr<OwnedResults> rescache;
+  // what the last miqp_solver_solve_fixed_batch call of the handle left for miqp_solver_fixed_batch_record (fixed_batch.hip): the trajectories and fix
+  // records of its accepted entries, and for each of its fb_n entries where its pair lies (-1: refused or infeasible); dropped by the next such
+  // call and whenever the instance changes
+  int fb_n = 0; std::vector<int> fb_slot; std::vector<double> fb_Z; std::vector<signed char> fb_fix;
+  void drop_fixed_batch() { fb_n = 0; std::vector<int>().swap(fb_slot); std::vector<double>().swap(fb_Z); std::vector<signed char>().swap(fb_fix); }
   std::string err;
 };
 
@@ -1628,6 +1633,7 @@ bool solve_batch_impl(miqp_solver_t* const* S, int n, int* statuses, const Split
 }  // namespace
 
 #include "certify.hip"
+#include "fixed_batch.hip"
 
 // ================================================================================================
 //  C ABI
@@ -1648,7 +1654,7 @@ void miqp_solver_destroy(miqp_solver_t* s) { delete s; }
 int miqp_solver_set_params(miqp_solver_t* s, const miqp_model_params_c* p) {
   if (!s || !p) return -1;
   s->has_inst = inst_from_params(p, s->opts.precision - 2, s->inst, s->err);
-  s->rescache.reset();
+  s->rescache.reset(); s->drop_fixed_batch();
   s->has_sol = false;   // MIP starts stay registered (the reference keeps them in the wrapper across resetParameters)
   if (!s->has_inst) std::fprintf(stderr, "[miqp_gpu] %s\n", s->err.c_str());
   return s->has_inst ? 0 : -2;
@@ -1657,7 +1663,7 @@ int miqp_solver_set_params(miqp_solver_t* s, const miqp_model_params_c* p) {
 int miqp_solver_load_dat(miqp_solver_t* s, const char* path) {
   if (!s || !path) return -1;
   s->has_inst = inst_from_dat(path, s->inst, s->err);
-  s->has_sol = false; s->rescache.reset();
+  s->has_sol = false; s->rescache.reset(); s->drop_fixed_batch();
   if (!s->has_inst) std::fprintf(stderr, "[miqp_gpu] %s\n", s->err.c_str());
   return s->has_inst ? 0 : -2;
 }

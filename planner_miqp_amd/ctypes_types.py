@@ -93,6 +93,12 @@ class Certificate:
                 % (self.max_violation, self.worst_family, fam, self.worst_row, self.rows, self.objective, self.max_int_infeas))
 
 
+class FixedResultC(C.Structure):
+    """miqp_fixed_result_c (include/miqp_types.h): one entry of CplexWrapper.solveFixedBatch"""
+    _fields_ = [("status", C.c_int), ("route", C.c_int), ("iterations", C.c_int), ("reserved", C.c_int),
+                ("objective", C.c_double), ("violation", C.c_double)]
+
+
 class SolverOptsC(C.Structure):
     _fields_ = [("precision", C.c_int), ("device", C.c_int), ("nodes_per_round", C.c_int),
                 ("max_open_nodes", C.c_int), ("gap_override", C.c_double), ("verbose", C.c_int)]

@@ -12,7 +12,7 @@ import numpy as np
 # (four concurrent launches per round + the null stream: see miqp_gpu.hip - effective when set before the process's first HIP call)
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
-from .ctypes_types import (Certificate, CertificateC, ModelParameters, ModelParamsC, RawResults, RawResultsC, SolutionPropertiesC, SolverOptsC,
+from .ctypes_types import (Certificate, CertificateC, FixedResultC, ModelParameters, ModelParamsC, RawResults, RawResultsC, SolutionPropertiesC, SolverOptsC,
                            c_double_p)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -92,6 +92,14 @@ def load_library():
     L.miqp_gpu_certificate_size.restype = C.c_int; L.miqp_gpu_certificate_size.argtypes = []
     L.miqp_gpu_certify_last_timing.restype = C.c_int; L.miqp_gpu_certify_last_timing.argtypes = [C.POINTER(C.c_double)]
     L.miqp_gpu_has_active_set.restype = C.c_int; L.miqp_gpu_has_active_set.argtypes = [C.c_int, C.c_int]
+    L.miqp_solver_solve_fixed_batch.restype = C.c_int
+    L.miqp_solver_solve_fixed_batch.argtypes = [vp, C.POINTER(C.POINTER(RawResultsC)), C.c_int, C.POINTER(FixedResultC), C.POINTER(C.c_int)]
+    L.miqp_solver_fixed_batch_record.restype = C.c_int; L.miqp_solver_fixed_batch_record.argtypes = [vp, C.c_int, C.POINTER(RawResultsC)]
+    L.miqp_gpu_fixed_result_size.restype = C.c_int; L.miqp_gpu_fixed_result_size.argtypes = []
+    L.miqp_gpu_fixed_batch_chunk.restype = C.c_int; L.miqp_gpu_fixed_batch_chunk.argtypes = []
+    if L.miqp_gpu_fixed_result_size() != C.sizeof(FixedResultC):
+        raise RuntimeError("libmiqp_gpu.so and ctypes_types.FixedResultC disagree on miqp_fixed_result_c (%d / %d bytes): rebuild the library"
+                           % (L.miqp_gpu_fixed_result_size(), C.sizeof(FixedResultC)))
     L.miqp_gpu_version.restype = C.c_char_p
     _LIB = L
     return L
@@ -110,7 +118,13 @@ EXPORTED_SYMBOLS = ["miqp_solver_create", "miqp_solver_destroy", "miqp_solver_se
                     "miqp_comm_init", "miqp_comm_finalize", "miqp_comm_selftest", "miqp_solver_solve_stream", "miqp_solver_materialize_results",
                     "miqp_initial_pose_check", "miqp_select_environment", "miqp_obstacle_intersects_environment", "miqp_obstacles_roi", "miqp_bark_trajectory", "miqp_obstacle_intersects_environment_roi", "miqp_environment_warmstart",
                     "miqp_solver_certify", "miqp_solver_certify_batch", "miqp_gpu_certificate_size", "miqp_gpu_certify_last_timing",
-                    "miqp_gpu_has_active_set", "miqp_solver_last_fixed_route"]
+                    "miqp_gpu_has_active_set", "miqp_solver_last_fixed_route",
+                    "miqp_solver_solve_fixed_batch", "miqp_solver_fixed_batch_record", "miqp_gpu_fixed_result_size", "miqp_gpu_fixed_batch_chunk"]
+
+
+def fixed_batch_chunk():
+    """nodes per launch group of CplexWrapper.solveFixedBatch (a constant of the built library; needs no device)"""
+    return int(load_library().miqp_gpu_fixed_batch_chunk())
 
 
 def has_active_set(cars, steps):
@@ -380,6 +394,36 @@ class CplexWrapper:
         """which launch solved the node of the last solveFixed(): 0 the standard on-chip kernel, 1 its larger variant, 2 the
         memory-backed kernel behind them, 3 the memory-backed kernel of a shape without an on-chip kernel; -1 before any"""
         return int(self._L.miqp_solver_last_fixed_route(self._h))
+
+    def solveFixedBatch(self, records):
+        """the continuous QPs of many records of this wrapper's instance in one device call (miqp_solver_solve_fixed_batch): each entry is
+        answered as solveFixed answers it alone.  Returns (status, objective, violation, iterations, route, best): numpy arrays of
+        len(records) - status 0 feasible, 1 infeasible, 2 entry refused (None, or a record of another shape) - and the index of the feasible
+        entry with the lowest objective (-1: none).  Raises RuntimeError where the library refuses the call (no device: there is no host solve)."""
+        if self._push_inputs() != 0:
+            raise RuntimeError("invalid parameters")
+        n = len(records)
+        keep = [r.to_c() if r is not None else None for r in records]
+        ptrs = (C.POINTER(RawResultsC) * max(n, 1))(*[C.pointer(c) if c is not None else None for c in keep])
+        out = (FixedResultC * max(n, 1))()
+        best = C.c_int(-1)
+        rc = self._L.miqp_solver_solve_fixed_batch(self._h, ptrs, n, out, C.byref(best))
+        if rc != 0:
+            raise RuntimeError("miqp_solver_solve_fixed_batch failed (%d)" % rc)
+        a = np.frombuffer(out, dtype=np.dtype([("status", "<i4"), ("route", "<i4"), ("iterations", "<i4"), ("reserved", "<i4"),
+                                               ("objective", "<f8"), ("violation", "<f8")]), count=n)
+        return (a["status"].copy(), a["objective"].copy(), a["violation"].copy(), a["iterations"].copy(), a["route"].copy(), best.value)
+
+    def fixedBatchRecord(self, k):
+        """(rc, RawResults) of entry ``k`` of the last solveFixedBatch of this wrapper: rc 0 and the record solveFixed would have returned
+        for it; rc 1 (entry not feasible), -1 (no such entry, no batch held: new parameters drop it) with None"""
+        d = (C.c_int * 6)()
+        if self._L.miqp_solver_get_dims(self._h, d) != 0:
+            return -1, None
+        out = RawResults(*list(d))
+        oc = out.to_c()
+        rc = self._L.miqp_solver_fixed_batch_record(self._h, int(k), C.byref(oc))
+        return rc, (out if rc == 0 else None)
 
     def liftTables(self):
         """response tables of the bound lifting, array [car][axis][step][4][4] (diagnostic, no device needed)"""
