@@ -6,6 +6,7 @@
 #ifndef CPLEX_WRAPPER_HEADER
 #define CPLEX_WRAPPER_HEADER
 
+#include <algorithm>
 #include <array>
 #include <cmath>
 #include <cstdio>
@@ -105,6 +106,7 @@ class CplexWrapper {
     try {
       if (!h_) { miqp_solver_opts o{}; o.precision = roundingDecimals_ + 2; o.device = -1; o.gap_override = -1.0; h_ = miqp_solver_create(&o); }   // (the C ABI rounds to precision - 2)
       if (!h_) return FAILED_SEG_FAULT;
+      miqp_solver_set_pool(h_, poolCapacity_);
       if (parameterSource_ == DATFILE || (parameterSource_ == MIXED && !parameters_)) {   // MIXED: the C++ inputs when given, else the file
         if (miqp_solver_load_dat(h_, datfile_.c_str()) != 0) return FAILED_SEG_FAULT;
       } else { if (!parameters_ || !pushParameters()) return FAILED_SEG_FAULT; }
@@ -181,6 +183,37 @@ class CplexWrapper {
     if (!h_ || miqp_solver_get_dims(h_, d) != 0) return nullptr;
     Pod p(d[0], d[1], d[2], d[3], d[4], d[5]);
     if (miqp_solver_fixed_batch_record(h_, k, &p.c) != 0) return nullptr;
+    auto out = std::make_shared<RawResults>();
+    unpackPod(p, *out);
+    return out;
+  }
+  // Solution pool (miqp_solver_set_pool ...; for a CPLEX user IloCplex::getSolnPoolNsolns / getObjValue(i) / getValues(x, i) - the reference source
+  // has no call site for them).  setSolutionPool: the next callCplex keeps its `capacity` best distinct integer solutions (0: off); returns the
+  // library's code.  solutionPoolCount: entries the last callCplex kept.  solveSolutionPool: refines them in one device call, one result per entry
+  // in pool order (entry 0: the incumbent); returns the number left, < 0 on failure.  solutionPoolRecord(k): the record of entry k of that call,
+  // null when the entry did not come out feasible or there is none.
+  // NOTE - the count can SHRINK in solveSolutionPool.  The search tells entries apart by what they decide (regions, pieces, obstacle edges, car/car
+  // alternatives), and two such records can be one solution with the same binaries; only the refinement sees that and merges them.  Before
+  // solveSolutionPool, solutionPoolCount() is an upper bound; behind it, it is the number that call returned, and entry numbers are those of the
+  // merged pool.  Size result buffers from the count BEFORE the call (as solveSolutionPool does itself) and use what it returns, not that count.
+  int setSolutionPool(int capacity) {   // (the handle is made by the first callCplex: the setting is kept here and handed on there)
+    if (capacity < 0 || capacity > miqp_gpu_pool_max()) return -2;
+    poolCapacity_ = capacity;
+    return h_ ? miqp_solver_set_pool(h_, capacity) : 0;
+  }
+  int solutionPoolCount() const { return h_ ? miqp_solver_pool_count(h_) : 0; }
+  int solveSolutionPool(std::vector<miqp_fixed_result_c>& results) {
+    results.assign(h_ ? (size_t)std::max(1, miqp_solver_pool_count(h_)) : 1, miqp_fixed_result_c{2, -1, 0, 0, std::nan(""), std::nan("")});
+    if (!h_) { results.clear(); return -1; }
+    const int m = miqp_solver_pool_solve(h_, results.data(), (int)results.size());
+    results.resize(m > 0 ? (size_t)m : 0);
+    return m;
+  }
+  std::shared_ptr<RawResults> solutionPoolRecord(int k) {
+    int d[6];
+    if (!h_ || miqp_solver_get_dims(h_, d) != 0) return nullptr;
+    Pod p(d[0], d[1], d[2], d[3], d[4], d[5]);
+    if (miqp_solver_pool_record(h_, k, &p.c) != 0) return nullptr;
     auto out = std::make_shared<RawResults>();
     unpackPod(p, *out);
     return out;
@@ -337,6 +370,7 @@ class CplexWrapper {
   bool bufferCplexOutputsToStream_ = false;
   std::shared_ptr<ModelParameters> parameters_;
   miqp_solver_t* h_ = nullptr;  // created lazily
+  int poolCapacity_ = 0;       // setSolutionPool
 };
 
 }  // namespace cplex

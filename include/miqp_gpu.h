@@ -218,6 +218,48 @@ int miqp_gpu_fixed_result_size(void);
 /* nodes per launch group of miqp_solver_solve_fixed_batch: a constant of the build (no reference counterpart; no device is needed or touched) */
 int miqp_gpu_fixed_batch_chunk(void);
 
+/* ---- solution pool: the K best distinct integer solutions of a solve.  Counterpart of the CPLEX solution pool - IloCplex::getSolnPoolNsolns,
+ * getObjValue(i), getValues(x, i) - which a user of the reference reaches through the IloCplex its wrapper owns; the reference source has no call
+ * site for it. ----
+ * miqp_solver_set_pool: the next solves of the handle keep up to `capacity` solutions, 0 <= capacity <= miqp_gpu_pool_max(); 0 (the default) = off:
+ * then nothing is allocated and no kernel is launched for it.  Returns 0, -1 NULL handle, -2 capacity out of range (the previous setting stays).
+ * With a pool, every integer-feasible leaf the branch and bound evaluates is merged on the device into the pool of its instance, which keeps the
+ * `capacity` smallest DISTINCT ones in the order (objective as found, hash of the record, bytes of the record) - a function of the set of leaves seen,
+ * not of their arrival order, so the pool of a single solve is reproducible bit for bit like the solve itself.  Two leaves are the same entry when they
+ * decide every disjunction alike.  The incumbent of the solve is entry 0, at every capacity.  (The search compares objectives to 44 bits and breaks
+ * ties by a hash of its own; among records whose objectives agree to those 44 bits the incumbent's is put first whatever the order above says, so
+ * the found objectives do not decrease up to that resolution, 2.4e-10 relative.)  The solve, its tree and its result are the same with and without a pool.
+ * Works in miqp_solver_solve, _solve_batch, _solve_stream (per handle: handles with and without a pool may share a call) and _solve_batch_multi (each
+ * device on its own).  A rank of miqp_solver_solve_split keeps the pool of its OWN search: pools are not exchanged.
+ * Device memory: instances of the call x largest capacity among them x (record bytes + 12); a pool that does not fit fails the call like any other
+ * allocation failure, and miqp_solver_last_error says so. */
+int miqp_solver_set_pool(miqp_solver_t* s, int capacity);
+/* number of entries the handle's last solve kept (getSolnPoolNsolns): 0 with the pool off, before a solve, without a solution and after
+ * miqp_solver_set_params / _load_dat.  Needs no device.  Behind miqp_solver_pool_solve it is the number that call left: the search tells leaves apart
+ * by what they decide, and two such records can be ONE solution - the optimum of one also holds the alternatives the other asserts, so both QPs have
+ * the same minimiser and their RawResults carry the same binaries.  Only the refinement sees that; it merges them (the best found stays), and
+ * the count, the found objectives and the entry numbers are from then on those of the merged pool.  Until then the count is an upper bound. */
+int miqp_solver_pool_count(const miqp_solver_t* s);
+/* the objectives of those entries as the search found them (node tolerance; constant cost included), best first: obj[0 .. min(count, cap) - 1];
+ * returns how many were written, -1 on NULL arguments.  Needs no device. */
+int miqp_solver_pool_found(const miqp_solver_t* s, double* obj, int cap);
+/* refines the kept entries: their continuous QPs at the tight tolerance, as nodes of one fixed-batch call (miqp_solver_solve_fixed_batch: one context,
+ * one upload of the tables, one device lock), out[k] in pool order for k < min(count, cap).  Every entry is answered as miqp_solver_solve_fixed
+ * answers the entry's record (miqp_solver_pool_record), bit for bit: for that the call labels each record with the canonical binaries of its own
+ * solution and solves again while labels move (a few launch groups; miqp_solver_last_timing out[2] = their number, out[0], out[1], out[3], out[4] as
+ * for the fixed batch; out[5] = 1 when labels still moved after the last pass - the entries are then answers to the labels of that pass, and
+ * miqp_solver_last_error says so - else 0).  Entries that come out with the same binaries are one solution and are merged (see miqp_solver_pool_count): the records of
+ * miqp_solver_pool_record differ pairwise in at least one binary.  Returns the number of entries left, which out[] then holds and
+ * miqp_solver_pool_count reports (0: nothing kept), -1 invalid arguments / no instance, -3 no device / kernel image / HIP error.
+ * The handle keeps the trajectories for miqp_solver_pool_record until its next solve, pool_solve or parameters.  Like the fixed batch it needs a device
+ * context of the batch call's sizes: it rebuilds the one the solve left, and the next solve rebuilds its own. */
+int miqp_solver_pool_solve(miqp_solver_t* s, miqp_fixed_result_c* out, int cap);
+/* the RawResults record of entry k of the handle's last miqp_solver_pool_solve (getValues(x, i)), built as miqp_solver_fixed_batch_record builds its own.
+ * 0, 1 when entry k did not come out feasible at the tight tolerance, -1 bad k / no refined pool held, -2 sizes of out differ from the instance. */
+int miqp_solver_pool_record(miqp_solver_t* s, int k, miqp_raw_results_c* out);
+/* largest capacity miqp_solver_set_pool accepts: a constant of the build (no device is needed or touched) */
+int miqp_gpu_pool_max(void);
+
 /* 1 when instances of this shape (NrCars, N) have the dual active-set launches - one or two cars, a horizon of up to 20 steps - else 0 (their node
  * relaxations are interior point solves).  Pure host code: no device is needed or touched.  A call switches the launches off with MIQP_AS=0 */
 int miqp_gpu_has_active_set(int num_cars, int num_steps);

@@ -186,6 +186,35 @@ bool fixed_batch_run(DevCtx& X, FixedBatchDev& G, const Layout& Y, const std::ve
   return true;
 }
 
+// The part of a fixed-batch call that runs PREPARED fix bytes (miqp_solver_solve_fixed_batch; miqp_solver_pool_solve of solution_pool.hip): open() takes the
+// device and its lock, brings the context to the sizes of the batch call, compiles the instance and checks its first step; run() sends m fix records of
+// Y.fixlen bytes through the chain.  The lock is held until the object goes.  Both return 0 or -3 (no device / kernel image / HIP error)
+struct FixedBatchCall {
+  miqp_solver_t* s = nullptr; Layout Y{}; DevCtx* X = nullptr; std::unique_lock<std::mutex> lock;
+  std::vector<double> D; std::vector<int> T; double cobj = 0;
+  int open(miqp_solver_t* s_, const Layout& Y_) {
+    s = s_; Y = Y_;
+    X = ctx_for_device(s->opts.device);
+    if (!X) return -3;
+    lock = std::unique_lock<std::mutex>(X->mu);
+    bool rebuilt = false; const double t_ctx = wall_s();
+    if (!ctx_prepare(*X, Y, 1, 1, 64, FB_CHUNK, 3, false, 1, &rebuilt)) return -3;
+    s->setup[1] = wall_s() - t_ctx; s->setup[2] = rebuilt ? 1.0 : 0.0;
+    if (X->batch_cap < FB_CHUNK || X->batch_alloc < FB_CHUNK || X->pool_cap < FB_CHUNK) { std::fprintf(stderr, "[miqp_gpu] the device context does not hold a chunk of %d nodes\n", FB_CHUNK); return -3; }
+    if (!set_kernel_lds(Y, ipm_lds_bytes(Y), eval_lds_bytes(Y, read_call_switches().seq_kinds))) return -3;
+    D.resize(Y.dstride); T.resize(Y.istride);
+    compile_instance(s->inst, Y, D.data(), T.data());
+    HostGeo G{s->inst, Y, D.data(), T.data()}; (void)step0_check(G, cobj);
+    return 0;
+  }
+  int run(const std::vector<signed char>& fix, int m, std::vector<miqp_fixed_result_c>& tmp, std::vector<double>& Z, std::vector<double>& bo, std::vector<int>& bi, float& dev_ms) {
+    FixedBatchDev& F = g_fixed_batch_dev[X->device];
+    if (!F.ensure((size_t)FB_CHUNK * Y.fixlen, (size_t)m, (size_t)m * Y.N * Y.nz)) return -3;
+    if (!fixed_batch_run(*X, F, Y, D, T, fix, m, cobj, tmp, Z, bo, bi, dev_ms)) { (void)hipStreamSynchronize(X->stream); (void)hipStreamSynchronize(F.s_up); return -3; }
+    return 0;
+  }
+};
+
 }  // namespace
 
 extern "C" {
@@ -209,18 +238,10 @@ int miqp_solver_solve_fixed_batch(miqp_solver_t* s, const miqp_raw_results_c* co
   for (int k = 0; k < n; ++k) if (fixed[k] && fixed_record_ok(*fixed[k]) && dims_match(*fixed[k], s->inst)) where.push_back(k);
   const int m = (int)where.size();
   if (m == 0) return 0;   // (nothing to run: no device is touched)
-  DevCtx* Xp = ctx_for_device(s->opts.device);
-  if (!Xp) return -3;
-  DevCtx& X = *Xp;
-  std::lock_guard<std::mutex> ctx_lock(X.mu);
-  bool rebuilt = false; const double t_ctx = wall_s();
-  if (!ctx_prepare(X, Y, 1, 1, 64, FB_CHUNK, 3, false, 1, &rebuilt)) return -3;
-  s->setup[1] = wall_s() - t_ctx; s->setup[2] = rebuilt ? 1.0 : 0.0;
-  if (X.batch_cap < FB_CHUNK || X.batch_alloc < FB_CHUNK || X.pool_cap < FB_CHUNK) { std::fprintf(stderr, "[miqp_gpu] the device context does not hold a chunk of %d nodes\n", FB_CHUNK); return -3; }
-  if (!set_kernel_lds(Y, ipm_lds_bytes(Y), eval_lds_bytes(Y, read_call_switches().seq_kinds))) return -3;
-  std::vector<double> D(Y.dstride); std::vector<int> T(Y.istride);
-  compile_instance(s->inst, Y, D.data(), T.data());
-  const size_t fl = (size_t)Y.fixlen, row = (size_t)Y.N * Y.nz;
+  FixedBatchCall call;
+  if (call.open(s, Y) != 0) return -3;
+  const std::vector<int>& T = call.T;
+  const size_t fl = (size_t)Y.fixlen;
   std::vector<signed char> fix((size_t)m * fl);
   {   // fix records on a few host threads when there are many (at most 16, as everywhere)
     const int nth = std::max(1, std::min({16, process_switches().prep_threads, (int)std::thread::hardware_concurrency(), m / 256}));
@@ -232,12 +253,9 @@ int miqp_solver_solve_fixed_batch(miqp_solver_t* s, const miqp_raw_results_c* co
     if (nth <= 1) work();
     else { std::vector<std::thread> th; for (int t = 0; t < nth; ++t) th.emplace_back(work); for (auto& t : th) t.join(); }
   }
-  HostGeo G{s->inst, Y, D.data(), T.data()}; double cobj = 0; (void)step0_check(G, cobj);
   s->setup[0] = wall_s() - t_call;
-  FixedBatchDev& F = g_fixed_batch_dev[X.device];
-  if (!F.ensure((size_t)FB_CHUNK * fl, (size_t)m, (size_t)m * row)) return -3;
   std::vector<miqp_fixed_result_c> tmp; std::vector<double> Z, bo; std::vector<int> bi; float dev_ms = 0.0f;
-  if (!fixed_batch_run(X, F, Y, D, T, fix, m, cobj, tmp, Z, bo, bi, dev_ms)) { (void)hipStreamSynchronize(X.stream); (void)hipStreamSynchronize(F.s_up); return -3; }
+  if (call.run(fix, m, tmp, Z, bo, bi, dev_ms) != 0) return -3;
   for (int c = 0; c < m; ++c) out[where[c]] = tmp[c];
   {   // the minimum of the call from the chunks' minima (ascending chunks: a tie keeps the lower index)
     double b = 0; int at = -1;

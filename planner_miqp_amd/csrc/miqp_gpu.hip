@@ -110,6 +110,12 @@ struct miqp_solver {
   // call and whenever the instance changes
   int fb_n = 0; std::vector<int> fb_slot; std::vector<double> fb_Z; std::vector<signed char> fb_fix;
   void drop_fixed_batch() { fb_n = 0; std::vector<int>().swap(fb_slot); std::vector<double>().swap(fb_Z); std::vector<signed char>().swap(fb_fix); }
+  // solution pool (solution_pool.hip).  pool_cap: what miqp_solver_set_pool asked for, 0 = off.  Of the last solve: the pool_n kept fix records (best first),
+  // their objectives as found and the record length; of the last miqp_solver_pool_solve: per entry whether it came out feasible, the fix record it was
+  // refined with and its trajectory.  Dropped by the next solve and whenever the instance changes
+  int pool_cap = 0, pool_n = 0, pool_fixlen = 0; std::vector<signed char> pool_fix; std::vector<double> pool_obj;
+  int pr_n = 0; std::vector<char> pr_ok; std::vector<signed char> pr_fix; std::vector<double> pr_Z;
+  void drop_pool() { pool_n = 0; pr_n = 0; std::vector<signed char>().swap(pool_fix); std::vector<double>().swap(pool_obj); std::vector<char>().swap(pr_ok); std::vector<signed char>().swap(pr_fix); std::vector<double>().swap(pr_Z); }
   std::string err;
 };
 
@@ -319,6 +325,15 @@ CallSwitches read_call_switches() {
   return w;
 }
 
+// device side of the solution pool (solution_pool.hip): allocated with the context when a call asks for a pool, freed with it
+struct SolPoolDev {
+  int* list = nullptr; int* count = nullptr;   // the round's candidates: batch slots, and their number (two words, by the parity of the capture)
+  signed char* fix = nullptr; double* obj = nullptr; unsigned int* hash = nullptr; int* cnt = nullptr; int* cap = nullptr;   // [n_inst][stride] records, objectives, hashes; [n_inst] entries kept, capacity asked for
+  int n_inst = 0, stride = 0, list_cap = 0;
+  int captures = 0;   // capture launches of the call: a capture uses count[captures & 1] and zeroes the other word for the next one (NOT the round number: rounds without a batch launch no capture)
+  bool on = false;   // the call that holds the context has a handle with a pool
+};
+
 struct DevCtx {
   std::mutex mu;   // held for the whole solve: one solve at a time per device, different devices run concurrently
   bool ready = false; int device = -1;
@@ -345,6 +360,7 @@ struct DevCtx {
   unsigned short* as_batch_A = nullptr; unsigned short* as_pool_A = nullptr;   // (kept here: a call with MIQP_AS=0 runs with the DevBuf pointers nulled)   // dual active-set launch in front of the standard interior point launch (the shapes of as_shape_ok; MIQP_AS=0: off)
   DevBuf B{};
   CallSwitches sw;   // of the call that holds the context (apply_call_switches)
+  SolPoolDev pool;
   std::vector<void*> allocs;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   std::vector<hipEvent_t> ipm_ev;  // pairs
@@ -361,6 +377,7 @@ struct DevCtx {
     ipm_ev.clear();
     for (auto e : std_ev) (void)hipEventDestroy(e);
     std_ev.clear();
+    pool = SolPoolDev{};
     ready = false;
   }
 };
@@ -1010,6 +1027,9 @@ void split_roots(const Layout& Y, const int* T, std::vector<std::vector<std::pai
 
 #include "solve_diag.hpp"
 
+// solution pool (solution_pool.hip): the capture launches behind a round's evaluation, `bc` nodes wide
+bool pool_capture(DevCtx& X, int bc);
+
 // ---------------------------------------------------------------- the batch solve: shape of the call
 // `inflight`: instances solved concurrently (<= 0 or >= n: all of them).  With fewer than n the call is a queue drained by
 // streaming admission: an instance that is proven (or has used up its own max_solution_time, counted from its admission)
@@ -1411,6 +1431,7 @@ struct Rounds {
       if (sw.trace && !trace_batch(X, rounds, bc)) return false;
       // ---- evaluation: incumbents, pruning, children into the list buffer the next select reads
       { DevBuf Be = B; Be.open_sel = 1 - (rounds & 1); launch_eval_c(Y.C, Be, bc, l_eval, st); }
+      if (X.pool.on && !pool_capture(X, bc)) return false;   // (before the next evaluation overwrites the candidates)
       if (sw.debug_sync) debug_sync(st, rounds, "eval");
       launched_nodes += bc; rounds++; prev_bc = bc;
       if (ps.round_log) round_bc.push_back(bc);
@@ -1560,12 +1581,16 @@ void report(miqp_solver_t* const* S, int* statuses, const Layout& Y, const HostT
   if (L.abandoned) std::fprintf(stderr, "[miqp_gpu] the round loop was abandoned with %d of %d instances never admitted: they report FAILED_SEG_FAULT, the call fails\n", n - L.next_q, n);
 }
 
+// solution pool (solution_pool.hip): the buffers and the reset of a call with a pool (nothing without one); the kept entries to the handles
+bool pool_prepare(DevCtx& X, miqp_solver_t* const* S, int n);
+bool pool_read_back(const DevCtx& X, miqp_solver_t* const* S, int n, const Results& R);   // (R.fix: the incumbents' records)
+
 // ---------------------------------------------------------------- the batch solve
 bool solve_batch_impl(miqp_solver_t* const* S, int n, int* statuses, const SplitCtx* split = nullptr, int inflight = 0, int lane = 0, int lanes = 1) {
   // every way out of this function that is not report() at its end (a failed HIP call, a failed exchange) leaves "the solver could not
   // run" behind: a caller's zero-filled status array would otherwise read as SUCCESS for instances that were never solved.  Every phase
   // returns false on such a failure (HIP_OK does, after naming the call) and nothing before report() touches `statuses`
-  for (int k = 0; k < n; ++k) { statuses[k] = MIQP_STATUS_FAILED_SEG_FAULT; if (S[k]) { S[k]->status = MIQP_STATUS_FAILED_SEG_FAULT; S[k]->has_sol = false; S[k]->rescache.reset(); } }
+  for (int k = 0; k < n; ++k) { statuses[k] = MIQP_STATUS_FAILED_SEG_FAULT; if (S[k]) { S[k]->status = MIQP_STATUS_FAILED_SEG_FAULT; S[k]->has_sol = false; S[k]->rescache.reset(); S[k]->drop_pool(); } }
   if (split && n != 1) return false;
   BatchShape bs = batch_layout(S, n);
   if (!bs.ok) { for (int k = 0; k < n; ++k) { if (S[k]) S[k]->err = bs.err; statuses[k] = MIQP_STATUS_FAILED_SEG_FAULT; } std::fprintf(stderr, "[miqp_gpu] %s\n", bs.err.c_str()); return false; }
@@ -1590,6 +1615,7 @@ bool solve_batch_impl(miqp_solver_t* const* S, int n, int* statuses, const Split
     bool setup_ok = ctx_prepare(X, Y, n, sh.NS, sh.open_cap, sh.npr, sh.MAXR, sh.clamp_open, lanes, &T.ctx_built);
     if (setup_ok && (l_ipm > 160 * 1024 || l_eval > 160 * 1024)) { std::fprintf(stderr, "[miqp_gpu] instance too large for LDS (%zu bytes)\n", l_ipm); setup_ok = false; }
     if (setup_ok && !set_kernel_lds(Y, l_ipm, l_eval)) setup_ok = false;
+    if (setup_ok && !pool_prepare(X, S, n)) setup_ok = false;
     if (split) {
       unsigned long long w = setup_ok ? 1ull : 0ull;
       if (split->fn(split->user, 0, &w, 1, 0) != 0) return fail_all("set-up exchange failed");
@@ -1623,8 +1649,10 @@ bool solve_batch_impl(miqp_solver_t* const* S, int n, int* statuses, const Split
 
   Results R;
   if (!read_back(X, n, R) || !take_polished(X, S, n, H, P, R)) return fail_all(nullptr);
+  if (X.pool.on && !pool_read_back(X, S, n, R)) return fail_all(nullptr);   // (before the broadcast of a tree split: a rank keeps the pool of its own search)
   if (split && !split_broadcast(split, L.sp, R)) return fail_all(nullptr);
   report(S, statuses, Y, H, L, R, T, split != nullptr);
+  for (int k = 0; k < n; ++k) if (!S[k]->has_sol) S[k]->drop_pool();
   if (sw.stats) std::fprintf(stderr, "[miqp_gpu stats] reachable-set diameter (L1) of instance 0: %.1f\n", H.D[Y.d_misc + 2]);
   if (sw.stats) std::fprintf(stderr, "[miqp_gpu stats] host: setup %.3f s (device context %.3f, instance tables and presolve %.3f, upload %.3f), rounds %.3f s (%d), results %.3f s\n", T.t_setup, T.t_ctx, T.t_tables, T.t_setup - T.t_ctx - T.t_tables, T.t_solve, L.rounds, wall_s() - L.t0 - T.t_solve);
   return !L.abandoned;
@@ -1634,6 +1662,7 @@ bool solve_batch_impl(miqp_solver_t* const* S, int n, int* statuses, const Split
 
 #include "certify.hip"
 #include "fixed_batch.hip"
+#include "solution_pool.hip"
 
 // ================================================================================================
 //  C ABI
@@ -1654,7 +1683,7 @@ void miqp_solver_destroy(miqp_solver_t* s) { delete s; }
 int miqp_solver_set_params(miqp_solver_t* s, const miqp_model_params_c* p) {
   if (!s || !p) return -1;
   s->has_inst = inst_from_params(p, s->opts.precision - 2, s->inst, s->err);
-  s->rescache.reset(); s->drop_fixed_batch();
+  s->rescache.reset(); s->drop_fixed_batch(); s->drop_pool();
   s->has_sol = false;   // MIP starts stay registered (the reference keeps them in the wrapper across resetParameters)
   if (!s->has_inst) std::fprintf(stderr, "[miqp_gpu] %s\n", s->err.c_str());
   return s->has_inst ? 0 : -2;
@@ -1663,7 +1692,7 @@ int miqp_solver_set_params(miqp_solver_t* s, const miqp_model_params_c* p) {
 int miqp_solver_load_dat(miqp_solver_t* s, const char* path) {
   if (!s || !path) return -1;
   s->has_inst = inst_from_dat(path, s->inst, s->err);
-  s->has_sol = false; s->rescache.reset(); s->drop_fixed_batch();
+  s->has_sol = false; s->rescache.reset(); s->drop_fixed_batch(); s->drop_pool();
   if (!s->has_inst) std::fprintf(stderr, "[miqp_gpu] %s\n", s->err.c_str());
   return s->has_inst ? 0 : -2;
 }

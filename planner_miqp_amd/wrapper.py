@@ -97,6 +97,12 @@ def load_library():
     L.miqp_solver_fixed_batch_record.restype = C.c_int; L.miqp_solver_fixed_batch_record.argtypes = [vp, C.c_int, C.POINTER(RawResultsC)]
     L.miqp_gpu_fixed_result_size.restype = C.c_int; L.miqp_gpu_fixed_result_size.argtypes = []
     L.miqp_gpu_fixed_batch_chunk.restype = C.c_int; L.miqp_gpu_fixed_batch_chunk.argtypes = []
+    L.miqp_solver_set_pool.restype = C.c_int; L.miqp_solver_set_pool.argtypes = [vp, C.c_int]
+    L.miqp_solver_pool_count.restype = C.c_int; L.miqp_solver_pool_count.argtypes = [vp]
+    L.miqp_solver_pool_found.restype = C.c_int; L.miqp_solver_pool_found.argtypes = [vp, c_double_p, C.c_int]
+    L.miqp_solver_pool_solve.restype = C.c_int; L.miqp_solver_pool_solve.argtypes = [vp, C.POINTER(FixedResultC), C.c_int]
+    L.miqp_solver_pool_record.restype = C.c_int; L.miqp_solver_pool_record.argtypes = [vp, C.c_int, C.POINTER(RawResultsC)]
+    L.miqp_gpu_pool_max.restype = C.c_int; L.miqp_gpu_pool_max.argtypes = []
     if L.miqp_gpu_fixed_result_size() != C.sizeof(FixedResultC):
         raise RuntimeError("libmiqp_gpu.so and ctypes_types.FixedResultC disagree on miqp_fixed_result_c (%d / %d bytes): rebuild the library"
                            % (L.miqp_gpu_fixed_result_size(), C.sizeof(FixedResultC)))
@@ -119,7 +125,13 @@ EXPORTED_SYMBOLS = ["miqp_solver_create", "miqp_solver_destroy", "miqp_solver_se
                     "miqp_initial_pose_check", "miqp_select_environment", "miqp_obstacle_intersects_environment", "miqp_obstacles_roi", "miqp_bark_trajectory", "miqp_obstacle_intersects_environment_roi", "miqp_environment_warmstart",
                     "miqp_solver_certify", "miqp_solver_certify_batch", "miqp_gpu_certificate_size", "miqp_gpu_certify_last_timing",
                     "miqp_gpu_has_active_set", "miqp_solver_last_fixed_route",
-                    "miqp_solver_solve_fixed_batch", "miqp_solver_fixed_batch_record", "miqp_gpu_fixed_result_size", "miqp_gpu_fixed_batch_chunk"]
+                    "miqp_solver_solve_fixed_batch", "miqp_solver_fixed_batch_record", "miqp_gpu_fixed_result_size", "miqp_gpu_fixed_batch_chunk",
+                    "miqp_solver_set_pool", "miqp_solver_pool_count", "miqp_solver_pool_found", "miqp_solver_pool_solve", "miqp_solver_pool_record", "miqp_gpu_pool_max"]
+
+
+def pool_max():
+    """largest capacity CplexWrapper.setSolutionPool accepts (a constant of the built library; needs no device)"""
+    return int(load_library().miqp_gpu_pool_max())
 
 
 def fixed_batch_chunk():
@@ -423,6 +435,49 @@ class CplexWrapper:
         out = RawResults(*list(d))
         oc = out.to_c()
         rc = self._L.miqp_solver_fixed_batch_record(self._h, int(k), C.byref(oc))
+        return rc, (out if rc == 0 else None)
+
+    # ---- solution pool (IloCplex::getSolnPoolNsolns / getObjValue(i) / getValues(x, i) for a CPLEX user)
+    def setSolutionPool(self, capacity):
+        """the next solves of this wrapper keep their ``capacity`` best distinct integer solutions (0: off, the default; at most pool_max()).
+        Returns the library's code: 0, < 0 when the capacity is refused (the previous setting stays)"""
+        return int(self._L.miqp_solver_set_pool(self._h, int(capacity)))
+
+    def solutionPoolCount(self):
+        """entries the last solve kept (0 with the pool off, before a solve, without a solution, after new parameters); needs no device.  Behind
+        solveSolutionPool: the entries that call left (it merges records that are one solution), before it an upper bound"""
+        return int(self._L.miqp_solver_pool_count(self._h))
+
+    def solutionPoolFound(self):
+        """the objectives of the kept entries as the search found them (node tolerance), best first; needs no device"""
+        n = self.solutionPoolCount()
+        o = np.zeros(max(n, 1))
+        m = self._L.miqp_solver_pool_found(self._h, o.ctypes.data_as(c_double_p), n)
+        return o[:max(m, 0)].copy()
+
+    def solveSolutionPool(self):
+        """the kept entries refined at the tight tolerance in one device call (miqp_solver_pool_solve): (status, objective, violation, iterations,
+        route) as numpy arrays in pool order, like solveFixedBatch - each entry as solveFixed answers its solutionPoolRecord.  Records that turn out
+        to be one solution (the same binaries) are merged, so the arrays can be shorter than solutionPoolCount() was before the call.  Raises RuntimeError
+        where the library refuses the call (no device: there is no host solve)."""
+        n = max(self.solutionPoolCount(), 1)
+        out = (FixedResultC * n)()
+        m = self._L.miqp_solver_pool_solve(self._h, out, n)
+        if m < 0:
+            raise RuntimeError("miqp_solver_pool_solve failed (%d)" % m)
+        a = np.frombuffer(out, dtype=np.dtype([("status", "<i4"), ("route", "<i4"), ("iterations", "<i4"), ("reserved", "<i4"),
+                                               ("objective", "<f8"), ("violation", "<f8")]), count=m)
+        return (a["status"].copy(), a["objective"].copy(), a["violation"].copy(), a["iterations"].copy(), a["route"].copy())
+
+    def solutionPoolRecord(self, k):
+        """(rc, RawResults) of entry ``k`` of the last solveSolutionPool: rc 0 and the record; rc 1 (the entry did not come out feasible at the
+        tight tolerance), -1 (no such entry, no refined pool held) with None"""
+        d = (C.c_int * 6)()
+        if self._L.miqp_solver_get_dims(self._h, d) != 0:
+            return -1, None
+        out = RawResults(*list(d))
+        oc = out.to_c()
+        rc = self._L.miqp_solver_pool_record(self._h, int(k), C.byref(oc))
         return rc, (out if rc == 0 else None)
 
     def liftTables(self):
