@@ -264,6 +264,18 @@ int miqp_gpu_pool_max(void);
  * relaxations are interior point solves).  Pure host code: no device is needed or touched.  A call switches the launches off with MIQP_AS=0 */
 int miqp_gpu_has_active_set(int num_cars, int num_steps);
 
+/* diagnostic: the node launches a solve of the handle's instance would issue for a round of bc nodes (overlap 1, par = the round's parity, or -1
+ * for a round without the parity counter sets) or for the serial chain of the polish and of miqp_solver_solve_fixed (overlap 0, par -1), on a device of
+ * `cus` compute units with `free_gb` GB free and all four streams.  cls_n3: the lengths of the round's three class lists, {-1, -1, -1}: not known.
+ * flags: 1 = the call uses the active-set launches (MIQP_AS), 2 = a context without the concurrent round (the tuning switch MIQP_CONCURRENT_BIG=0, which
+ * the shipped library does not read): the serial chain with its probe overlap.  Writes one row of 13 ints per launch, in the order of issue: kernel (0
+ * memory-backed, 1 / 2 larger active-set / larger on-chip interior point, 3 / 4 standard active-set / standard on-chip interior point), stream (0 the solver's, 2 .. 4 the ones beside
+ * it), workgroups, dynamic LDS bytes, ovf_mode, cls_take, as_split, skip_probes, bounce, work counter (> 0: word of the parity set, 0 the batch's, -1 the
+ * second stream's), hand-over list read (0 the standard launch's, 1 the larger variant's), per-block buffers (0 the batch's, 1 the second stream's,
+ * 2 those with the third gain buffer), memsets in front (1 work counter, 2 hand-over count, 4 the larger variant's hand-over count).  Returns the number
+ * of launches; < 0: no instance (-1), shape refused (-2), cap too small (-3).  Pure host code: no device is needed or touched */
+int miqp_solver_launch_plan(const miqp_solver_t* s, int bc, int overlap, int par, const int* cls_n3, int cus, double free_gb, int flags, int* out, int cap);
+
 /* host set-up of the last solve / batch / stream call this handle took part in: out[0] = seconds from the entry of the call to
  * the first round, out[1] = of which building the device context (pools, lists: reused by a call of the same shape with no more
  * instances than its per-instance arrays hold), out[2] = 1 when the context was built or rebuilt by that call, else 0 */

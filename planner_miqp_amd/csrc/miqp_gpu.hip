@@ -672,33 +672,20 @@ size_t eval_lds_bytes(const Layout& Y, int seq_kinds) {
          + (size_t)Y.fixlen + 16;                                  // ploose
 }
 
-// `zero` false: the counters of the launch are the round's parity set, zeroed by roll_kernel one round ahead (no memset in the stream)
-template <int C> void launch_ipm(const DevBuf& B, int nblocks, size_t lds, hipStream_t st, bool zero = true) { if (zero) (void)hipMemsetAsync(B.work_counter, 0, 4, st); hipLaunchKernelGGL((ipm_kernel<C, ipm_nt(C)>), dim3(nblocks), dim3(ipm_nt(C)), lds, st, B); }
-template <int C> void launch_ipm_oc(const DevBuf& B, int nblocks, size_t lds, hipStream_t st, bool zero = true) {
-  if (zero) { (void)hipMemsetAsync(B.work_counter, 0, 4, st); (void)hipMemsetAsync(B.ovf_count, 0, 4, st); }
-  hipLaunchKernelGGL((ipm_onchip_kernel<C, OC_NSL>), dim3(nblocks), dim3(64), lds, st, B);
-}
-// the larger variant: works through the list of the standard one (ovf_mode 1) or through the rounding probes of the batch (ovf_mode 2, on its
-// own stream with its own work counter); the caller has zeroed ovf2_count
-template <int C> void launch_ipm_oc_big(const DevBuf& B, int nblocks, size_t lds, hipStream_t st, bool zero = true) {
-  if (zero) (void)hipMemsetAsync(B.work_counter, 0, 4, st);
-  hipLaunchKernelGGL((ipm_onchip_kernel<C, OC_NSL, 0, OC_GCAP_BIG>), dim3(nblocks), dim3(64), lds, st, B);
-}
+// the node kernels of a round, by kind and car count: the launcher and set_kernel_lds take a kernel from here and nowhere else.  (The compiler emits the
+// instantiations in the order they are named here: the rows keep the order the launches named them in, and with it the code object byte for byte.)
+enum NodeKernel { NK_IPM, NK_AS_BIG, NK_OC_BIG, NK_AS, NK_OC, NK_KINDS };   // memory-backed ipm_kernel; larger active-set, larger on-chip interior point; standard active-set, standard on-chip interior point
+using NodeKernelFn = void (*)(DevBuf);
+const NodeKernelFn NODE_KERNEL[NK_KINDS][4] = {
+    {ipm_kernel<1, ipm_nt(1)>, ipm_kernel<2, ipm_nt(2)>, ipm_kernel<3, ipm_nt(3)>, ipm_kernel<4, ipm_nt(4)>},
+    {as_onchip_kernel<1, OC_NSL, OC_GCAP_BIG>, as_onchip_kernel<2, OC_NSL, OC_GCAP_BIG>, nullptr, nullptr},
+    // the larger variant: works through the list of the standard one (ovf_mode 1) or through the rounding probes of the batch (ovf_mode 2, on its
+    // own stream with its own work counter)
+    {ipm_onchip_kernel<1, OC_NSL, 0, OC_GCAP_BIG>, ipm_onchip_kernel<2, OC_NSL, 0, OC_GCAP_BIG>, nullptr, nullptr},
+    {as_onchip_kernel<1, OC_NSL>, as_onchip_kernel<2, OC_NSL>, nullptr, nullptr},
+    {ipm_onchip_kernel<1, OC_NSL>, ipm_onchip_kernel<2, OC_NSL>, nullptr, nullptr}};
 template <int C> void launch_eval(const DevBuf& B, int nblocks, size_t lds, hipStream_t st) { hipLaunchKernelGGL(eval_kernel<C>, dim3(nblocks), dim3(64), lds, st, B); }
 
-void launch_ipm_c(int C, const DevBuf& B, int nblocks, size_t lds, hipStream_t st, bool zero = true) {
-  switch (C) { case 1: launch_ipm<1>(B, nblocks, lds, st, zero); break; case 2: launch_ipm<2>(B, nblocks, lds, st, zero); break;
-               case 3: launch_ipm<3>(B, nblocks, lds, st, zero); break; default: launch_ipm<4>(B, nblocks, lds, st, zero); }
-}
-// interior point solves of the first `bc` batch entries: the on-chip kernel where the shape qualifies, followed by the
-// memory-backed kernel on the nodes it handed over (their count stays on the device: no host round trip); else the
-// memory-backed kernel on everything
-// The rounding probes of the batch (every disjunction fixed: >= 480 general rows, always beyond the on-chip capacity) are known
-// before the launch - their depth word says so - and go to a launch of the memory-backed kernel on a SECOND stream that runs
-// beside the on-chip kernel: that kernel waits on memory for most of its cycles (58 % in s_waitcnt), the on-chip kernel is bound
-// by VALU issue, and the probes no longer cost a generation of their own behind it.  `overlap` false (the polish, solve_fixed): the
-// serial order of round 2.
-// `par` >= 0 (the rounds of a solve): the counters of this launch group are set `par` of X.ctr, zeroed one round ahead by roll_kernel
 // LDS of a larger launch's block beside the standard active-set launch: padded to TWO blocks of that launch (rounded to the allocation granule), as
 // long as four of them still fit a CU.  A larger block leaves a hole behind when it ends; the unpadded 34 KB took one standard block of 19.6 KB and
 // wasted the rest - no CU ever held more than seven of its eight standard blocks again (tools/wave_dump.py, tools/resident_lab.hip)
@@ -708,109 +695,150 @@ inline size_t oc_big_lds_beside_as(const Layout& Y) {
   const size_t two = 2 * ((la + st_ + 1279) / 1280 * 1280) - st_;
   return (two >= lb && 4 * (two + st_) <= 160 * 1024) ? two : lb;
 }
-void launch_ipm_batch(DevCtx& X, const DevBuf& B, int bc, hipStream_t st, bool overlap = false, int par = -1, hipEvent_t ev_std_end = nullptr) {
-  const Layout& Y = X.Y;
+
+// ---------------------------------------------------------------- the node launches of a round: a plan (pure) and its launcher
+// interior point solves of the first `bc` batch entries: the on-chip kernel where the shape qualifies, followed by the
+// memory-backed kernel on the nodes it handed over (their count stays on the device: no host round trip); else the
+// memory-backed kernel on everything.  plan_node_launches decides, run_node_launches issues, launch_ipm_batch is the two together.
+// One launch of a round.  Every field is an int: a row of the plan is what miqp_solver_launch_plan writes out
+enum { Z_WORK = 1, Z_OVF = 2, Z_OVF2 = 4 };           // NodeLaunch::zero: the launch's work counter and hand-over count, on its stream; the larger variant's hand-over count, on
+                                                      // stream 0 ahead of the fork (the launches of every stream append to that list)
+enum { BUF_PRIMARY, BUF_SECOND, BUF_KGAIN3 };         // NodeLaunch::bufs: the batch's per-block buffers, those of the second stream, those with the gain buffer of the fourth
+struct NodeLaunch {
+  int kind, stream, grid, lds;                        // NodeKernel; 0: the caller's stream, 2 .. 4: stream2 .. stream4; workgroups; dynamic LDS bytes
+  int ovf_mode, cls_take, as_split, skip_probes, bounce;   // the DevBuf fields of these names
+  int work;                                           // work counter: > 0 that word of the round's parity set, 0 the batch's own, -1 the second stream's (work_counter2)
+  int from_ovf2;                                      // hand-over count and list it reads: 0 the standard launch's (ovf_count, ovf_list), 1 the larger variant's (ovf2_count, ovf2_list)
+  int bufs, zero;
+};
+static_assert(sizeof(NodeLaunch) == 13 * sizeof(int), "a row of the plan is the 13 ints of include/miqp_gpu.h");
+// the launches of a round in the order they are issued; rebuilt every round (no allocation).  A launch without a workgroup - an empty class list - is not in it
+struct RoundPlan {
+  int n = 0, par = -1;   // par >= 0: the counters of the launches are that parity set of DevCtx::ctr, zeroed one round ahead by roll_kernel (no memset in the stream)
+  NodeLaunch l[5], none;
+  NodeLaunch& add(int kind, int stream, int grid, size_t lds) { NodeLaunch& L = grid > 0 ? l[n++] : none; L = NodeLaunch{kind, stream, grid, (int)lds}; return L; }
+};
+struct PlanCaps { int oc_grid, ocb_grid, probe_grid, ipm_grid_max; bool concurrent_big, as_on, stream2, stream3, stream4, ctr; };   // of the context: capacities, and which streams and counter sets exist
+struct PlanSwitches { int big_grid_cap; double big_w1, big_w2; bool big_pad; int as_chunk, as_quota; };
+
+// Which node kernels run in a round, where and on what: a pure function (no HIP call, no environment).  cls_n: lengths of the round's class lists, [0] < 0: not known
+RoundPlan plan_node_launches(const Layout& Y, const PlanCaps& X, const PlanSwitches& S, const int* cls_n, int bc, bool overlap, int par) {
+  RoundPlan P;
   const size_t l_ipm = ipm_lds_bytes(Y);
-  if (X.oc_grid > 0) {
-    const size_t l_oc = (size_t)oc_lds_layout(Y.N, Y.fixlen).total;
-    const size_t l_ocb = (size_t)oc_lds_layout(Y.N, Y.fixlen, OC_GCAP_BIG).total;
-    const size_t l_ocb_as = as_shape_ok(Y.C, Y.N) && X.sw.big_pad ? oc_big_lds_beside_as(Y) : l_ocb;
-    const bool big = X.ocb_grid > 0;
-    const bool ov = overlap && X.probe_grid > 0 && X.stream2 && bc <= 4096;   // (a full batch keeps the device busy on its own: measured no gain there, 5.4 against 5.1 s on a 2048-instance queue; single solves: median 6.0 instead of 7.0 ms)
-    DevBuf Bc = B;
-    const bool pc = par >= 0 && X.ctr && big && overlap && X.probe_grid > 0 && X.stream2 && X.concurrent_big;
-    if (big && !pc) (void)hipMemsetAsync(B.ovf2_count, 0, 4, st);
-    if (big && overlap && X.probe_grid > 0 && X.stream2 && X.concurrent_big) {
-      // Every round: the larger variant works beside the standard one, on its own stream, through the nodes known to be large
-      // (rounding probes, marked records); behind it, on that stream, the memory-backed kernel takes what even it cannot hold.
-      // Both kernels hand their nodes out dynamically, so the wavefronts of the standard launch that find no room at first start
-      // as the large nodes finish: the tail of the large nodes (40+ iterations) hides behind the standard launch instead of
-      // being a launch of its own.  A node the standard kernel finds too large at its decode is marked and returned unsolved
-      // (bounce): no second launch behind the standard one.
-      (void)hipEventRecord(X.ev_fork, st); (void)hipStreamWaitEvent(X.stream2, X.ev_fork, 0);
-      int* const cs = pc ? X.ctr + CTR_SET * par : nullptr;   // [0] batch count, [1] standard launch, [2] its hand-over list, [3] the larger variant's list, [4] the larger variant, [5] the memory-backed launch behind it
-      if (pc) { Bc.work_counter = cs + 1; Bc.ovf_count = cs + 2; Bc.ovf2_count = cs + 3; }
-      DevBuf Bp = Bc; Bp.ovf_mode = 2; Bp.work_counter = pc ? cs + 4 : X.work_counter2; Bp.rowstate = X.rowstate2; Bp.rowcache = X.rowcache2; Bp.kgain = X.kgain2;
-      const ProcessSwitches& ps = process_switches();
-      const int gb = std::min(std::min(bc, ps.big_grid_cap), std::min(X.probe_grid, X.ocb_grid));
-      const bool as2 = X.as_on && pc && X.stream3;   // (as_on: the shape has the launches - as_shape_ok - and the call has not switched them off)
-      const bool lists = as2 && X.stream4 && B.cls_list && X.cls_n[0] >= 0;
-      // With the class lists the larger launches get the SHARE of the device their work is of the round's, not all of it: their wavefronts take a SIMD
-      // each (450 / 424 registers) and are enqueued first - a full grid of them held every SIMD until the larger active-set launch was through
-      // (5 of 16 ms, tools/wave_dump.py), the standard launch started behind them and never got its holes back.  Weights: SIMD time of a node of the
-      // class in units of a standard node's (half a SIMD for ~0.19 ms)
-      const double w1_ = ps.big_w1, w2_ = ps.big_w2;
-      int g1s = gb, g2s = gb;
-      if (lists && w1_ > 0) {
-        const double n1 = X.cls_n[0], n2 = X.cls_n[1], n0 = std::max(0, bc - X.cls_n[0] - X.cls_n[1] - X.cls_n[2]);
-        const double den = w1_ * n1 + w2_ * n2 + n0 + 1.0;
-        g1s = std::max(32, (int)(gb * w1_ * n1 / den + 0.5)); g2s = std::max(32, (int)(gb * w2_ * n2 / den + 0.5));
-      }
-      if (as2) {
-        // the large nodes of the round that the active-set method takes (large_class 1): its larger block, on a third stream beside the interior
-        // point chain, which keeps the rest of them
-        (void)hipStreamWaitEvent(X.stream3, X.ev_fork, 0);
-        DevBuf Bq = Bp; Bq.work_counter = cs + 6;
-        if (lists) Bq.cls_take = 1;
-        const int g1 = lists ? std::min(std::min(gb, g1s), X.cls_n[0]) : gb;   // (with the class lists: as many workgroups as the class has nodes, none when it is empty)
-        if (g1 > 0) hipLaunchKernelGGL((Y.C == 1 ? as_onchip_kernel<1, OC_NSL, OC_GCAP_BIG> : as_onchip_kernel<2, OC_NSL, OC_GCAP_BIG>), dim3(g1), dim3(64), l_ocb_as, X.stream3, Bq);
-        (void)hipEventRecord(X.ev_join3, X.stream3);
-        Bp.as_split = 1;
-      }
-      if (lists) { Bp.cls_take = 2; const int g2 = std::min(std::min(gb, g2s), X.cls_n[1]); if (g2 > 0) { if (Y.C == 1) launch_ipm_oc_big<1>(Bp, g2, l_ocb_as, X.stream2, false); else launch_ipm_oc_big<2>(Bp, g2, l_ocb_as, X.stream2, false); } Bp.cls_take = 0; }
-      else
-      if (Y.C == 1) launch_ipm_oc_big<1>(Bp, gb, l_ocb, X.stream2, !pc); else launch_ipm_oc_big<2>(Bp, gb, l_ocb, X.stream2, !pc);
-      DevBuf Bm = Bp; Bm.ovf_mode = 1; Bm.ovf_count = Bc.ovf2_count; Bm.ovf_list = B.ovf2_list; if (pc) Bm.work_counter = cs + 5;
-      if (as2 && X.stream4) {   // the records known to exceed the larger block: the memory-backed kernel beside the three others, on a fourth stream (gain buffer of its own)
-        (void)hipStreamWaitEvent(X.stream4, X.ev_fork, 0);
-        Bm.ovf_mode = 3; Bm.kgain = X.kgain3;
-        if (lists) { Bm.cls_take = 3; const int g3 = std::min(X.probe_grid, X.cls_n[2]); if (g3 > 0) launch_ipm_c(Y.C, Bm, g3, l_ipm, X.stream4, false); }
-        else
-        launch_ipm_c(Y.C, Bm, std::min(bc, X.probe_grid), l_ipm, X.stream4, !pc);
-        (void)hipEventRecord(X.ev_join4, X.stream4);
-      } else
-      launch_ipm_c(Y.C, Bm, std::min(bc, X.probe_grid), l_ipm, X.stream2, !pc);
-      (void)hipEventRecord(X.ev_join, X.stream2);
-      Bc.skip_probes = 1; Bc.bounce = 1;
-      if (X.as_on && pc) {
-        // the ordinary nodes of the round: dual active-set solves (as_onchip.hip) in place of the standard interior point launch; a node that
-        // launch cannot finish comes back marked, like a node that is too large, and the larger interior point variant takes it next round
-        DevBuf Ba = Bc; Ba.work_counter = cs + 1;
-        const size_t l_as = (size_t)oc_lds_layout(Y.N, Y.fixlen, OC_GCAP, true).total;
-        const int ch_ = std::max(1, Ba.as_chunk);
-        const int ga = Ba.as_quota > 0 ? std::max(1, (bc + Ba.as_quota * ch_ - 1) / (Ba.as_quota * ch_)) : std::min(bc, X.oc_grid);
-        hipLaunchKernelGGL((Y.C == 1 ? as_onchip_kernel<1, OC_NSL> : as_onchip_kernel<2, OC_NSL>), dim3(ga), dim3(64), l_as, st, Ba);
-      } else if (Y.C == 1) launch_ipm_oc<1>(Bc, std::min(bc, X.oc_grid), l_oc, st, !pc); else launch_ipm_oc<2>(Bc, std::min(bc, X.oc_grid), l_oc, st, !pc);
-      if (X.ev_mid) (void)hipEventRecord(X.ev_mid, st);
-      if (ev_std_end) (void)hipEventRecord(ev_std_end, st);   // (where the standard launch of the round ends: the dominant kernel's own time)
-      (void)hipStreamWaitEvent(st, X.ev_join, 0);
-      if (as2) (void)hipStreamWaitEvent(st, X.ev_join3, 0);
-      if (as2 && X.stream4) (void)hipStreamWaitEvent(st, X.ev_join4, 0);
-      return;
+  // ---- no on-chip kernel for the shape: the memory-backed kernel on everything
+  if (X.oc_grid <= 0) { P.add(NK_IPM, 0, std::min(bc, X.ipm_grid_max), l_ipm).zero = Z_WORK; return P; }
+  const size_t l_oc = (size_t)oc_lds_layout(Y.N, Y.fixlen).total, l_ocb = (size_t)oc_lds_layout(Y.N, Y.fixlen, OC_GCAP_BIG).total;
+  const size_t l_ocb_as = as_shape_ok(Y.C, Y.N) && S.big_pad ? oc_big_lds_beside_as(Y) : l_ocb;
+  const bool big = X.ocb_grid > 0, aside = overlap && X.probe_grid > 0 && X.stream2, conc = big && aside && X.concurrent_big, pc = par >= 0 && X.ctr && conc;
+  if (pc) P.par = par;
+  if (conc) {
+    // ---- the concurrent round
+    // Every round: the larger variant works beside the standard one, on its own stream, through the nodes known to be large
+    // (rounding probes, marked records); behind it, on that stream, the memory-backed kernel takes what even it cannot hold.
+    // Both kernels hand their nodes out dynamically, so the wavefronts of the standard launch that find no room at first start
+    // as the large nodes finish: the tail of the large nodes (40+ iterations) hides behind the standard launch instead of
+    // being a launch of its own.  A node the standard kernel finds too large at its decode is marked and returned unsolved
+    // (bounce): no second launch behind the standard one.
+    // Words of the parity set: [0] batch count, [1] standard launch, [2] its hand-over list, [3] the larger variant's list, [4] the larger variant, [5] the
+    // memory-backed launch behind it, [6] the larger active-set launch.  Without the set (!pc) every launch has its counters zeroed by memsets; the
+    // class lists come with the set, so a launch that takes a list never has one
+    const int zw = pc ? 0 : Z_WORK;
+    const int gb = std::min(std::min(bc, S.big_grid_cap), std::min(X.probe_grid, X.ocb_grid));
+    const bool as2 = X.as_on && pc && X.stream3;   // (as_on: the shape has the launches - as_shape_ok - and the call has not switched them off)
+    const bool lists = as2 && X.stream4 && cls_n[0] >= 0;
+    // With the class lists the larger launches get the SHARE of the device their work is of the round's, not all of it: their wavefronts take a SIMD
+    // each (450 / 424 registers) and are enqueued first - a full grid of them held every SIMD until the larger active-set launch was through
+    // (5 of 16 ms, tools/wave_dump.py), the standard launch started behind them and never got its holes back.  Weights: SIMD time of a node of the
+    // class in units of a standard node's (half a SIMD for ~0.19 ms)
+    int g1s = gb, g2s = gb;
+    if (lists && S.big_w1 > 0) {
+      const double n1 = cls_n[0], n2 = cls_n[1], n0 = std::max(0, bc - cls_n[0] - cls_n[1] - cls_n[2]);
+      const double den = S.big_w1 * n1 + S.big_w2 * n2 + n0 + 1.0;
+      g1s = std::max(32, (int)(gb * S.big_w1 * n1 / den + 0.5)); g2s = std::max(32, (int)(gb * S.big_w2 * n2 / den + 0.5));
     }
-    if (ov) {
-      (void)hipEventRecord(X.ev_fork, st); (void)hipStreamWaitEvent(X.stream2, X.ev_fork, 0);
-      DevBuf Bp = B; Bp.ovf_mode = 2; Bp.work_counter = X.work_counter2; Bp.rowstate = X.rowstate2; Bp.rowcache = X.rowcache2; Bp.kgain = X.kgain2;
-      if (big) { if (Y.C == 1) launch_ipm_oc_big<1>(Bp, std::min(bc, std::min(X.probe_grid, X.ocb_grid)), l_ocb, X.stream2); else launch_ipm_oc_big<2>(Bp, std::min(bc, std::min(X.probe_grid, X.ocb_grid)), l_ocb, X.stream2); }
-      else launch_ipm_c(Y.C, Bp, std::min(bc, X.probe_grid), l_ipm, X.stream2);
-      (void)hipEventRecord(X.ev_join, X.stream2);
-      Bc.skip_probes = 1;
+    if (as2) {
+      // the large nodes of the round that the active-set method takes (large_class 1): its larger block, on a third stream beside the interior
+      // point chain, which keeps the rest of them.  (With the class lists: as many workgroups as the class has nodes, none when it is empty.)  Its
+      // LDS is that of a block beside the standard active-set launch with and without the lists
+      NodeLaunch& L = P.add(NK_AS_BIG, 3, lists ? std::min(std::min(gb, g1s), cls_n[0]) : gb, l_ocb_as);
+      L.ovf_mode = 2; L.cls_take = lists ? 1 : 0; L.work = 6; L.bufs = BUF_SECOND;
     }
-    if (Y.C == 1) launch_ipm_oc<1>(Bc, std::min(bc, X.oc_grid), l_oc, st); else launch_ipm_oc<2>(Bc, std::min(bc, X.oc_grid), l_oc, st);
-    if (X.ev_mid) (void)hipEventRecord(X.ev_mid, st);   // (diagnostic, MIQP_LAUNCH_TRACE: where the on-chip kernel ends)
-    if (ov) (void)hipStreamWaitEvent(st, X.ev_join, 0);   // (the launches below and the evaluation need the probes' results)
-    DevBuf Bo = B; Bo.ovf_mode = 1;
-    if (big) {
-      // the nodes the standard variant could not hold go to the larger one (up to OC_GCAP_BIG general rows: the rounding probes
-      // without their slack front-point rows, the other large nodes); what even that one cannot hold - the polish of an
-      // incumbent, every row of it - to the memory-backed kernel
-      if (Y.C == 1) launch_ipm_oc_big<1>(Bo, std::min(bc, X.ocb_grid), l_ocb, st); else launch_ipm_oc_big<2>(Bo, std::min(bc, X.ocb_grid), l_ocb, st);
-      Bo.ovf_count = B.ovf2_count; Bo.ovf_list = B.ovf2_list;
+    { // the larger interior point variant, on the second stream; padded like the launch above only when it takes its class's list
+      NodeLaunch& L = P.add(NK_OC_BIG, 2, lists ? std::min(std::min(gb, g2s), cls_n[1]) : gb, lists ? l_ocb_as : l_ocb);
+      L.ovf_mode = 2; L.cls_take = lists ? 2 : 0; L.as_split = as2; L.work = pc ? 4 : -1; L.bufs = BUF_SECOND; L.zero = zw;
     }
-    launch_ipm_c(Y.C, Bo, std::min(bc, X.ipm_grid_max), l_ipm, st);   // blocks without a node read the count and leave
+    { // the memory-backed kernel on the larger variant's list: behind it on the second stream or, beside the larger active-set launch and where a
+      // fourth stream exists, on that one - the records known to exceed the larger block, beside the three others (gain buffer of its own)
+      const bool own = as2 && X.stream4;
+      NodeLaunch& L = P.add(NK_IPM, own ? 4 : 2, lists ? std::min(X.probe_grid, cls_n[2]) : std::min(bc, X.probe_grid), l_ipm);
+      L.ovf_mode = own ? 3 : 1; L.cls_take = lists ? 3 : 0; L.as_split = as2; L.from_ovf2 = 1; L.work = pc ? 5 : -1; L.bufs = own ? BUF_KGAIN3 : BUF_SECOND; L.zero = zw;
+    }
+    { // the ordinary nodes of the round: dual active-set solves (as_onchip.hip) in place of the standard interior point launch; a node that
+      // launch cannot finish comes back marked, like a node that is too large, and the larger interior point variant takes it next round
+      const bool as = X.as_on && pc; const int run = S.as_quota * std::max(1, S.as_chunk);   // (nodes a wavefront of the launch takes before it leaves; 0: it stays)
+      NodeLaunch& L = as ? P.add(NK_AS, 0, run > 0 ? std::max(1, (bc + run - 1) / run) : std::min(bc, X.oc_grid), (size_t)oc_lds_layout(Y.N, Y.fixlen, OC_GCAP, true).total)
+                         : P.add(NK_OC, 0, std::min(bc, X.oc_grid), l_oc);
+      L.skip_probes = 1; L.bounce = 1; L.work = pc ? 1 : 0; L.zero = pc ? 0 : Z_WORK | Z_OVF;
+    }
   } else {
-    launch_ipm_c(Y.C, B, std::min(bc, X.ipm_grid_max), l_ipm, st);
+    // ---- the serial chain (`overlap` false: the polish, solve_fixed, the fixed batch, the replays), with the probe overlap in front of it in a round
+    // The rounding probes of the batch (every disjunction fixed: >= 480 general rows, always beyond the on-chip capacity) are known
+    // before the launch - their depth word says so - and go to a launch of their own on a SECOND stream that runs
+    // beside the on-chip kernel: that kernel waits on memory for most of its cycles (58 % in s_waitcnt), the on-chip kernel is bound
+    // by VALU issue, and the probes no longer cost a generation of their own behind it.
+    const bool ov = aside && bc <= 4096;   // (a full batch keeps the device busy on its own: measured no gain there, 5.4 against 5.1 s on a 2048-instance queue; single solves: median 6.0 instead of 7.0 ms)
+    if (ov) {
+      NodeLaunch& L = big ? P.add(NK_OC_BIG, 2, std::min(bc, std::min(X.probe_grid, X.ocb_grid)), l_ocb) : P.add(NK_IPM, 2, std::min(bc, X.probe_grid), l_ipm);
+      L.ovf_mode = 2; L.work = -1; L.bufs = BUF_SECOND; L.zero = Z_WORK;
+    }
+    { NodeLaunch& L = P.add(NK_OC, 0, std::min(bc, X.oc_grid), l_oc); L.skip_probes = ov; L.zero = Z_WORK | Z_OVF; }
+    // the nodes the standard variant could not hold go to the larger one (up to OC_GCAP_BIG general rows: the rounding probes
+    // without their slack front-point rows, the other large nodes); what even that one cannot hold - the polish of an
+    // incumbent, every row of it - to the memory-backed kernel
+    if (big) { NodeLaunch& L = P.add(NK_OC_BIG, 0, std::min(bc, X.ocb_grid), l_ocb); L.ovf_mode = 1; L.zero = Z_WORK; }
+    { NodeLaunch& L = P.add(NK_IPM, 0, std::min(bc, X.ipm_grid_max), l_ipm); L.ovf_mode = 1; L.from_ovf2 = big; L.zero = Z_WORK; }   // blocks without a node read the count and leave
   }
+  if (big && !pc && P.n > 0) P.l[0].zero |= Z_OVF2;
+  return P;
+}
+
+// Issues a plan: every launch starts from the caller's B and gets its own fields, nothing of another launch's.  A stream beside the caller's waits for the
+// fork event before its first launch and records its join event behind its last one; the caller's stream waits for those behind the standard
+// launch (the launches below it in a serial chain and the evaluation need the results)
+void run_node_launches(DevCtx& X, const DevBuf& B, const RoundPlan& P, hipStream_t st, hipEvent_t ev_std_end) {
+  const hipStream_t stream[5] = {st, nullptr, X.stream2, X.stream3, X.stream4};
+  const hipEvent_t join[5] = {nullptr, nullptr, X.ev_join, X.ev_join3, X.ev_join4};
+  int* const cs = P.par >= 0 ? X.ctr + CTR_SET * P.par : nullptr;
+  int last[5] = {-1, -1, -1, -1, -1};
+  for (int i = 0; i < P.n; ++i) { last[P.l[i].stream] = i; if (P.l[i].zero & Z_OVF2) (void)hipMemsetAsync(B.ovf2_count, 0, 4, st); }
+  if (last[2] >= 0 || last[3] >= 0 || last[4] >= 0) (void)hipEventRecord(X.ev_fork, st);
+  for (int k = 2; k < 5; ++k) if (last[k] >= 0) (void)hipStreamWaitEvent(stream[k], X.ev_fork, 0);
+  for (int i = 0; i < P.n; ++i) {
+    const NodeLaunch& L = P.l[i]; const hipStream_t s = stream[L.stream];
+    DevBuf Bl = B;
+    Bl.ovf_mode = L.ovf_mode; Bl.cls_take = L.cls_take; Bl.as_split = L.as_split; Bl.skip_probes = L.skip_probes; Bl.bounce = L.bounce;
+    if (cs) { Bl.ovf_count = cs + 2; Bl.ovf2_count = cs + 3; }
+    Bl.work_counter = L.work > 0 ? cs + L.work : L.work < 0 ? X.work_counter2 : B.work_counter;
+    if (L.from_ovf2) { Bl.ovf_count = Bl.ovf2_count; Bl.ovf_list = B.ovf2_list; }
+    if (L.bufs != BUF_PRIMARY) { Bl.rowstate = X.rowstate2; Bl.rowcache = X.rowcache2; Bl.kgain = L.bufs == BUF_KGAIN3 ? X.kgain3 : X.kgain2; }
+    if (L.zero & Z_WORK) (void)hipMemsetAsync(Bl.work_counter, 0, 4, s);
+    if (L.zero & Z_OVF) (void)hipMemsetAsync(Bl.ovf_count, 0, 4, s);
+    hipLaunchKernelGGL(NODE_KERNEL[L.kind][X.Y.C - 1], dim3(L.grid), dim3(L.kind == NK_IPM ? ipm_nt(X.Y.C) : 64), (size_t)L.lds, s, Bl);
+    if (L.stream != 0 && last[L.stream] == i) (void)hipEventRecord(join[L.stream], s);
+    if (L.kind == NK_OC || L.kind == NK_AS) {
+      if (X.ev_mid) (void)hipEventRecord(X.ev_mid, st);       // (diagnostic, MIQP_LAUNCH_TRACE: where the standard launch ends)
+      if (ev_std_end) (void)hipEventRecord(ev_std_end, st);   // (where the standard launch of the round ends: the dominant kernel's own time)
+      for (int k = 2; k < 5; ++k) if (last[k] >= 0) (void)hipStreamWaitEvent(st, join[k], 0);
+    }
+  }
+}
+
+void launch_ipm_batch(DevCtx& X, const DevBuf& B, int bc, hipStream_t st, bool overlap = false, int par = -1, hipEvent_t ev_std_end = nullptr) {
+  static const int unknown[3] = {-1, -1, -1};
+  const ProcessSwitches& ps = process_switches();
+  const PlanCaps caps = {X.oc_grid, X.ocb_grid, X.probe_grid, X.ipm_grid_max, X.concurrent_big, X.as_on, X.stream2 != nullptr, X.stream3 != nullptr, X.stream4 != nullptr, X.ctr != nullptr};
+  const PlanSwitches sw = {ps.big_grid_cap, ps.big_w1, ps.big_w2, X.sw.big_pad, B.as_chunk, B.as_quota};
+  run_node_launches(X, B, plan_node_launches(X.Y, caps, sw, B.cls_list ? X.cls_n : unknown, bc, overlap, par), st, ev_std_end);
 }
 
 void launch_eval_c(int C, const DevBuf& B, int nblocks, size_t lds, hipStream_t st) {
@@ -818,25 +846,14 @@ void launch_eval_c(int C, const DevBuf& B, int nblocks, size_t lds, hipStream_t 
                case 3: launch_eval<3>(B, nblocks, lds, st); break; default: launch_eval<4>(B, nblocks, lds, st); }
 }
 
-template <int C> bool set_kernel_lds_oc(size_t lds, size_t lds_big) {
-  HIP_OK(hipFuncSetAttribute((const void*)ipm_onchip_kernel<C, OC_NSL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  HIP_OK(hipFuncSetAttribute((const void*)ipm_onchip_kernel<C, OC_NSL, 0, OC_GCAP_BIG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_big));
-  if constexpr (as_shape_ok(C, 2 * OC_NSL)) { HIP_OK(hipFuncSetAttribute((const void*)as_onchip_kernel<C, OC_NSL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    HIP_OK(hipFuncSetAttribute((const void*)as_onchip_kernel<C, OC_NSL, OC_GCAP_BIG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_big)); }
-  return true;
-}
-template <int C> bool set_kernel_lds_c(size_t ipm_lds, size_t eval_lds) {
-  HIP_OK(hipFuncSetAttribute((const void*)ipm_kernel<C, ipm_nt(C)>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ipm_lds));
-  HIP_OK(hipFuncSetAttribute((const void*)eval_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)eval_lds));
-  return true;
-}
 bool set_kernel_lds(const Layout& Y, size_t ipm_lds, size_t eval_lds) {
+  const auto set = [](NodeKernelFn k, size_t lds) { HIP_OK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); return true; };
   if (Y.C <= 2 && Y.N <= 2 * OC_NSL) {
     const size_t l = (size_t)oc_lds_layout(Y.N, Y.fixlen).total, lb = std::max((size_t)oc_lds_layout(Y.N, Y.fixlen, OC_GCAP_BIG).total, as_shape_ok(Y.C, Y.N) ? oc_big_lds_beside_as(Y) : (size_t)0);
-    if (l <= 160 * 1024 && !(Y.C == 1 ? set_kernel_lds_oc<1>(l, lb) : set_kernel_lds_oc<2>(l, lb))) return false;
+    if (l <= 160 * 1024) for (int k = NK_AS_BIG; k <= NK_OC; ++k) if (!set(NODE_KERNEL[k][Y.C - 1], k == NK_OC_BIG || k == NK_AS_BIG ? lb : l)) return false;
   }
-  switch (Y.C) { case 1: return set_kernel_lds_c<1>(ipm_lds, eval_lds); case 2: return set_kernel_lds_c<2>(ipm_lds, eval_lds);
-                 case 3: return set_kernel_lds_c<3>(ipm_lds, eval_lds); default: return set_kernel_lds_c<4>(ipm_lds, eval_lds); }
+  const NodeKernelFn eval[4] = {eval_kernel<1>, eval_kernel<2>, eval_kernel<3>, eval_kernel<4>};
+  return set(NODE_KERNEL[NK_IPM][std::min(Y.C, 4) - 1], ipm_lds) && set(eval[std::min(Y.C, 4) - 1], eval_lds);
 }
 
 // ---------------------------------------------------------------- results (collectRawResults, cplex_wrapper.cpp:311-448)
@@ -1980,6 +1997,22 @@ int miqp_solver_last_active_set(const miqp_solver_t* s, double* out8) {
 int miqp_solver_last_fixed_route(const miqp_solver_t* s) { return s ? s->fixed_route : -1; }
 
 int miqp_gpu_has_active_set(int num_cars, int num_steps) { return miqp::as_shape_ok(num_cars, num_steps) ? 1 : 0; }
+
+int miqp_solver_launch_plan(const miqp_solver_t* s, int bc, int overlap, int par, const int* cls_n3, int cus, double free_gb, int flags, int* out, int cap) {
+  if (!s || !s->has_inst || !cls_n3 || !out || bc < 1 || cus < 1 || free_gb <= 0) return -1;
+  miqp_solver_t* one[1] = {const_cast<miqp_solver_t*>(s)};
+  const BatchShape bs = batch_layout(one, 1);
+  if (!bs.ok) return -2;
+  const CallSwitches sw = read_call_switches(); const CtxSwitches cs = read_ctx_switches(); const ProcessSwitches& ps = process_switches();
+  const CallShape sh = plan_call(bs.Y, s->opts, 1, 0, 1, false, sw);
+  const CtxSizes Z = ctx_sizes(bs.Y, 1, sh.NS, sh.open_cap, sh.npr, sh.MAXR, sh.clamp_open, 1, true, (size_t)(free_gb * 1073741824.0), cus, cs);
+  const PlanCaps caps = {Z.oc_grid, Z.ocb_grid, Z.probe_grid, Z.ipm_grid_max, Z.concurrent_big && !(flags & 2), Z.as_cap && (flags & 1), true, true, true, true};
+  const PlanSwitches psw = {ps.big_grid_cap, ps.big_w1, ps.big_w2, sw.big_pad, cs.as_chunk, cs.as_quota};
+  const RoundPlan P = plan_node_launches(bs.Y, caps, psw, cls_n3, bc, overlap != 0, par);
+  if ((size_t)cap * sizeof(int) < (size_t)P.n * sizeof(NodeLaunch)) return -3;
+  std::memcpy(out, P.l, (size_t)P.n * sizeof(NodeLaunch));
+  return P.n;
+}
 
 int miqp_solver_last_setup(const miqp_solver_t* s, double* out3) {
   if (!s || !out3) return -1;

@@ -92,6 +92,8 @@ def load_library():
     L.miqp_gpu_certificate_size.restype = C.c_int; L.miqp_gpu_certificate_size.argtypes = []
     L.miqp_gpu_certify_last_timing.restype = C.c_int; L.miqp_gpu_certify_last_timing.argtypes = [C.POINTER(C.c_double)]
     L.miqp_gpu_has_active_set.restype = C.c_int; L.miqp_gpu_has_active_set.argtypes = [C.c_int, C.c_int]
+    L.miqp_solver_launch_plan.restype = C.c_int
+    L.miqp_solver_launch_plan.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_double, C.c_int, C.POINTER(C.c_int), C.c_int]
     L.miqp_solver_solve_fixed_batch.restype = C.c_int
     L.miqp_solver_solve_fixed_batch.argtypes = [vp, C.POINTER(C.POINTER(RawResultsC)), C.c_int, C.POINTER(FixedResultC), C.POINTER(C.c_int)]
     L.miqp_solver_fixed_batch_record.restype = C.c_int; L.miqp_solver_fixed_batch_record.argtypes = [vp, C.c_int, C.POINTER(RawResultsC)]
@@ -124,9 +126,13 @@ EXPORTED_SYMBOLS = ["miqp_solver_create", "miqp_solver_destroy", "miqp_solver_se
                     "miqp_comm_init", "miqp_comm_finalize", "miqp_comm_selftest", "miqp_solver_solve_stream", "miqp_solver_materialize_results",
                     "miqp_initial_pose_check", "miqp_select_environment", "miqp_obstacle_intersects_environment", "miqp_obstacles_roi", "miqp_bark_trajectory", "miqp_obstacle_intersects_environment_roi", "miqp_environment_warmstart",
                     "miqp_solver_certify", "miqp_solver_certify_batch", "miqp_gpu_certificate_size", "miqp_gpu_certify_last_timing",
-                    "miqp_gpu_has_active_set", "miqp_solver_last_fixed_route",
+                    "miqp_gpu_has_active_set", "miqp_solver_last_fixed_route", "miqp_solver_launch_plan",
                     "miqp_solver_solve_fixed_batch", "miqp_solver_fixed_batch_record", "miqp_gpu_fixed_result_size", "miqp_gpu_fixed_batch_chunk",
                     "miqp_solver_set_pool", "miqp_solver_pool_count", "miqp_solver_pool_found", "miqp_solver_pool_solve", "miqp_solver_pool_record", "miqp_gpu_pool_max"]
+
+
+# a row of CplexWrapper.launchPlan (NodeLaunch in csrc/miqp_gpu.hip)
+LAUNCH_PLAN_FIELDS = ("kernel", "stream", "grid", "lds", "ovf_mode", "cls_take", "as_split", "skip_probes", "bounce", "work", "from_ovf2", "bufs", "zero")
 
 
 def pool_max():
@@ -406,6 +412,19 @@ class CplexWrapper:
         """which launch solved the node of the last solveFixed(): 0 the standard on-chip kernel, 1 its larger variant, 2 the
         memory-backed kernel behind them, 3 the memory-backed kernel of a shape without an on-chip kernel; -1 before any"""
         return int(self._L.miqp_solver_last_fixed_route(self._h))
+
+    def launchPlan(self, bc, overlap=0, par=-1, cls_n=(-1, -1, -1), cus=256, free_gb=256.0, as_on=1, concurrent=True):
+        """the node launches of a round of ``bc`` nodes (``overlap`` 1, ``par`` the round's parity) or of the serial chain (``overlap`` 0), one tuple
+        of LAUNCH_PLAN_FIELDS per launch in the order of issue (miqp_solver_launch_plan, include/miqp_gpu.h).  Host code; needs no device."""
+        if self._push_inputs() != 0:
+            return None
+        out = (C.c_int * (5 * len(LAUNCH_PLAN_FIELDS)))()
+        n = self._L.miqp_solver_launch_plan(self._h, int(bc), int(overlap), int(par), (C.c_int * 3)(*cls_n), int(cus), float(free_gb),
+                                            (1 if as_on else 0) | (0 if concurrent else 2), out, len(out))
+        if n < 0:
+            raise RuntimeError("miqp_solver_launch_plan failed (%d)" % n)
+        k = len(LAUNCH_PLAN_FIELDS)
+        return [tuple(out[i * k:(i + 1) * k]) for i in range(n)]
 
     def solveFixedBatch(self, records):
         """the continuous QPs of many records of this wrapper's instance in one device call (miqp_solver_solve_fixed_batch): each entry is

@@ -40,5 +40,9 @@ def test_one_predicate_decides_every_site_of_the_host_code():
     assert src.count("as_shape_ok(") >= 5
     kern = open(os.path.join(ROOT, "planner_miqp_amd", "csrc", "as_onchip.hip")).read()
     assert len(re.findall(r"constexpr bool as_shape_ok\(int C, int N\)", kern)) == 1
+    # the four instantiations of the active-set kernel are named in the kernel table, which the launcher and set_kernel_lds read, and nowhere else
+    table = src[src.index("const NodeKernelFn NODE_KERNEL["):]
+    table = table[:table.index("};")]
     for c in (1, 2):
-        assert "as_onchip_kernel<%d, OC_NSL>" % c in src and "as_onchip_kernel<%d, OC_NSL, OC_GCAP_BIG>" % c in src
+        for spelling in ("as_onchip_kernel<%d, OC_NSL>" % c, "as_onchip_kernel<%d, OC_NSL, OC_GCAP_BIG>" % c):
+            assert spelling in table and src.count(spelling) == 1, spelling
