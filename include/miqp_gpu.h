@@ -260,6 +260,32 @@ int miqp_solver_pool_record(miqp_solver_t* s, int k, miqp_raw_results_c* out);
 /* largest capacity miqp_solver_set_pool accepts: a constant of the build (no device is needed or touched) */
 int miqp_gpu_pool_max(void);
 
+/* ---- fix records and solution pools of MANY handles in one device call: one device lock, one context, the n instances compiled on host threads and
+ * their tables uploaded once, the nodes of all handles in common launch groups of miqp_gpu_fixed_batch_chunk nodes. ----
+ * miqp_solver_solve_fixed_multi: entries first[h] .. first[h + 1] - 1 of fixed[] are fix records of the instance loaded in solvers[h] (first has n + 1
+ * entries, ascending, first[0] == 0; an empty range is allowed).  For every handle the call answers what miqp_solver_solve_fixed_batch(solvers[h], ...)
+ * answers for that handle's records alone, bit for bit: out[first[h] + k] per entry, best[h] (may be NULL) = index INSIDE the handle's range of its
+ * feasible entry with the lowest objective, ties to the lower index, -1 when none is feasible; and every handle keeps what the single call leaves
+ * for miqp_solver_fixed_batch_record (a handle with an empty range keeps nothing).  The context has the common Layout of the handles; a node gives
+ * the same bits under it as under its own instance's.
+ * Returns 0; -1 invalid arguments (NULL arrays, n <= 0, a handle without an instance, a handle named twice, a `first` that does not ascend from 0);
+ * -2 handles that do not share a shape (as miqp_solver_solve_batch refuses them; miqp_solver_last_error says why) or name different devices;
+ * -5 more than 65536 entries in all; -3 no device / kernel image / HIP error (every entry then has status 2: not run).  -1, -2 and -5 are found
+ * before any device is touched and leave what the handles keep alone; a call with nothing to run returns 0 without touching a device.
+ * A refused ENTRY - NULL record, NULL array in it, sizes that differ from its handle's instance - is status 2 of that entry and does not fail the call.
+ * miqp_solver_last_timing of every handle of the call then reports out[0] = the whole call, out[1] = of which on the device, out[2] = launch groups
+ * (all three of the CALL), out[3] = the handle's own entries run, out[4] = their iterations.  No reference counterpart. */
+int miqp_solver_solve_fixed_multi(miqp_solver_t* const* solvers, int n, const miqp_raw_results_c* const* fixed, const int* first, miqp_fixed_result_c* out, int* best);
+/* refines the pools of n handles as miqp_solver_pool_solve refines one - the re-labelling passes, the merge of entries that end with the same
+ * binaries, miqp_solver_pool_count and what miqp_solver_pool_record hands out afterwards are those of the single call, bit for bit - with the entries
+ * of all handles as nodes of common launch groups; a pass re-runs only the entries of handles whose labels moved.  out[h * cap + k], k < counts[h],
+ * receives the entries left of handle h (at most min(count, cap) are refined, cap >= 1); a handle with an empty pool gets counts[h] = 0 and nothing written.
+ * Returns the total number of entries left (0: no handle kept anything - no device is touched then), -1 / -2 / -5 / -3 as
+ * miqp_solver_solve_fixed_multi.  miqp_solver_last_timing of every handle: out[0], out[1] of the call, out[2] = passes the handle's entries took,
+ * out[3] = its entries left, out[4] = their iterations, out[5] = 1 when the handle's labels still moved after the last pass (miqp_solver_last_error of
+ * that handle says so), else 0.  No reference counterpart. */
+int miqp_solver_pool_solve_multi(miqp_solver_t* const* solvers, int n, miqp_fixed_result_c* out, int cap, int* counts);
+
 /* 1 when instances of this shape (NrCars, N) have the dual active-set launches - one or two cars, a horizon of up to 20 steps - else 0 (their node
  * relaxations are interior point solves).  Pure host code: no device is needed or touched.  A call switches the launches off with MIQP_AS=0 */
 int miqp_gpu_has_active_set(int num_cars, int num_steps);

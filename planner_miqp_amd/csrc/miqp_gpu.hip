@@ -1680,6 +1680,7 @@ bool solve_batch_impl(miqp_solver_t* const* S, int n, int* statuses, const Split
 #include "certify.hip"
 #include "fixed_batch.hip"
 #include "solution_pool.hip"
+#include "fixed_multi.hip"
 
 // ================================================================================================
 //  C ABI

@@ -105,6 +105,10 @@ def load_library():
     L.miqp_solver_pool_solve.restype = C.c_int; L.miqp_solver_pool_solve.argtypes = [vp, C.POINTER(FixedResultC), C.c_int]
     L.miqp_solver_pool_record.restype = C.c_int; L.miqp_solver_pool_record.argtypes = [vp, C.c_int, C.POINTER(RawResultsC)]
     L.miqp_gpu_pool_max.restype = C.c_int; L.miqp_gpu_pool_max.argtypes = []
+    L.miqp_solver_solve_fixed_multi.restype = C.c_int
+    L.miqp_solver_solve_fixed_multi.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(C.POINTER(RawResultsC)), C.POINTER(C.c_int), C.POINTER(FixedResultC), C.POINTER(C.c_int)]
+    L.miqp_solver_pool_solve_multi.restype = C.c_int
+    L.miqp_solver_pool_solve_multi.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(FixedResultC), C.c_int, C.POINTER(C.c_int)]
     if L.miqp_gpu_fixed_result_size() != C.sizeof(FixedResultC):
         raise RuntimeError("libmiqp_gpu.so and ctypes_types.FixedResultC disagree on miqp_fixed_result_c (%d / %d bytes): rebuild the library"
                            % (L.miqp_gpu_fixed_result_size(), C.sizeof(FixedResultC)))
@@ -128,11 +132,16 @@ EXPORTED_SYMBOLS = ["miqp_solver_create", "miqp_solver_destroy", "miqp_solver_se
                     "miqp_solver_certify", "miqp_solver_certify_batch", "miqp_gpu_certificate_size", "miqp_gpu_certify_last_timing",
                     "miqp_gpu_has_active_set", "miqp_solver_last_fixed_route", "miqp_solver_launch_plan",
                     "miqp_solver_solve_fixed_batch", "miqp_solver_fixed_batch_record", "miqp_gpu_fixed_result_size", "miqp_gpu_fixed_batch_chunk",
-                    "miqp_solver_set_pool", "miqp_solver_pool_count", "miqp_solver_pool_found", "miqp_solver_pool_solve", "miqp_solver_pool_record", "miqp_gpu_pool_max"]
+                    "miqp_solver_set_pool", "miqp_solver_pool_count", "miqp_solver_pool_found", "miqp_solver_pool_solve", "miqp_solver_pool_record", "miqp_gpu_pool_max",
+                    "miqp_solver_solve_fixed_multi", "miqp_solver_pool_solve_multi"]
 
 
 # a row of CplexWrapper.launchPlan (NodeLaunch in csrc/miqp_gpu.hip)
 LAUNCH_PLAN_FIELDS = ("kernel", "stream", "grid", "lds", "ovf_mode", "cls_take", "as_split", "skip_probes", "bounce", "work", "from_ovf2", "bufs", "zero")
+
+
+# miqp_fixed_result_c as a numpy record
+_FIXED_RESULT_DTYPE = np.dtype([("status", "<i4"), ("route", "<i4"), ("iterations", "<i4"), ("reserved", "<i4"), ("objective", "<f8"), ("violation", "<f8")])
 
 
 def pool_max():
@@ -606,6 +615,59 @@ def certify_batch(wrappers):
     if rc != 0:
         raise RuntimeError("miqp_solver_certify_batch failed (%d): %s" % (rc, wrappers[0].lastError()))
     return [Certificate(out[k]) for k in range(n)]
+
+
+def solve_fixed_multi(wrappers, records_per_wrapper):
+    """the fix records of many wrappers in one device call (miqp_solver_solve_fixed_multi): records_per_wrapper[h] is the list solveFixedBatch would
+    get for wrappers[h] (it may be empty).  Returns, per wrapper, what its solveFixedBatch returns - (status, objective, violation, iterations, route,
+    best), best counting inside the wrapper's own list - bit for bit; fixedBatchRecord works per wrapper afterwards.  A wrapper whose handle holds an
+    instance already (it has solved, or answered a solveFixedBatch) keeps it, and with it what the handle holds - the queue that was drained is the
+    queue that is asked; one that has not loaded its parameters yet loads them now.  Raises RuntimeError where the library refuses the call
+    (wrappers of different shape, no device: there is no host solve); a refused call leaves what the handles keep alone."""
+    L = load_library()
+    n = len(wrappers)
+    if n != len(records_per_wrapper):
+        raise ValueError("one list of records per wrapper")
+    d = (C.c_int * 6)()
+    for w in wrappers:
+        if L.miqp_solver_get_dims(w._h, d) != 0 and w._push_inputs() != 0:
+            raise RuntimeError("invalid parameters")
+    first = [0]
+    for recs in records_per_wrapper:
+        first.append(first[-1] + len(recs))
+    total = first[-1]
+    keep = [r.to_c() if r is not None else None for recs in records_per_wrapper for r in recs]
+    ptrs = (C.POINTER(RawResultsC) * max(total, 1))(*[C.pointer(c) if c is not None else None for c in keep])
+    out = (FixedResultC * max(total, 1))()
+    best = (C.c_int * max(n, 1))(*([-1] * max(n, 1)))
+    hs = (C.c_void_p * max(n, 1))(*[w._h for w in wrappers])
+    rc = L.miqp_solver_solve_fixed_multi(hs, n, ptrs, (C.c_int * (n + 1))(*first), out, best)
+    if rc != 0:
+        raise RuntimeError("miqp_solver_solve_fixed_multi failed (%d)%s" % (rc, ": " + wrappers[0].lastError() if n and rc == -2 else ""))
+    a = np.frombuffer(out, dtype=_FIXED_RESULT_DTYPE, count=total)
+    return [(a["status"][first[h]:first[h + 1]].copy(), a["objective"][first[h]:first[h + 1]].copy(), a["violation"][first[h]:first[h + 1]].copy(),
+             a["iterations"][first[h]:first[h + 1]].copy(), a["route"][first[h]:first[h + 1]].copy(), int(best[h])) for h in range(n)]
+
+
+def solve_solution_pools(wrappers):
+    """the solution pools of many wrappers refined in one device call (miqp_solver_pool_solve_multi): per wrapper what its solveSolutionPool
+    returns - (status, objective, violation, iterations, route) in pool order, bit for bit; solutionPoolCount and solutionPoolRecord work per
+    wrapper afterwards.  A wrapper without a pool gets empty arrays.  Raises RuntimeError where the library refuses the call."""
+    L = load_library()
+    n = len(wrappers)
+    cap = max([w.solutionPoolCount() for w in wrappers] + [1])
+    out = (FixedResultC * (max(n, 1) * cap))()
+    counts = (C.c_int * max(n, 1))()
+    hs = (C.c_void_p * max(n, 1))(*[w._h for w in wrappers])
+    m = L.miqp_solver_pool_solve_multi(hs, n, out, cap, counts)
+    if m < 0:
+        raise RuntimeError("miqp_solver_pool_solve_multi failed (%d)%s" % (m, ": " + wrappers[0].lastError() if n and m == -2 else ""))
+    a = np.frombuffer(out, dtype=_FIXED_RESULT_DTYPE, count=n * cap)
+    res = []
+    for h in range(n):
+        b = a[h * cap:h * cap + counts[h]]
+        res.append((b["status"].copy(), b["objective"].copy(), b["violation"].copy(), b["iterations"].copy(), b["route"].copy()))
+    return res
 
 
 def certify_last_timing():
