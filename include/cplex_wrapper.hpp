@@ -107,6 +107,7 @@ class CplexWrapper {
       if (!h_) { miqp_solver_opts o{}; o.precision = roundingDecimals_ + 2; o.device = -1; o.gap_override = -1.0; h_ = miqp_solver_create(&o); }   // (the C ABI rounds to precision - 2)
       if (!h_) return FAILED_SEG_FAULT;
       miqp_solver_set_pool(h_, poolCapacity_);
+      miqp_solver_set_pool_filter(h_, poolFilter_);
       if (parameterSource_ == DATFILE || (parameterSource_ == MIXED && !parameters_)) {   // MIXED: the C++ inputs when given, else the file
         if (miqp_solver_load_dat(h_, datfile_.c_str()) != 0) return FAILED_SEG_FAULT;
       } else { if (!parameters_ || !pushParameters()) return FAILED_SEG_FAULT; }
@@ -200,6 +201,13 @@ class CplexWrapper {
     if (capacity < 0 || capacity > miqp_gpu_pool_max()) return -2;
     poolCapacity_ = capacity;
     return h_ ? miqp_solver_set_pool(h_, capacity) : 0;
+  }
+  // setSolutionPoolFilter: which leaves are ONE entry of the pool (miqp_solver_set_pool_filter; IloCplex::addDiversityFilter for a CPLEX user) - a bit
+  // set of MIQP_POOL_BY_*; MIQP_POOL_BY_OBSTACLE | MIQP_POOL_BY_CAR_CAR keeps one entry per manoeuvre, 0 (the default) switches the filter off
+  int setSolutionPoolFilter(int families) {
+    if (families < 0 || families > 31) return -2;
+    poolFilter_ = families;
+    return h_ ? miqp_solver_set_pool_filter(h_, families) : 0;
   }
   int solutionPoolCount() const { return h_ ? miqp_solver_pool_count(h_) : 0; }
   int solveSolutionPool(std::vector<miqp_fixed_result_c>& results) {
@@ -371,6 +379,7 @@ class CplexWrapper {
   std::shared_ptr<ModelParameters> parameters_;
   miqp_solver_t* h_ = nullptr;  // created lazily
   int poolCapacity_ = 0;       // setSolutionPool
+  int poolFilter_ = 0;         // setSolutionPoolFilter
 };
 
 }  // namespace cplex

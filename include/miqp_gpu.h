@@ -260,6 +260,38 @@ int miqp_solver_pool_record(miqp_solver_t* s, int k, miqp_raw_results_c* out);
 /* largest capacity miqp_solver_set_pool accepts: a constant of the build (no device is needed or touched) */
 int miqp_gpu_pool_max(void);
 
+/* ---- manoeuvre filter of the solution pool: which leaves are ONE entry.  Counterpart of the diversity filter of the CPLEX pool
+ * (IloCplex::addDiversityFilter); the reference source has no call site for it. ----
+ * Without a filter two leaves are the same entry when they agree in every decision byte, and the near-optimal leaves of one manoeuvre - the same
+ * alternatives, changed a step earlier or later - fill the pool.  With a filter two leaves are the same entry when their SIGNATURES under `families`
+ * are equal, and the pool keeps the smallest member (in the pool's order) of each class: the `capacity` smallest class minima of the set of leaves
+ * seen, still a function of that set and reproducible bit for bit.
+ * families: a bit set of MIQP_POOL_BY_REGION (1), _BY_ENVIRONMENT (2), _BY_OBSTACLE (4), _BY_CAR_CAR (8), MIQP_POOL_EXACT_TIMING (16); 0 (the
+ * default) = off: then nothing is allocated, launched or changed.  MIQP_POOL_BY_OBSTACLE | MIQP_POOL_BY_CAR_CAR (12) is the setting for a planner
+ * that wants fallbacks: one entry per side of each obstacle and order of the cars.  31 is by definition the unfiltered pool.
+ * The signature of the D decision bytes d of a fix record (D = cars * steps * 6 + cars * obstacles * steps * 5 + pairs * steps * 4, pairs =
+ * cars * (cars - 1) / 2; per step i the region code of car c at d[c * steps + i], the environment piece of point pt at d[cars * steps + (c * steps + i)
+ * * 5 + pt], the obstacle edge at d[6 * cars * steps + ((c * obstacles + o) * steps + i) * 5 + pt], the car/car alternative of pair p, group g behind
+ * those at [(p * steps + i) * 4 + g]): D bytes, -1 except on the positions of the selected families.  A SITE is one such disjunction followed over i.
+ * Per site: the bytes of steps 1 .. steps - 1 that are not negative - of a region code its possible-region index, code >> 2 - with repeats of the
+ * value before collapsed, written left-packed to the site's positions of steps 1, 2, ...: what is decided in which order, not at which step.  With
+ * MIQP_POOL_EXACT_TIMING the site's bytes as they are, step 0 included.
+ * The incumbent stays entry 0: when its record is not kept but an entry of its signature is, it takes that entry's place.  miqp_solver_pool_solve and
+ * _pool_solve_multi also merge entries whose final labels have one signature.  Device memory: instances x largest capacity x record bytes more
+ * (the signatures of the entries kept), only in a call that has a handle with a filter.
+ * miqp_solver_set_pool_filter: 0, -1 NULL handle, -2 families outside 0 .. 31 (the previous setting stays).  The setting lasts like the capacity. */
+int miqp_solver_set_pool_filter(miqp_solver_t* s, int families);
+/* the signature of decisions[0 .. D) into out[0 .. D): a pure function on bytes, no handle, no device.  Returns D; -1 NULL pointers or a
+ * non-positive dimension (obstacles may be 0), -2 families outside 1 .. 31, -3 len < D. */
+int miqp_gpu_pool_signature(int cars, int steps, int obstacles, int families, const signed char* decisions, signed char* out, int len);
+/* ... of a RawResults record of the handle's instance: its fix record (the first alternative that holds, as miqp_solver_solve_fixed reads it), then
+ * the function above.  Returns D; -1 NULL arguments / no instance, -2 a record without its arrays or families outside 1 .. 31, -3 sizes of the
+ * record differ from the instance, -4 cap < D.  Needs no device. */
+int miqp_solver_pool_signature(const miqp_solver_t* s, const miqp_raw_results_c* rec, int families, signed char* out, int cap);
+/* the D decision bytes of entry k of the handle's pool as the search kept it (miqp_solver_pool_solve does not change them; entries it merges away
+ * leave).  Returns D; -1 NULL arguments, bad k or no pool, -3 cap < D.  Needs no device. */
+int miqp_solver_pool_found_decisions(const miqp_solver_t* s, int k, signed char* out, int cap);
+
 /* ---- fix records and solution pools of MANY handles in one device call: one device lock, one context, the n instances compiled on host threads and
  * their tables uploaded once, the nodes of all handles in common launch groups of miqp_gpu_fixed_batch_chunk nodes. ----
  * miqp_solver_solve_fixed_multi: entries first[h] .. first[h + 1] - 1 of fixed[] are fix records of the instance loaded in solvers[h] (first has n + 1

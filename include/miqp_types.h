@@ -39,6 +39,16 @@ enum {
   MIQP_WARMSTART_BOTH = 3
 };
 
+/* families of miqp_solver_set_pool_filter and miqp_gpu_pool_signature (include/miqp_gpu.h): a bit set.  Which disjunctions tell two pool entries
+ * apart - by the ORDER of their alternatives along the horizon; with MIQP_POOL_EXACT_TIMING by the alternative of every step */
+enum {
+  MIQP_POOL_BY_REGION = 1,
+  MIQP_POOL_BY_ENVIRONMENT = 2,
+  MIQP_POOL_BY_OBSTACLE = 4,
+  MIQP_POOL_BY_CAR_CAR = 8,
+  MIQP_POOL_EXACT_TIMING = 16
+};
+
 /* CPLEX status integers reported in SolutionProperties.status (src/cplex_wrapper.cpp:672-677) */
 enum {
   MIQP_CPX_STAT_OPTIMAL = 101,

@@ -379,12 +379,13 @@ int miqp_solver_pool_solve_multi(miqp_solver_t* const* solvers, int n, miqp_fixe
       char msg[220]; std::snprintf(msg, sizeof msg, "miqp_solver_pool_solve_multi: the labels of the pool entries still moved after %d passes; an entry may differ from what miqp_solver_solve_fixed answers for its record", P.passes);
       s->err = msg; std::fprintf(stderr, "[miqp_gpu] %s\n", msg);
     }
-    // entries whose records carry the same binaries are ONE solution: the first in pool order stays, the handle's pool shrinks with it (miqp_solver_pool_solve)
+    // entries whose records carry the same binaries - under the handle's filter: the same signature - are ONE solution (pool_same_entry, shared with
+    // miqp_solver_pool_solve): the first in pool order stays, the handle's pool shrinks with it
     std::vector<miqp_fixed_result_c>& tmp = P.tmp; std::vector<signed char>& fix = P.fix; std::vector<signed char>& canon = P.canon; std::vector<double>& Z = P.Z;
     int kept = 0;
     for (int k = 0; k < m; ++k) {
       bool dup = false;
-      for (int j = 0; j < kept && !dup; ++j) dup = tmp[k].status == 0 && tmp[j].status == 0 && std::memcmp(canon.data() + (size_t)k * fl, canon.data() + (size_t)j * fl, fl) == 0;
+      for (int j = 0; j < kept && !dup; ++j) dup = tmp[k].status == 0 && tmp[j].status == 0 && pool_same_entry(Y, s->pool_fam, canon.data() + (size_t)k * fl, canon.data() + (size_t)j * fl);
       if (dup) continue;
       if (kept != k) {
         tmp[kept] = tmp[k]; s->pool_obj[kept] = s->pool_obj[k];

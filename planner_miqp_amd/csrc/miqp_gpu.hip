@@ -114,6 +114,7 @@ struct miqp_solver {
   // their objectives as found and the record length; of the last miqp_solver_pool_solve: per entry whether it came out feasible, the fix record it was
   // refined with and its trajectory.  Dropped by the next solve and whenever the instance changes
   int pool_cap = 0, pool_n = 0, pool_fixlen = 0; std::vector<signed char> pool_fix; std::vector<double> pool_obj;
+  int pool_fam = 0;   // miqp_solver_set_pool_filter: the families whose signature says which leaves are one entry, 0 = off (a setting like pool_cap: it stays)
   int pr_n = 0; std::vector<char> pr_ok; std::vector<signed char> pr_fix; std::vector<double> pr_Z;
   void drop_pool() { pool_n = 0; pr_n = 0; std::vector<signed char>().swap(pool_fix); std::vector<double>().swap(pool_obj); std::vector<char>().swap(pr_ok); std::vector<signed char>().swap(pr_fix); std::vector<double>().swap(pr_Z); }
   std::string err;
@@ -329,6 +330,8 @@ CallSwitches read_call_switches() {
 struct SolPoolDev {
   int* list = nullptr; int* count = nullptr;   // the round's candidates: batch slots, and their number (two words, by the parity of the capture)
   signed char* fix = nullptr; double* obj = nullptr; unsigned int* hash = nullptr; int* cnt = nullptr; int* cap = nullptr;   // [n_inst][stride] records, objectives, hashes; [n_inst] entries kept, capacity asked for
+  signed char* sig = nullptr; int* fam = nullptr;   // manoeuvre filter, only once a call had a handle with one: [n_inst][stride] signatures of the records, [n_inst] family sets
+  bool filt = false;   // a handle of the call that holds the context has a filter: the capture launches pool_filter_kernel
   int n_inst = 0, stride = 0, list_cap = 0;
   int captures = 0;   // capture launches of the call: a capture uses count[captures & 1] and zeroes the other word for the next one (NOT the round number: rounds without a batch launch no capture)
   bool on = false;   // the call that holds the context has a handle with a pool

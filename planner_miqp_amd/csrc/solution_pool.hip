@@ -23,7 +23,8 @@
 // incumbent's, or at capacity push it out: pool_read_back puts the incumbent's record first, so entry 0 is the incumbent at every capacity.
 //
 // Memory: n_inst x stride x (fixlen + 12) + 8 n_inst + 4 batch_alloc + 8 bytes, stride = the largest capacity of the call's handles (n_inst = 51 200 handles
-// of two cars x 8 steps, capacity 8: 0.2 GB).  A rank of a tree split keeps the pool of its own search; pools are not exchanged.
+// of two cars x 8 steps, capacity 8: 0.2 GB); with a filter in the call n_inst x stride x fixlen + 4 n_inst more (the signatures, the family sets).
+// A rank of a tree split keeps the pool of its own search; pools are not exchanged.
 //
 // Refinement: pool entries were found at node tolerance; miqp_solver_pool_solve sends them through the fixed-batch chain (fixed_batch.hip) at the tight
 // tolerance.  What the caller gets per entry is what miqp_solver_solve_fixed answers for the entry's RawResults record: the call re-labels each record
@@ -32,6 +33,14 @@
 // both QPs have the same minimiser - and are merged there, the best found staying (of the one-car helper shape c1n6r16hex the search keeps 4 records,
 // all of them the incumbent's trajectory).  The capture cannot see this: it has the decisions of a leaf, not a tight solution.  So a pool can hand out
 // fewer than `capacity` solutions although the search saw more distinct ones.
+//
+// Manoeuvre filter (miqp_solver_set_pool_filter; off by default - then nothing below runs): the near-optimal leaves of ONE manoeuvre differ in
+// WHEN a car changes its alternative, and a pool that tells entries apart by every decision byte fills with those timing variants.  With a filter two
+// candidates are the same entry when their SIGNATURES agree (pool_signature below: per site - one disjunction followed along the horizon - the
+// sequence of alternatives with repeats collapsed, for the selected families), and the pool keeps the smallest member of each class: the `capacity`
+// smallest class minima of the set seen.  pool_filter_kernel replaces pool_merge_kernel in a call that has a handle with a filter; the signatures of the
+// entries kept lie in a buffer of their own (n_inst x stride x fixlen bytes, only then).  A handle of such a call WITHOUT a filter is merged exactly as
+// pool_merge_kernel merges it: its signature is its record.
 #pragma once
 
 namespace {
@@ -141,6 +150,148 @@ __global__ __launch_bounds__(64) void pool_merge_kernel(const PoolArgs A) {
   if (lane == 0) A.cnt[inst] = cnt;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- manoeuvre filter
+constexpr int POOL_FAM_REGION = 1, POOL_FAM_ENVIRONMENT = 2, POOL_FAM_OBSTACLE = 4, POOL_FAM_CAR_CAR = 8, POOL_FAM_TIMING = 16, POOL_FAM_ALL = 31;
+
+// the sites of a decision record - one disjunction followed along the horizon: the byte of step i of a site lies at first + i * step
+struct PoolDims { int C, N, O, NP; };
+struct PoolSite { int first, step, family; };
+__host__ __device__ inline int pool_declen(const PoolDims& d) { return d.C * d.N * 6 + d.C * d.O * d.N * 5 + d.NP * d.N * 4; }
+__host__ __device__ inline int pool_sites(const PoolDims& d) { return d.C * 6 + d.C * d.O * 5 + d.NP * 4; }
+__host__ __device__ inline PoolSite pool_site(const PoolDims& d, int s) {
+  const int f_env = d.C * d.N, f_obs = f_env + d.C * d.N * 5, f_c2c = f_obs + d.C * d.O * d.N * 5;
+  if (s < d.C) return PoolSite{s * d.N, 1, POOL_FAM_REGION};
+  s -= d.C;
+  if (s < d.C * 5) return PoolSite{f_env + (s / 5) * d.N * 5 + s % 5, 5, POOL_FAM_ENVIRONMENT};
+  s -= d.C * 5;
+  if (s < d.C * d.O * 5) return PoolSite{f_obs + (s / 5) * d.N * 5 + s % 5, 5, POOL_FAM_OBSTACLE};
+  s -= d.C * d.O * 5;
+  return PoolSite{f_c2c + (s >> 2) * d.N * 4 + (s & 3), 4, POOL_FAM_CAR_CAR};
+}
+// the signature bytes of ONE site (sg is -1 there before): with the timing bit its bytes as they are, step 0 included; without it the alternatives of
+// steps 1 .. N - 1 in their order, undecided bytes skipped, repeats collapsed, left-packed from step 1 - of a region byte the possible-region index
+// (byte >> 2: the low two bits are the half-plane or slow alternative)
+__host__ __device__ inline void pool_site_signature(const PoolDims& d, int fam, int s, const signed char* rec, signed char* sg) {
+  const PoolSite t = pool_site(d, s);
+  if (!(fam & t.family)) return;
+  if (fam & POOL_FAM_TIMING) { for (int i = 0; i < d.N; ++i) sg[t.first + i * t.step] = rec[t.first + i * t.step]; return; }
+  int last = -1, w = 0;
+  for (int i = 1; i < d.N; ++i) {
+    int v = rec[t.first + i * t.step];
+    if (v < 0) continue;
+    if (t.family == POOL_FAM_REGION) v >>= 2;
+    if (v != last) { w++; sg[t.first + w * t.step] = (signed char)v; last = v; }
+  }
+}
+
+struct PoolFilterArgs { PoolArgs A; signed char* sig; const int* fam; PoolDims dims; };
+
+// pool_merge_kernel with the filter: the same launch (one wavefront per instance in flight, owner computes, ballot over 64 list entries), the same
+// order of the pool; what changes is which entry a candidate IS.  The candidate's signature is built in a second LDS block (one lane per site, in a
+// loop when there are more sites than lanes) and compared with the signatures kept beside the records; a candidate of a kept signature replaces that
+// entry when it is smaller in the pool's order, else it is dropped.  fam[inst] == 0: the signature is the record, and every step below is
+// pool_merge_kernel's (the signature buffer is not touched)
+__global__ __launch_bounds__(64) void pool_filter_kernel(const PoolFilterArgs F) {
+  extern __shared__ uint4 cand[];   // the candidate's record, mask bytes reset; behind it its signature
+  const PoolArgs& A = F.A;
+  const int lane = threadIdx.x;
+  const int inst = A.slot_inst[blockIdx.x];
+  if (inst < 0 || inst >= A.n_inst) return;
+  const int K = min(A.cap[inst], A.stride);
+  if (K <= 0) return;
+  const int fam = F.fam[inst] & POOL_FAM_ALL;
+  const int m = min(A.count[A.par], min(A.bc, A.list_cap)), chunks = A.fixlen >> 4, nsites = pool_sites(F.dims);
+  uint4* const csig = fam ? cand + chunks : cand;
+  uint4* const rec = (uint4*)(A.fix + (size_t)inst * A.stride * A.fixlen);
+  uint4* const sig = fam ? (uint4*)(F.sig + (size_t)inst * A.stride * A.fixlen) : rec;
+  double* const pobj = A.obj + (size_t)inst * A.stride; unsigned int* const phash = A.hash + (size_t)inst * A.stride;
+  int cnt = min(A.cnt[inst], K);
+  for (int q0 = 0; q0 < m; q0 += 64) {
+    int mynode = q0 + lane < m ? A.list[q0 + lane] : -1;
+    if ((unsigned)mynode >= (unsigned)A.bc || A.candinst[mynode] != inst) mynode = -1;
+    unsigned long long own = __ballot(mynode >= 0);
+    for (; own; own &= own - 1ull) {
+      const int node = __shfl(mynode, __ffsll((long long)own) - 1, 64);
+      __syncthreads();
+      int h = 0;
+      {
+        const uint4* src = (const uint4*)(A.batch_comp + (size_t)node * A.fixlen);
+        for (int c = lane; c < chunks; c += 64) {
+          uint4 v = src[c]; signed char* b = (signed char*)&v;
+          for (int t = 0; t < 16; ++t) { const int k = c * 16 + t; if (k >= A.declen) b[t] = (signed char)-1; else h += ((int)b[t] + 3) * (2 * k + 1); }
+          cand[c] = v;
+          if (fam) csig[c] = make_uint4(~0u, ~0u, ~0u, ~0u);
+        }
+        for (int o = 32; o > 0; o >>= 1) h += __shfl_xor(h, o, 64);
+      }
+      __syncthreads();
+      if (fam) {
+        for (int s = lane; s < nsites; s += 64) pool_site_signature(F.dims, fam, s, (const signed char*)cand, (signed char*)csig);
+        __syncthreads();
+      }
+      const unsigned int hs = (unsigned int)h; const double o = A.batch_obj[node]; const unsigned long long ok = d2key(o);
+      // an entry of this signature already kept: the smaller of the two in the pool's order stays (and moves to its new place)
+      int dup = -1;
+      for (int j = 0; j < cnt && dup < 0; ++j) if ((fam || phash[j] == hs) && pool_cmp(csig, sig + (size_t)j * chunks, chunks, lane) == 0) dup = j;
+      if (dup >= 0) {
+        const unsigned long long kd = d2key(pobj[dup]); const unsigned int hd = phash[dup];
+        bool less = ok < kd || (ok == kd && hs < hd);
+        if (fam && !less && ok == kd && hs == hd) less = pool_cmp(cand, rec + (size_t)dup * chunks, chunks, lane) < 0;
+        if (!less) continue;
+        for (int j = dup; j + 1 < cnt; ++j) {
+          for (int c = lane; c < chunks; c += 64) {
+            rec[(size_t)j * chunks + c] = rec[(size_t)(j + 1) * chunks + c];
+            if (fam) sig[(size_t)j * chunks + c] = sig[(size_t)(j + 1) * chunks + c];
+          }
+          if (lane == 0) { pobj[j] = pobj[j + 1]; phash[j] = phash[j + 1]; }
+          __syncthreads();
+        }
+        cnt--;
+      }
+      int p = 0;
+      for (int j = 0; j < cnt; ++j) {
+        const unsigned long long kj = d2key(pobj[j]); const unsigned int hj = phash[j];
+        bool less = kj < ok || (kj == ok && hj < hs);
+        if (!less && kj == ok && hj == hs) less = pool_cmp(rec + (size_t)j * chunks, cand, chunks, lane) < 0;
+        if (less) p = j + 1;
+      }
+      if (p >= K) continue;
+      const int last = min(cnt, K - 1);   // entries p .. last - 1 move down by one (the one at K - 1 leaves)
+      for (int j = last; j > p; --j) {
+        for (int c = lane; c < chunks; c += 64) {
+          rec[(size_t)j * chunks + c] = rec[(size_t)(j - 1) * chunks + c];
+          if (fam) sig[(size_t)j * chunks + c] = sig[(size_t)(j - 1) * chunks + c];
+        }
+        if (lane == 0) { pobj[j] = pobj[j - 1]; phash[j] = phash[j - 1]; }
+        __syncthreads();
+      }
+      for (int c = lane; c < chunks; c += 64) { rec[(size_t)p * chunks + c] = cand[c]; if (fam) sig[(size_t)p * chunks + c] = csig[c]; }
+      if (lane == 0) { pobj[p] = o; phash[p] = hs; }
+      cnt = min(cnt + 1, K);
+      __syncthreads();
+    }
+  }
+  if (lane == 0) A.cnt[inst] = cnt;
+}
+
+// the whole signature on the host: sg[0 .. fixlen) (-1 behind the decisions, like the mask bytes of a pool record)
+inline void pool_signature(const PoolDims& d, int fam, const signed char* rec, signed char* sg, size_t len) {
+  std::memset(sg, 0xFF, len);
+  for (int s = 0, n = pool_sites(d); s < n; ++s) pool_site_signature(d, fam, s, rec, sg);
+}
+inline PoolDims pool_dims(const Layout& Y) { return PoolDims{Y.C, Y.N, Y.O, Y.NP}; }
+
+// "the same entry" of the refinement (miqp_solver_pool_solve and miqp_solver_pool_solve_multi, so that the two cannot drift apart): two feasible
+// entries whose final labels a, b are the same binaries, or - under the handle's filter - have the same signature
+inline bool pool_same_entry(const Layout& Y, int fam, const signed char* a, const signed char* b) {
+  const size_t fl = (size_t)Y.fixlen;
+  if (std::memcmp(a, b, fl) == 0) return true;
+  if (!(fam & POOL_FAM_ALL)) return false;
+  std::vector<signed char> sa(fl), sb(fl);
+  pool_signature(pool_dims(Y), fam, a, sa.data(), fl); pool_signature(pool_dims(Y), fam, b, sb.data(), fl);
+  return sa == sb;
+}
+
 // ---------------------------------------------------------------------------------------------------------------- host: capture
 template <class Tp> bool pool_alloc(DevCtx& X, Tp** p, size_t n) {
   if (*p) { for (auto it = X.allocs.begin(); it != X.allocs.end(); ++it) if (*it == (void*)*p) { X.allocs.erase(it); break; } (void)hipFree(*p); *p = nullptr; }
@@ -148,18 +299,20 @@ template <class Tp> bool pool_alloc(DevCtx& X, Tp** p, size_t n) {
 }
 
 bool pool_prepare(DevCtx& X, miqp_solver_t* const* S, int n) {
-  int stride = 0;
-  for (int k = 0; k < n; ++k) stride = std::max(stride, std::min(S[k]->pool_cap, MIQP_POOL_MAX));
-  X.pool.on = stride > 0;
+  int stride = 0; bool filt = false;   // (a filter counts only on a handle that has a pool)
+  for (int k = 0; k < n; ++k) { stride = std::max(stride, std::min(S[k]->pool_cap, MIQP_POOL_MAX)); filt = filt || (S[k]->pool_cap > 0 && (S[k]->pool_fam & POOL_FAM_ALL) != 0); }
+  X.pool.on = stride > 0; X.pool.filt = false;
   if (!X.pool.on) return true;
   SolPoolDev& Q = X.pool; const size_t fl = (size_t)X.Y.fixlen;
-  if (!Q.fix || Q.n_inst < n || Q.stride < stride || Q.list_cap < X.batch_alloc) {
-    const size_t bytes = (size_t)n * stride * (fl + 12) + (size_t)n * 8 + (size_t)X.batch_alloc * 4 + 8;
+  if (!Q.fix || Q.n_inst < n || Q.stride < stride || Q.list_cap < X.batch_alloc || (filt && !Q.sig)) {
+    filt = filt || Q.sig != nullptr;   // (a context that held signatures keeps holding them: a later call with a filter finds them)
+    const size_t bytes = (size_t)n * stride * (fl + 12) + (size_t)n * 8 + (size_t)X.batch_alloc * 4 + 8 + (filt ? (size_t)n * stride * fl + (size_t)n * 4 : 0);
     Q.n_inst = 0;
-    const bool ok = pool_alloc(X, &Q.fix, (size_t)n * stride * fl) && pool_alloc(X, &Q.obj, (size_t)n * stride) && pool_alloc(X, &Q.hash, (size_t)n * stride) &&
-                    pool_alloc(X, &Q.cnt, (size_t)n) && pool_alloc(X, &Q.cap, (size_t)n) && pool_alloc(X, &Q.list, (size_t)X.batch_alloc) && pool_alloc(X, &Q.count, 2);
+    bool ok = pool_alloc(X, &Q.fix, (size_t)n * stride * fl) && pool_alloc(X, &Q.obj, (size_t)n * stride) && pool_alloc(X, &Q.hash, (size_t)n * stride) &&
+              pool_alloc(X, &Q.cnt, (size_t)n) && pool_alloc(X, &Q.cap, (size_t)n) && pool_alloc(X, &Q.list, (size_t)X.batch_alloc) && pool_alloc(X, &Q.count, 2);
+    if (ok && filt) ok = pool_alloc(X, &Q.sig, (size_t)n * stride * fl) && pool_alloc(X, &Q.fam, (size_t)n);
     if (!ok) {
-      char msg[160]; std::snprintf(msg, sizeof msg, "the solution pool of this call (%d instances x %d entries, %zu bytes) does not fit the device", n, stride, bytes);
+      char msg[200]; std::snprintf(msg, sizeof msg, "the solution pool of this call (%d instances x %d entries%s, %zu bytes) does not fit the device", n, stride, filt ? ", with signatures" : "", bytes);
       for (int k = 0; k < n; ++k) S[k]->err = msg;
       std::fprintf(stderr, "[miqp_gpu] %s\n", msg);
       X.pool.on = false; return false;
@@ -168,8 +321,11 @@ bool pool_prepare(DevCtx& X, miqp_solver_t* const* S, int n) {
   }
   std::vector<int> cap(n); for (int k = 0; k < n; ++k) cap[k] = std::max(0, std::min(S[k]->pool_cap, MIQP_POOL_MAX));
   HIP_OK(hipMemcpyAsync(Q.cap, cap.data(), (size_t)n * 4, hipMemcpyHostToDevice, X.stream));
+  std::vector<int> fam(n, 0);
+  for (int k = 0; k < n; ++k) if (cap[k] > 0 && (S[k]->pool_fam & POOL_FAM_ALL)) { fam[k] = S[k]->pool_fam & POOL_FAM_ALL; Q.filt = true; }
+  if (Q.filt) HIP_OK(hipMemcpyAsync(Q.fam, fam.data(), (size_t)n * 4, hipMemcpyHostToDevice, X.stream));
   HIP_OK(hipMemsetAsync(Q.cnt, 0, (size_t)n * 4, X.stream)); HIP_OK(hipMemsetAsync(Q.count, 0, 8, X.stream)); Q.captures = 0;
-  HIP_OK(hipStreamSynchronize(X.stream));   // (cap is a local)
+  HIP_OK(hipStreamSynchronize(X.stream));   // (cap and fam are locals)
   return true;
 }
 
@@ -185,7 +341,11 @@ bool pool_capture(DevCtx& X, int bc) {
   if (A.bc <= 0) return true;
   Q.captures++;
   hipLaunchKernelGGL(pool_compact_kernel, dim3((A.bc + 255) / 256), dim3(256), 0, X.stream, A);
-  hipLaunchKernelGGL(pool_merge_kernel, dim3(X.n_slots), dim3(64), (size_t)X.Y.fixlen, X.stream, A);
+  if (Q.filt) {
+    PoolFilterArgs F; F.A = A; F.sig = Q.sig; F.fam = Q.fam; F.dims = pool_dims(X.Y);
+    hipLaunchKernelGGL(pool_filter_kernel, dim3(X.n_slots), dim3(64), 2 * (size_t)X.Y.fixlen, X.stream, F);
+  } else
+    hipLaunchKernelGGL(pool_merge_kernel, dim3(X.n_slots), dim3(64), (size_t)X.Y.fixlen, X.stream, A);
   HIP_OK(hipGetLastError());
   return true;
 }
@@ -194,7 +354,8 @@ bool pool_capture(DevCtx& X, int bc) {
 // every path: it is a candidate of some round and the smallest in the search's order - the objective to 44 bits, then the hash of the WHOLE record -
 // which the pool's order (the full objective, then the hash of the decisions) follows except among records whose objectives agree to those 44 bits.
 // There another record can sort in front of the incumbent's, or (capacity 1, or that many ties) push it out: the incumbent's record (R.fix, mask
-// bytes reset like a pool record) is moved to the front, or put there with the objective it was found with, the last entry leaving
+// bytes reset like a pool record) is moved to the front, or put there with the objective it was found with, the last entry leaving - under a filter the
+// entry of the incumbent's signature, when there is one: the pool keeps one entry per signature
 bool pool_read_back(const DevCtx& X, miqp_solver_t* const* S, int n, const Results& R) {
   const SolPoolDev& Q = X.pool; const size_t fl = (size_t)X.Y.fixlen; const int declen = X.Y.f_c2n;
   std::vector<int> cnt(n); std::vector<double> obj((size_t)n * Q.stride), inc(n); std::vector<signed char> fix((size_t)n * Q.stride * fl);
@@ -202,7 +363,7 @@ bool pool_read_back(const DevCtx& X, miqp_solver_t* const* S, int n, const Resul
   HIP_OK(hipMemcpy(obj.data(), Q.obj, obj.size() * 8, hipMemcpyDeviceToHost));
   HIP_OK(hipMemcpy(fix.data(), Q.fix, fix.size(), hipMemcpyDeviceToHost));
   HIP_OK(hipMemcpy(inc.data(), X.B.inc_obj, (size_t)n * 8, hipMemcpyDeviceToHost));   // (as found: R.inc is the polished one by now)
-  std::vector<signed char> mine(fl);
+  std::vector<signed char> mine(fl), msig(fl), esig(fl);
   for (int k = 0; k < n; ++k) {
     miqp_solver* s = S[k];
     const int K = std::max(0, std::min(s->pool_cap, Q.stride));
@@ -213,12 +374,18 @@ bool pool_read_back(const DevCtx& X, miqp_solver_t* const* S, int n, const Resul
       for (size_t q = (size_t)declen; q < fl; ++q) mine[q] = (signed char)-1;
       int at = -1;
       for (int j = 0; j < c && at < 0; ++j) if (std::memcmp(pf + (size_t)j * fl, mine.data(), fl) == 0) at = j;
+      int twin = -1;   // the entry of the incumbent's signature, its record not being kept
+      const int fam = s->pool_fam & POOL_FAM_ALL;
+      if (at < 0 && fam) {
+        pool_signature(pool_dims(X.Y), fam, mine.data(), msig.data(), fl);
+        for (int j = 0; j < c && twin < 0; ++j) { pool_signature(pool_dims(X.Y), fam, pf + (size_t)j * fl, esig.data(), fl); if (esig == msig) twin = j; }
+      }
       if (at != 0) {
         const double o = at > 0 ? po[at] : inc[k];
-        const int last = at > 0 ? at : std::min(c, K - 1);   // entries 0 .. last - 1 move down by one
+        const int last = at > 0 ? at : (twin >= 0 ? twin : std::min(c, K - 1));   // entries 0 .. last - 1 move down by one
         std::memmove(pf + fl, pf, (size_t)last * fl); std::memmove(po + 1, po, (size_t)last * 8);
         std::memcpy(pf, mine.data(), fl); po[0] = o;
-        if (at < 0) c = std::min(c + 1, K);
+        if (at < 0 && twin < 0) c = std::min(c + 1, K);
       }
     }
     s->pool_n = c; s->pool_fixlen = (int)fl;
@@ -239,6 +406,51 @@ int miqp_solver_set_pool(miqp_solver_t* s, int capacity) {
   if (capacity < 0 || capacity > MIQP_POOL_MAX) return -2;
   s->pool_cap = capacity;
   return 0;
+}
+
+int miqp_solver_set_pool_filter(miqp_solver_t* s, int families) {
+  if (!s) return -1;
+  if (families < 0 || families > POOL_FAM_ALL) return -2;
+  s->pool_fam = families;
+  return 0;
+}
+
+int miqp_gpu_pool_signature(int cars, int steps, int obstacles, int families, const signed char* decisions, signed char* out, int len) {
+  if (!decisions || !out || cars <= 0 || steps <= 0 || obstacles < 0) return -1;
+  if (families < 1 || families > POOL_FAM_ALL) return -2;
+  const PoolDims d{cars, steps, obstacles, cars * (cars - 1) / 2};
+  const int D = pool_declen(d);
+  if (len < D) return -3;
+  pool_signature(d, families, decisions, out, (size_t)D);
+  return D;
+}
+
+int miqp_solver_pool_signature(const miqp_solver_t* s, const miqp_raw_results_c* rec, int families, signed char* out, int cap) {
+  if (!s || !rec || !out || !s->has_inst) return -1;
+  if (families < 1 || families > POOL_FAM_ALL || !cert_candidate_ok(*rec)) return -2;
+  if (!dims_match(*rec, s->inst)) return -3;   // a record of another shape is never indexed
+  miqp_solver_t* one[1] = {const_cast<miqp_solver_t*>(s)};
+  BatchShape bs = batch_layout(one, 1);
+  if (!bs.ok) return -1;
+  const Layout& Y = bs.Y;
+  if (cap < Y.f_c2n) return -4;
+  std::vector<double> D(Y.dstride); std::vector<int> T(Y.istride);
+  compile_instance(s->inst, Y, D.data(), T.data());
+  std::vector<signed char> fix, sg((size_t)Y.fixlen);
+  if (!fix_from_results(s->inst, Y, T.data(), rec, fix)) return -2;
+  pool_signature(pool_dims(Y), families, fix.data(), sg.data(), sg.size());
+  std::memcpy(out, sg.data(), (size_t)Y.f_c2n);
+  return Y.f_c2n;
+}
+
+int miqp_solver_pool_found_decisions(const miqp_solver_t* s, int k, signed char* out, int cap) {
+  if (!s || !out || k < 0 || k >= miqp_solver_pool_count(s)) return -1;
+  const PoolDims d{s->inst.C, s->inst.N, s->inst.O, s->inst.C * (s->inst.C - 1) / 2};
+  const int D = pool_declen(d);
+  if (D > s->pool_fixlen || s->pool_fix.size() < (size_t)(k + 1) * s->pool_fixlen) return -1;
+  if (cap < D) return -3;
+  std::memcpy(out, s->pool_fix.data() + (size_t)k * s->pool_fixlen, (size_t)D);
+  return D;
 }
 
 int miqp_solver_pool_count(const miqp_solver_t* s) { return (s && s->has_inst && s->has_sol && s->pool_cap > 0) ? s->pool_n : 0; }
@@ -290,11 +502,12 @@ int miqp_solver_pool_solve(miqp_solver_t* s, miqp_fixed_result_c* out, int cap) 
     s->err = msg; std::fprintf(stderr, "[miqp_gpu] %s\n", msg);
   }
   // entries whose records carry the same binaries are ONE solution (the optimum of one holds the alternatives of the other too, so both QPs have the
-  // same strictly convex minimiser): the first in pool order stays, the handle's pool shrinks with it
+  // same strictly convex minimiser), and under the handle's filter so are entries whose final labels have one signature (pool_same_entry): the first
+  // in pool order stays, the handle's pool shrinks with it
   int kept = 0;
   for (int k = 0; k < m; ++k) {
     bool dup = false;
-    for (int j = 0; j < kept && !dup; ++j) dup = tmp[k].status == 0 && tmp[j].status == 0 && std::memcmp(canon.data() + (size_t)k * fl, canon.data() + (size_t)j * fl, fl) == 0;
+    for (int j = 0; j < kept && !dup; ++j) dup = tmp[k].status == 0 && tmp[j].status == 0 && pool_same_entry(Y, s->pool_fam, canon.data() + (size_t)k * fl, canon.data() + (size_t)j * fl);
     if (dup) continue;
     if (kept != k) {
       tmp[kept] = tmp[k]; s->pool_obj[kept] = s->pool_obj[k];

@@ -105,6 +105,11 @@ def load_library():
     L.miqp_solver_pool_solve.restype = C.c_int; L.miqp_solver_pool_solve.argtypes = [vp, C.POINTER(FixedResultC), C.c_int]
     L.miqp_solver_pool_record.restype = C.c_int; L.miqp_solver_pool_record.argtypes = [vp, C.c_int, C.POINTER(RawResultsC)]
     L.miqp_gpu_pool_max.restype = C.c_int; L.miqp_gpu_pool_max.argtypes = []
+    L.miqp_solver_set_pool_filter.restype = C.c_int; L.miqp_solver_set_pool_filter.argtypes = [vp, C.c_int]
+    L.miqp_gpu_pool_signature.restype = C.c_int
+    L.miqp_gpu_pool_signature.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_byte), C.POINTER(C.c_byte), C.c_int]
+    L.miqp_solver_pool_signature.restype = C.c_int; L.miqp_solver_pool_signature.argtypes = [vp, C.POINTER(RawResultsC), C.c_int, C.POINTER(C.c_byte), C.c_int]
+    L.miqp_solver_pool_found_decisions.restype = C.c_int; L.miqp_solver_pool_found_decisions.argtypes = [vp, C.c_int, C.POINTER(C.c_byte), C.c_int]
     L.miqp_solver_solve_fixed_multi.restype = C.c_int
     L.miqp_solver_solve_fixed_multi.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(C.POINTER(RawResultsC)), C.POINTER(C.c_int), C.POINTER(FixedResultC), C.POINTER(C.c_int)]
     L.miqp_solver_pool_solve_multi.restype = C.c_int
@@ -133,7 +138,8 @@ EXPORTED_SYMBOLS = ["miqp_solver_create", "miqp_solver_destroy", "miqp_solver_se
                     "miqp_gpu_has_active_set", "miqp_solver_last_fixed_route", "miqp_solver_launch_plan",
                     "miqp_solver_solve_fixed_batch", "miqp_solver_fixed_batch_record", "miqp_gpu_fixed_result_size", "miqp_gpu_fixed_batch_chunk",
                     "miqp_solver_set_pool", "miqp_solver_pool_count", "miqp_solver_pool_found", "miqp_solver_pool_solve", "miqp_solver_pool_record", "miqp_gpu_pool_max",
-                    "miqp_solver_solve_fixed_multi", "miqp_solver_pool_solve_multi"]
+                    "miqp_solver_solve_fixed_multi", "miqp_solver_pool_solve_multi",
+                    "miqp_solver_set_pool_filter", "miqp_gpu_pool_signature", "miqp_solver_pool_signature", "miqp_solver_pool_found_decisions"]
 
 
 # a row of CplexWrapper.launchPlan (NodeLaunch in csrc/miqp_gpu.hip)
@@ -142,6 +148,31 @@ LAUNCH_PLAN_FIELDS = ("kernel", "stream", "grid", "lds", "ovf_mode", "cls_take",
 
 # miqp_fixed_result_c as a numpy record
 _FIXED_RESULT_DTYPE = np.dtype([("status", "<i4"), ("route", "<i4"), ("iterations", "<i4"), ("reserved", "<i4"), ("objective", "<f8"), ("violation", "<f8")])
+
+
+# the families of CplexWrapper.setSolutionPoolFilter (MIQP_POOL_BY_* of include/miqp_types.h): a bit set
+POOL_BY_REGION, POOL_BY_ENVIRONMENT, POOL_BY_OBSTACLE, POOL_BY_CAR_CAR, POOL_EXACT_TIMING = 1, 2, 4, 8, 16
+
+
+def _decision_len(cars, steps, obstacles):
+    """D: the decision bytes of a fix record (regions, environment pieces, obstacle edges, car/car alternatives)"""
+    return cars * steps * 6 + cars * obstacles * steps * 5 + cars * (cars - 1) // 2 * steps * 4
+
+
+def pool_signature(cars, steps, obstacles, families, decisions):
+    """the signature of a record's D decision bytes under ``families`` (miqp_gpu_pool_signature; int8 array of D bytes): two records are the same
+    entry of a filtered pool when their signatures are equal.  A pure function on bytes: needs no wrapper and no device.  Raises ValueError
+    where the library refuses the arguments."""
+    d = np.ascontiguousarray(decisions, dtype=np.int8)
+    D = _decision_len(int(cars), int(steps), int(obstacles))
+    if d.ndim != 1 or d.size < D or D <= 0:
+        raise ValueError("%d decision bytes given, the shape has %d" % (d.size, D))
+    out = np.empty(D, dtype=np.int8)
+    bp = C.POINTER(C.c_byte)
+    rc = load_library().miqp_gpu_pool_signature(int(cars), int(steps), int(obstacles), int(families), d.ctypes.data_as(bp), out.ctypes.data_as(bp), D)
+    if rc != D:
+        raise ValueError("miqp_gpu_pool_signature refused the arguments (%d)" % rc)
+    return out
 
 
 def pool_max():
@@ -470,6 +501,34 @@ class CplexWrapper:
         """the next solves of this wrapper keep their ``capacity`` best distinct integer solutions (0: off, the default; at most pool_max()).
         Returns the library's code: 0, < 0 when the capacity is refused (the previous setting stays)"""
         return int(self._L.miqp_solver_set_pool(self._h, int(capacity)))
+
+    def setSolutionPoolFilter(self, families):
+        """which leaves are ONE entry of the pool of the next solves: a bit set of POOL_BY_REGION, POOL_BY_ENVIRONMENT, POOL_BY_OBSTACLE,
+        POOL_BY_CAR_CAR and POOL_EXACT_TIMING (0: off, the default - entries differ in any decision byte).  POOL_BY_OBSTACLE | POOL_BY_CAR_CAR keeps
+        one entry per manoeuvre: which side of each obstacle, which order of the cars, not at which step.  Returns the library's code: 0, < 0 when
+        the value is refused (the previous setting stays)"""
+        return int(self._L.miqp_solver_set_pool_filter(self._h, int(families)))
+
+    def solutionPoolFoundDecisions(self, k):
+        """the decision bytes of entry ``k`` as the search kept it (int8 array; before any refinement), None when there is no such entry; needs no device"""
+        d = (C.c_int * 6)()
+        if self._L.miqp_solver_get_dims(self._h, d) != 0:
+            return None
+        out = np.empty(_decision_len(d[0], d[1], d[4]), dtype=np.int8)
+        rc = self._L.miqp_solver_pool_found_decisions(self._h, int(k), out.ctypes.data_as(C.POINTER(C.c_byte)), out.size)
+        return out if rc == out.size else None
+
+    def poolSignature(self, record, families):
+        """the signature of a RawResults record of this wrapper's instance under ``families`` (int8 array): the record's fix record, then
+        pool_signature.  Needs no device.  Raises ValueError where the library refuses the arguments."""
+        d = (C.c_int * 6)()
+        if self._L.miqp_solver_get_dims(self._h, d) != 0 and (self._push_inputs() != 0 or self._L.miqp_solver_get_dims(self._h, d) != 0):   # (a loaded instance is kept: loading drops its pool)
+            raise ValueError("invalid parameters")
+        out = np.empty(_decision_len(d[0], d[1], d[4]), dtype=np.int8)
+        rc = self._L.miqp_solver_pool_signature(self._h, C.byref(record.to_c()), int(families), out.ctypes.data_as(C.POINTER(C.c_byte)), out.size)
+        if rc != out.size:
+            raise ValueError("miqp_solver_pool_signature refused the arguments (%d)" % rc)
+        return out
 
     def solutionPoolCount(self):
         """entries the last solve kept (0 with the pool off, before a solve, without a solution, after new parameters); needs no device.  Behind
