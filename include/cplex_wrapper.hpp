@@ -226,6 +226,25 @@ class CplexWrapper {
     unpackPod(p, *out);
     return out;
   }
+  // improveSolutionPool: every kept entry of a FILTERED pool hill-climbed inside its own class on the device (miqp_solver_pool_improve), one result
+  // per entry in pool order; returns the number of entries that moved, < 0 on failure (-2: the filter is not in 1 .. 15; the pool is untouched then).
+  // Call solveSolutionPool afterwards.  solveDecisions: n decision records of decisions.size() / n bytes each (miqp_solver_solve_decisions).
+  int improveSolutionPool(std::vector<miqp_pool_improve_c>& results, int max_passes = 8) {
+    results.assign(h_ ? (size_t)std::max(1, miqp_solver_pool_count(h_)) : 1, miqp_pool_improve_c{std::nan(""), std::nan(""), 0, 1});
+    if (!h_) { results.clear(); return -1; }
+    const int n = miqp_solver_pool_count(h_);
+    const int rc = miqp_solver_pool_improve(h_, max_passes, results.data(), (int)results.size());
+    results.resize(rc >= 0 ? (size_t)n : 0);
+    return rc;
+  }
+  int solveDecisions(const std::vector<signed char>& decisions, int n, std::vector<miqp_fixed_result_c>& results, int* best = nullptr) {
+    results.assign(n > 0 ? (size_t)n : 0, miqp_fixed_result_c{2, -1, 0, 0, std::nan(""), std::nan("")});
+    int d[6];
+    if (!h_ || n <= 0 || miqp_solver_get_dims(h_, d) != 0) return -1;
+    const size_t D = (size_t)d[0] * d[1] * 6 + (size_t)d[0] * d[4] * d[1] * 5 + (size_t)(d[0] * (d[0] - 1) / 2) * d[1] * 4;
+    if (decisions.size() < D * (size_t)n) return -1;
+    return miqp_solver_solve_decisions(h_, decisions.data(), n, results.data(), best);
+  }
   SolutionProperties getSolutionProperties() const { return solutionProperties_; }
   void setDebugOutputPrint(bool v) { print_debug_outputs_ = v; }
   void setDebugOutputFilePath(std::string in) { debugOutputFilePath_ = in; }

@@ -318,6 +318,44 @@ int miqp_solver_solve_fixed_multi(miqp_solver_t* const* solvers, int n, const mi
  * that handle says so), else 0.  No reference counterpart. */
 int miqp_solver_pool_solve_multi(miqp_solver_t* const* solvers, int n, miqp_fixed_result_c* out, int cap, int* counts);
 
+/* ---- the kept entries of a FILTERED pool improved inside their manoeuvre classes.  The filter keeps, of each class, the smallest
+ * leaf the search happened to evaluate; the best trajectory of the class usually changes its alternatives at other steps.  No reference counterpart. ----
+ * A MOVE is (first, stride, count, value): the decision bytes d[first + k * stride], k < count, take `value`.  Of every site (one disjunction along
+ * the horizon, bytes b[i]) and every change point i = 2 .. N - 1 (b[i] != b[i - 1], both decided): L1 b[i] := b[i - 1]; L2 b[i], b[i + 1] := b[i - 1]
+ * when i + 1 < N; E1 b[i - 1] := b[i]; E2 b[i - 2], b[i - 1] := b[i] when i - 2 >= 1.  Step 0 is never written.  A move is kept when the site's
+ * family is not in `families` or the site's signature under `families` is the same behind it.  Order: site, change point, L1 L2 E1 E2; at most
+ * miqp_gpu_pool_moves_max() per record, the first ones in that order.
+ * miqp_gpu_pool_moves: the kept moves of a record of D decision bytes, 4 ints each, into moves4[4 * cap].  Returns their number; -1 NULL pointers or
+ * a non-positive dimension, -2 families outside 1 .. 15 (without a family, or with MIQP_POOL_EXACT_TIMING, every move changes the signature), -3 cap
+ * too small.  Pure host code: no handle, no device. */
+int miqp_gpu_pool_moves(int cars, int steps, int obstacles, int families, const signed char* decisions, int* moves4, int cap);
+int miqp_gpu_pool_moves_max(void);
+/* sizeof(miqp_pool_improve_c) of the built library (binding check) */
+int miqp_gpu_pool_improve_size(void);
+/* n decision records of D bytes each (the format of miqp_solver_pool_found_decisions), completed to fix records as the pool's are - every byte behind
+ * D is "none" - and solved as the nodes of one fixed-batch call: contract, return codes and miqp_solver_last_timing are those of
+ * miqp_solver_solve_fixed_batch, every entry is answered bit for bit whatever its place and its neighbours, and miqp_solver_fixed_batch_record hands
+ * out the trajectories.  A record with a byte that is neither -1 (undecided) nor an alternative of its site - a possible region of the car and one of
+ * its half-plane alternatives, an environment piece, an obstacle edge or, for a soft obstacle, max_lines_obstacles, a car/car alternative 0 .. 3 - is
+ * status 2 of that entry and never reaches the device. */
+int miqp_solver_solve_decisions(miqp_solver_t* s, const signed char* decisions, int n, miqp_fixed_result_c* out, int* best);
+/* hill-climbs the first min(count, cap) entries of the handle's pool as found, each inside its own class under the handle's filter, in one
+ * device-resident loop: pass 0 solves the entries' own records at the tight tolerance (out[k].before; an entry that is not feasible there gets
+ * status 1 and is left as it is); every further pass solves all kept moves of every entry that moved in the pass before (all live entries in pass 1)
+ * as nodes of the fixed-batch chain (an entry that did not move is not expanded again: its neighbours are the ones just rejected) and applies, per entry, the feasible neighbour of the lowest objective (ties: the lower move number) when it is
+ * below the entry's objective by more than 1e-9 (1 + |objective|).  Ends when no entry moved or after max_passes passes; the objectives decrease
+ * strictly, so it ends.  Results are a function of the records alone: the call is reproducible bit for bit.
+ * Afterwards miqp_solver_pool_found_decisions reports the improved bytes and miqp_solver_pool_found out[k].after - TIGHT-tolerance objectives from
+ * then on, for the live entries.  Entries keep their places (no re-sort: the found objectives need not ascend any more); entry 0 stays the
+ * incumbent's class and may come out better than the solve's result.  A refined pool the handle held is dropped: run miqp_solver_pool_solve afterwards.
+ * Returns the number of entries with moves > 0; 0 also for an empty pool (no device is touched); -1 invalid arguments / no instance; -2 the handle's
+ * filter is not in 1 .. 15, or max_passes outside 1 .. 64; -3 no device / kernel image / HIP error, or a shape whose fix record does not fit the
+ * LDS of a workgroup three times (3 x record bytes + 4 x sites > 160 KB: miqp_solver_last_error says so).  On every failure the pool is untouched.
+ * miqp_solver_last_error is cleared at the start of the call.
+ * miqp_solver_last_timing: out[0] the whole call, out[1] of which on the device, out[2] passes run (pass 0 not counted), out[3] neighbours solved,
+ * out[4] their iterations, out[5] 1 when the last allowed pass still accepted a move (miqp_solver_last_error says so), else 0. */
+int miqp_solver_pool_improve(miqp_solver_t* s, int max_passes, miqp_pool_improve_c* out, int cap);
+
 /* 1 when instances of this shape (NrCars, N) have the dual active-set launches - one or two cars, a horizon of up to 20 steps - else 0 (their node
  * relaxations are interior point solves).  Pure host code: no device is needed or touched.  A call switches the launches off with MIQP_AS=0 */
 int miqp_gpu_has_active_set(int num_cars, int num_steps);

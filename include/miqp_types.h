@@ -174,6 +174,14 @@ typedef struct miqp_fixed_result_c {
   double violation; /* worst elastic violation of the node's rows at its solution (feasible: <= 1e-6); NaN for status 2 */
 } miqp_fixed_result_c;
 
+/* Outcome of one entry of miqp_solver_pool_improve: the entry's own QP at the tight tolerance before the climb and its objective behind it. */
+typedef struct miqp_pool_improve_c {
+  double before;    /* objective of the entry's record as found, solved at the tight tolerance (with the constant cost of step 0) */
+  double after;     /* objective of the record the call leaves; the bits of `before` exactly when moves == 0 */
+  int moves;        /* accepted moves, at most one per pass */
+  int status;       /* 0; 1 the entry's own QP did not come out feasible at the tight tolerance: the entry is left as it was */
+} miqp_pool_improve_c;
+
 #ifdef __cplusplus
 }
 #endif

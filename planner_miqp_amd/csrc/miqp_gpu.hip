@@ -1684,6 +1684,7 @@ bool solve_batch_impl(miqp_solver_t* const* S, int n, int* statuses, const Split
 #include "fixed_batch.hip"
 #include "solution_pool.hip"
 #include "fixed_multi.hip"
+#include "pool_improve.hip"
 
 // ================================================================================================
 //  C ABI

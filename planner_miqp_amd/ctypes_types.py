@@ -99,6 +99,11 @@ class FixedResultC(C.Structure):
                 ("objective", C.c_double), ("violation", C.c_double)]
 
 
+class PoolImproveC(C.Structure):
+    """miqp_pool_improve_c (include/miqp_types.h): one entry of CplexWrapper.improveSolutionPool"""
+    _fields_ = [("before", C.c_double), ("after", C.c_double), ("moves", C.c_int), ("status", C.c_int)]
+
+
 class SolverOptsC(C.Structure):
     _fields_ = [("precision", C.c_int), ("device", C.c_int), ("nodes_per_round", C.c_int),
                 ("max_open_nodes", C.c_int), ("gap_override", C.c_double), ("verbose", C.c_int)]

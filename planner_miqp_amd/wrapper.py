@@ -12,7 +12,7 @@ import numpy as np
 # (four concurrent launches per round + the null stream: see miqp_gpu.hip - effective when set before the process's first HIP call)
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
-from .ctypes_types import (Certificate, CertificateC, FixedResultC, ModelParameters, ModelParamsC, RawResults, RawResultsC, SolutionPropertiesC, SolverOptsC,
+from .ctypes_types import (Certificate, CertificateC, FixedResultC, ModelParameters, ModelParamsC, PoolImproveC, RawResults, RawResultsC, SolutionPropertiesC, SolverOptsC,
                            c_double_p)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -110,6 +110,13 @@ def load_library():
     L.miqp_gpu_pool_signature.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_byte), C.POINTER(C.c_byte), C.c_int]
     L.miqp_solver_pool_signature.restype = C.c_int; L.miqp_solver_pool_signature.argtypes = [vp, C.POINTER(RawResultsC), C.c_int, C.POINTER(C.c_byte), C.c_int]
     L.miqp_solver_pool_found_decisions.restype = C.c_int; L.miqp_solver_pool_found_decisions.argtypes = [vp, C.c_int, C.POINTER(C.c_byte), C.c_int]
+    L.miqp_gpu_pool_moves.restype = C.c_int
+    L.miqp_gpu_pool_moves.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_byte), C.POINTER(C.c_int), C.c_int]
+    L.miqp_gpu_pool_moves_max.restype = C.c_int; L.miqp_gpu_pool_moves_max.argtypes = []
+    L.miqp_gpu_pool_improve_size.restype = C.c_int; L.miqp_gpu_pool_improve_size.argtypes = []
+    L.miqp_solver_solve_decisions.restype = C.c_int
+    L.miqp_solver_solve_decisions.argtypes = [vp, C.POINTER(C.c_byte), C.c_int, C.POINTER(FixedResultC), C.POINTER(C.c_int)]
+    L.miqp_solver_pool_improve.restype = C.c_int; L.miqp_solver_pool_improve.argtypes = [vp, C.c_int, C.POINTER(PoolImproveC), C.c_int]
     L.miqp_solver_solve_fixed_multi.restype = C.c_int
     L.miqp_solver_solve_fixed_multi.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(C.POINTER(RawResultsC)), C.POINTER(C.c_int), C.POINTER(FixedResultC), C.POINTER(C.c_int)]
     L.miqp_solver_pool_solve_multi.restype = C.c_int
@@ -117,6 +124,9 @@ def load_library():
     if L.miqp_gpu_fixed_result_size() != C.sizeof(FixedResultC):
         raise RuntimeError("libmiqp_gpu.so and ctypes_types.FixedResultC disagree on miqp_fixed_result_c (%d / %d bytes): rebuild the library"
                            % (L.miqp_gpu_fixed_result_size(), C.sizeof(FixedResultC)))
+    if L.miqp_gpu_pool_improve_size() != C.sizeof(PoolImproveC):
+        raise RuntimeError("libmiqp_gpu.so and ctypes_types.PoolImproveC disagree on miqp_pool_improve_c (%d / %d bytes): rebuild the library"
+                           % (L.miqp_gpu_pool_improve_size(), C.sizeof(PoolImproveC)))
     L.miqp_gpu_version.restype = C.c_char_p
     _LIB = L
     return L
@@ -139,7 +149,8 @@ EXPORTED_SYMBOLS = ["miqp_solver_create", "miqp_solver_destroy", "miqp_solver_se
                     "miqp_solver_solve_fixed_batch", "miqp_solver_fixed_batch_record", "miqp_gpu_fixed_result_size", "miqp_gpu_fixed_batch_chunk",
                     "miqp_solver_set_pool", "miqp_solver_pool_count", "miqp_solver_pool_found", "miqp_solver_pool_solve", "miqp_solver_pool_record", "miqp_gpu_pool_max",
                     "miqp_solver_solve_fixed_multi", "miqp_solver_pool_solve_multi",
-                    "miqp_solver_set_pool_filter", "miqp_gpu_pool_signature", "miqp_solver_pool_signature", "miqp_solver_pool_found_decisions"]
+                    "miqp_solver_set_pool_filter", "miqp_gpu_pool_signature", "miqp_solver_pool_signature", "miqp_solver_pool_found_decisions",
+                    "miqp_gpu_pool_moves", "miqp_gpu_pool_moves_max", "miqp_gpu_pool_improve_size", "miqp_solver_solve_decisions", "miqp_solver_pool_improve"]
 
 
 # a row of CplexWrapper.launchPlan (NodeLaunch in csrc/miqp_gpu.hip)
@@ -173,6 +184,29 @@ def pool_signature(cars, steps, obstacles, families, decisions):
     if rc != D:
         raise ValueError("miqp_gpu_pool_signature refused the arguments (%d)" % rc)
     return out
+
+
+def pool_moves_max():
+    """most moves pool_moves and CplexWrapper.improveSolutionPool take of one record (a constant of the built library; needs no device)"""
+    return int(load_library().miqp_gpu_pool_moves_max())
+
+
+def pool_moves(cars, steps, obstacles, families, decisions):
+    """the timing moves of a record's D decision bytes that keep its signature under ``families`` (miqp_gpu_pool_moves): an int32 array [n, 4] of
+    (first, stride, count, value) - the bytes decisions[first + k * stride], k < count, take value - in the order site, change point, later by one,
+    later by two, earlier by one, earlier by two; at most pool_moves_max().  A pure function on bytes: needs no wrapper and no device.  Raises
+    ValueError where the library refuses the arguments (families outside 1 .. 15)."""
+    d = np.ascontiguousarray(decisions, dtype=np.int8)
+    D = _decision_len(int(cars), int(steps), int(obstacles))
+    if d.ndim != 1 or d.size < D or D <= 0:
+        raise ValueError("%d decision bytes given, the shape has %d" % (d.size, D))
+    cap = pool_moves_max()
+    out = np.empty((cap, 4), dtype=np.int32)
+    n = load_library().miqp_gpu_pool_moves(int(cars), int(steps), int(obstacles), int(families), d.ctypes.data_as(C.POINTER(C.c_byte)),
+                                           out.ctypes.data_as(C.POINTER(C.c_int)), cap)
+    if n < 0:
+        raise ValueError("miqp_gpu_pool_moves refused the arguments (%d)" % n)
+    return out[:n].copy()
 
 
 def pool_max():
@@ -555,6 +589,39 @@ class CplexWrapper:
         a = np.frombuffer(out, dtype=np.dtype([("status", "<i4"), ("route", "<i4"), ("iterations", "<i4"), ("reserved", "<i4"),
                                                ("objective", "<f8"), ("violation", "<f8")]), count=m)
         return (a["status"].copy(), a["objective"].copy(), a["violation"].copy(), a["iterations"].copy(), a["route"].copy())
+
+    def improveSolutionPool(self, max_passes=8):
+        """every kept entry of a FILTERED pool hill-climbed inside its own class in one device-resident loop (miqp_solver_pool_improve): per pass
+        all timing moves of pool_moves of every entry that still moves are solved at the tight tolerance and the best improving one is applied.
+        Returns (rc, before, after, moves, status): rc the number of entries that moved - or the library's code < 0: -2 the filter is not in
+        1 .. 15 or max_passes not in 1 .. 64, -3 no device; the pool is untouched then - and numpy arrays in pool order (empty for rc < 0).
+        Behind it solutionPoolFoundDecisions / solutionPoolFound report the improved records and their tight-tolerance objectives; entries keep
+        their places.  A refined pool is dropped: call solveSolutionPool afterwards."""
+        n = max(self.solutionPoolCount(), 1)
+        out = (PoolImproveC * n)()
+        rc = int(self._L.miqp_solver_pool_improve(self._h, int(max_passes), out, n))
+        m = min(self.solutionPoolCount(), n) if rc >= 0 else 0
+        a = np.frombuffer(out, dtype=np.dtype([("before", "<f8"), ("after", "<f8"), ("moves", "<i4"), ("status", "<i4")]), count=m)
+        return rc, a["before"].copy(), a["after"].copy(), a["moves"].copy(), a["status"].copy()
+
+    def solveDecisions(self, decisions):
+        """the continuous QPs of many DECISION records of this wrapper's instance in one device call (miqp_solver_solve_decisions): ``decisions`` is
+        an int8 array [n, D] of records as solutionPoolFoundDecisions hands them out.  Returns (rc, status, objective, violation, iterations,
+        route, best) as solveFixedBatch does, with the library's code in front instead of an exception: 0, -3 without a device (every status
+        is 2 then).  A record with a byte outside its site's alternatives is status 2 of that entry.  fixedBatchRecord(k) works behind it."""
+        d = np.ascontiguousarray(decisions, dtype=np.int8)
+        dims = (C.c_int * 6)()
+        if self._L.miqp_solver_get_dims(self._h, dims) != 0 and (self._push_inputs() != 0 or self._L.miqp_solver_get_dims(self._h, dims) != 0):   # (a loaded instance is kept: loading drops its pool)
+            raise RuntimeError("invalid parameters")
+        D = _decision_len(dims[0], dims[1], dims[4])
+        if d.ndim != 2 or d.shape[1] != D:
+            raise ValueError("decision records of %d bytes expected, got an array of shape %s" % (D, d.shape))
+        n = d.shape[0]
+        out = (FixedResultC * max(n, 1))()
+        best = C.c_int(-1)
+        rc = int(self._L.miqp_solver_solve_decisions(self._h, d.ctypes.data_as(C.POINTER(C.c_byte)), n, out, C.byref(best)))
+        a = np.frombuffer(out, dtype=_FIXED_RESULT_DTYPE, count=n)
+        return (rc, a["status"].copy(), a["objective"].copy(), a["violation"].copy(), a["iterations"].copy(), a["route"].copy(), best.value)
 
     def solutionPoolRecord(self, k):
         """(rc, RawResults) of entry ``k`` of the last solveSolutionPool: rc 0 and the record; rc 1 (the entry did not come out feasible at the
