@@ -355,6 +355,37 @@ int miqp_solver_solve_decisions(miqp_solver_t* s, const signed char* decisions, 
  * miqp_solver_last_timing: out[0] the whole call, out[1] of which on the device, out[2] passes run (pass 0 not counted), out[3] neighbours solved,
  * out[4] their iterations, out[5] 1 when the last allowed pass still accepted a move (miqp_solver_last_error says so), else 0. */
 int miqp_solver_pool_improve(miqp_solver_t* s, int max_passes, miqp_pool_improve_c* out, int cap);
+/* the climb of miqp_solver_pool_improve over the pools of n handles in one device call: one device lock, one context of the handles'
+ * common Layout, the instances compiled on host threads and their tables uploaded once.  One pass of the call is one pass of every handle that still
+ * moves; the neighbours of all handles fill common launch groups of miqp_gpu_fixed_batch_chunk nodes, and the host waits for the device once per pass.
+ * For every handle h the call answers what miqp_solver_pool_improve(solvers[h], max_passes, ., cap) answers for that handle alone, bit for bit:
+ * counts[h] = min(miqp_solver_pool_count(solvers[h]), cap), out[h * cap + k], k < counts[h], the entry's before / after / moves / status, and
+ * miqp_solver_pool_found_decisions, miqp_solver_pool_found and the dropped refined pool behind the call are those of the single call.  The handles
+ * may differ in their filters.  A handle stops exactly when the single call's loop would stop for it (its move total of a pass is 0); a handle
+ * whose entries have all stopped contributes no nodes to later passes.  The call ends when no handle moved or after max_passes passes.
+ * DIFFERENCE from the single call: a handle that kept nothing (pool off, no solution) gets counts[h] = 0 and is left alone WHATEVER ITS FILTER -
+ * the single call checks the filter first and answers -2 for such a handle without one; its miqp_solver_last_error and miqp_solver_last_timing
+ * stay what they were.
+ * Returns the number of entries with moves > 0, summed over the handles.  -1: NULL arrays, n <= 0, cap < 1, a NULL handle, a handle without an
+ * instance, a handle named twice, or a kept pool whose record length differs from the common Layout's.  -2: max_passes outside 1 .. 64; handles that
+ * do not share a shape or name different devices (as miqp_solver_solve_fixed_multi refuses them, with its text as the handles' last error); a handle
+ * that kept entries and whose filter is outside 1 .. 15 (its miqp_solver_last_error names it).  -5: more than 65536 entries in all.  -3: no device /
+ * kernel image / HIP error (an allocation that failed is one), or the LDS refusal of miqp_solver_pool_improve.  -1, -2 and -5 are found before any
+ * device is touched; on EVERY failure out, counts and every pool of the call are untouched.  A call in which no handle kept anything returns 0
+ * (counts all 0) without touching a device.
+ * Device memory: entries x (record + miqp_gpu_pool_moves_max() x 16 bytes + a few words) beside the fixed buffers of the single call, whatever the
+ * number of neighbours; cached per device, grown, not shrunk.
+ * miqp_solver_last_timing of every handle that kept entries: out[0] the whole call, out[1] of which on the device (both of the CALL); out[2] passes in which the handle
+ * had neighbours, out[3] the handle's neighbours solved, out[4] their iterations, out[5] 1 when an entry of the handle was still accepted in pass
+ * max_passes (miqp_solver_last_error of that handle says so), else 0 - out[2 .. 5] are the single call's.  No reference counterpart. */
+int miqp_solver_pool_improve_multi(miqp_solver_t* const* solvers, int n, int max_passes, miqp_pool_improve_c* out, int cap, int* counts);
+/* the SLICES of a pass of the climb: the results of a pass are kept a slice at a time, a slice being a run of whole entries whose neighbours fit 8192
+ * results (16 x miqp_gpu_pool_moves_max()).  move_counts[e], e < entries: the moves of entry e, clamped to 0 .. miqp_gpu_pool_moves_max() as the
+ * kernels clamp them.  Slices are formed greedily in entry order: an entry opens a new slice when its moves do not fit what is left of the current
+ * one.  slice_first[s] receives the first entry of slice s, slice_first[nslices] = entries.  Returns nslices (>= 1); -1 NULL pointers, entries <= 0
+ * or cap < 0; -3 cap < nslices + 1 (nothing is written).  Pure host code - no handle, no device - and the function the host loop of
+ * miqp_solver_pool_improve_multi itself calls. */
+int miqp_gpu_pool_improve_plan(const int* move_counts, int entries, int* slice_first, int cap);
 
 /* 1 when instances of this shape (NrCars, N) have the dual active-set launches - one or two cars, a horizon of up to 20 steps - else 0 (their node
  * relaxations are interior point solves).  Pure host code: no device is needed or touched.  A call switches the launches off with MIQP_AS=0 */

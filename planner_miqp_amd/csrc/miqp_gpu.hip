@@ -1685,6 +1685,7 @@ bool solve_batch_impl(miqp_solver_t* const* S, int n, int* statuses, const Split
 #include "solution_pool.hip"
 #include "fixed_multi.hip"
 #include "pool_improve.hip"
+#include "pool_improve_multi.hip"
 
 // ================================================================================================
 //  C ABI

@@ -18,13 +18,18 @@
 //
 // The climb, per pass, all on the solver stream:
 //   pool_moves_kernel      one wavefront per entry: the record staged in LDS, one lane per site (in a loop when there are more sites than lanes)
-//                          counts its kept moves, a wave scan over the per-site counts numbers them, the lanes write them to the move table in HBM
-//   pool_neighbour_kernel  one wavefront per node of the chunk being launched: neighbour number -> (entry, move) through the per-entry counts, the
-//                          entry's current record in 16-byte loads, the move patched in registers, 16-byte stores into slot k of pool_fix
+//                          counts its kept moves under the ENTRY's filter, a wave scan over the per-site counts numbers them, the lanes write them
+//                          to the move table in HBM
+//   pool_offsets_kernel    one workgroup: the exclusive scan of the per-entry counts, off[0 .. m] - neighbour off[e] + j is move j of entry e
+//   pool_neighbour_kernel  one wavefront per node of the chunk being launched: neighbour number -> (entry, move) by binary search in the scan, the
+//                          entry's current record in 16-byte loads, the move patched in registers, 16-byte stores into slot k of pool_fix; the
+//                          entry's instance into slot k of batch_inst
 //   launch_ipm_batch       the chain of the fixed batch with its settings (QP_TOL_FINAL, no cutoff, cold start), fixed_batch_collect_kernel behind it
 //   pool_pick_kernel       one wavefront per entry over its contiguous range of results: the feasible neighbour of the lowest objective, ties to the
 //                          lower move number; accepted when it is below the entry's objective by more than 1e-9 (1 + |objective|) - then the move is
 //                          patched into the entry's current record and the objective replaced
+// The kernels serve the entries of MANY handles as well (pool_improve_multi.hip: per entry its handle's index and filter; the results of a pass kept a
+// SLICE of entries at a time); this file's call is their one-handle case - every entry instance 0 and the handle's filter, one slice.
 // Owner computes: no atomics, no lock, no wavefront waits on another, no scratch.  The host reads back, per pass, one (accepted, iterations,
 // objective) triple and one move count per entry.  An entry that did not move in a pass is not expanded again: its record, hence its neighbours and
 // their answers, would be the ones just rejected.  (The literal loop - every live entry expanded in every pass - ends on the same records and
@@ -85,9 +90,12 @@ struct PoolWord { int accepted, iterations; double objective; };   // what the h
 
 struct PoolImproveArgs {
   signed char* cur; double* cur_obj; int* act; int* cnt; int4* moves; PoolWord* words;   // per entry: current record and objective, expand it in the next pass, moves of this pass
-  const miqp_fixed_result_c* res;   // of the pass's first neighbour
+  const int* ent_inst; const int* ent_fam;   // per entry: its handle's index in the call (0 in the single call) and that handle's filter
+  int* off;                         // [m + 1] exclusive scan of the clamped move counts (pool_offsets_kernel): neighbour off[e] + j is move j of entry e, off[m] the pass total
+  const miqp_fixed_result_c* res;   // of the first node of the SLICE being picked (a slice: a run of whole entries whose nodes fit NB_MAX results)
   signed char* pool_fix;            // the chain's fix records: slot k of the chunk
-  PoolDims dims; int fam, fixlen, m;
+  int* batch_inst;                  // the chain's instance of slot k
+  PoolDims dims; int fixlen, m;     // (one shape for every handle of a call: batch_layout)
 };
 
 __global__ __launch_bounds__(64) void pool_moves_kernel(const PoolImproveArgs A) {
@@ -101,9 +109,10 @@ __global__ __launch_bounds__(64) void pool_moves_kernel(const PoolImproveArgs A)
   for (int c = lane; c < chunks; c += 64) { rec4[c] = src[c]; sg04[c] = make_uint4(~0u, ~0u, ~0u, ~0u); sg14[c] = make_uint4(~0u, ~0u, ~0u, ~0u); }
   __syncthreads();
   // (a site reads and writes its own bytes of the three blocks and no others: the lanes do not meet until the scan)
+  const int fam = A.ent_fam[e];
   for (int s = lane; s < nsites; s += 64) {
-    pool_site_signature(A.dims, A.fam, s, rec, sg0);
-    scnt[s] = pool_site_moves(A.dims, A.fam, s, rec, sg0, sg1, [](int, const PoolMove&) {});
+    pool_site_signature(A.dims, fam, s, rec, sg0);
+    scnt[s] = pool_site_moves(A.dims, fam, s, rec, sg0, sg1, [](int, const PoolMove&) {});
   }
   __syncthreads();
   int total = 0;   // exclusive scan of the per-site counts, 64 sites at a time
@@ -119,7 +128,7 @@ __global__ __launch_bounds__(64) void pool_moves_kernel(const PoolImproveArgs A)
   for (int s = lane; s < nsites; s += 64) {
     const int off = scnt[s];
     if (off >= POOL_MOVES_MAX) continue;
-    (void)pool_site_moves(A.dims, A.fam, s, rec, sg0, sg1, [&](int j, const PoolMove& mv) { if (off + j < POOL_MOVES_MAX) out[off + j] = make_int4(mv.first, mv.stride, mv.count, mv.value); });
+    (void)pool_site_moves(A.dims, fam, s, rec, sg0, sg1, [&](int j, const PoolMove& mv) { if (off + j < POOL_MOVES_MAX) out[off + j] = make_int4(mv.first, mv.stride, mv.count, mv.value); });
   }
   if (lane == 0) A.cnt[e] = min(total, POOL_MOVES_MAX);
 }
@@ -131,16 +140,43 @@ __device__ inline void pool_patch_byte(uint4& v, int p, int val) {   // byte p (
   v.z = w == 2 ? (v.z & keep) | bits : v.z; v.w = w == 3 ? (v.w & keep) | bits : v.w;
 }
 
-// nodes c0 .. c0 + bc - 1 of the pass into slots 0 .. bc - 1 of pool_fix; own: pass 0, node e is entry e's own record
+// off[0 .. m] behind pool_moves_kernel: ONE workgroup, tiles of 256 entries - a wave scan per wavefront, the four wavefront totals through LDS, the
+// running total of the tiles before in a register of every lane.  m <= 65536 entries of at most 512 moves: a pass total is at most 2^25
+__global__ __launch_bounds__(256) void pool_offsets_kernel(const PoolImproveArgs A) {
+  __shared__ int carry[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int base = 0;
+  for (int t0 = 0; t0 < A.m; t0 += 256) {   // (A.m is uniform: every lane meets every barrier)
+    const int e = t0 + tid;
+    const int c = e < A.m ? min(max(A.cnt[e], 0), POOL_MOVES_MAX) : 0;
+    int x = c;
+    for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(x, o, 64); if (lane >= o) x += y; }
+    if (lane == 63) carry[wave] = x;
+    __syncthreads();
+    int before = 0;
+    for (int w = 0; w < 4; ++w) before += w < wave ? carry[w] : 0;
+    if (e < A.m) A.off[e] = base + before + x - c;
+    base += carry[0] + carry[1] + carry[2] + carry[3];
+    __syncthreads();
+  }
+  if (tid == 0) A.off[A.m] = base;
+}
+
+// nodes c0 .. c0 + bc - 1 of the pass into slots 0 .. bc - 1 of pool_fix and batch_inst; own: pass 0, node e is entry e's own record.  Else node g is
+// move g - off[e] of the entry e with off[e] <= g < off[e + 1]: a binary search of at most 17 probes, the same in every lane of the wavefront
 __global__ __launch_bounds__(256) void pool_neighbour_kernel(const PoolImproveArgs A, int c0, int bc, int own) {
   const int lane = threadIdx.x & 63, slot = blockIdx.x * 4 + (threadIdx.x >> 6), chunks = A.fixlen >> 4;
   if (slot >= bc) return;
   int e = c0 + slot, j = -1;
   if (!own) {
-    j = c0 + slot;
-    for (e = 0; e < A.m; ++e) { const int c = min(max(A.cnt[e], 0), POOL_MOVES_MAX); if (j < c) break; j -= c; }
+    const int g = c0 + slot;
+    if (g < 0 || g >= A.off[A.m]) return;
+    int lo = 0, hi = A.m;   // off[lo] <= g < off[hi]
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (A.off[mid] <= g) lo = mid; else hi = mid; }
+    e = lo; j = g - A.off[lo];
+    if (j >= POOL_MOVES_MAX) return;
   }
-  if (e >= A.m) return;
+  if (e < 0 || e >= A.m) return;
   const int4 mv = j >= 0 ? A.moves[(size_t)e * POOL_MOVES_MAX + j] : make_int4(0, 1, 0, 0);
   const uint4* src = (const uint4*)(A.cur + (size_t)e * A.fixlen);
   uint4* dst = (uint4*)(A.pool_fix + (size_t)slot * A.fixlen);
@@ -149,21 +185,24 @@ __global__ __launch_bounds__(256) void pool_neighbour_kernel(const PoolImproveAr
     for (int k = 0; k < mv.z; ++k) { const int p = mv.x + k * mv.y - c * 16; if ((unsigned)p < 16u) pool_patch_byte(v, p, mv.w); }
     dst[c] = v;
   }
+  if (lane == 0) A.batch_inst[slot] = A.ent_inst[e];
 }
 
-__global__ __launch_bounds__(64) void pool_pick_kernel(const PoolImproveArgs A, int own) {
-  const int e = blockIdx.x, lane = threadIdx.x;
+// entries e0 .. e0 + gridDim.x - 1: one slice, whose first node's result is A.res[0]; nb_max: results the buffer behind A.res holds
+__global__ __launch_bounds__(64) void pool_pick_kernel(const PoolImproveArgs A, int e0, int nb_max, int own) {
+  const int e = e0 + blockIdx.x, lane = threadIdx.x;
+  if (e >= A.m) return;
   if (own) {
-    if (lane == 0) {
-      const miqp_fixed_result_c r = A.res[e]; const int live = r.status == 0 ? 1 : 0;
+    if (lane == 0 && (int)blockIdx.x < nb_max) {
+      const miqp_fixed_result_c r = A.res[blockIdx.x]; const int live = r.status == 0 ? 1 : 0;
       A.cur_obj[e] = r.objective; A.act[e] = live;
       A.words[e] = PoolWord{live, r.iterations, r.objective};
     }
     return;
   }
-  int off = 0;
-  for (int q = 0; q < e; ++q) off += min(max(A.cnt[q], 0), POOL_MOVES_MAX);
-  const int n = A.act[e] ? min(max(A.cnt[e], 0), POOL_MOVES_MAX) : 0;
+  const int off = A.off[e] - A.off[e0];
+  int n = A.act[e] ? min(max(A.cnt[e], 0), POOL_MOVES_MAX) : 0;
+  if (off < 0 || off + n > nb_max) n = 0;   // (the host forms the slices so that this does not happen: miqp_gpu_pool_improve_plan)
   const double cur = A.cur_obj[e];
   double bo = 1e308; int bj = 0x7FFFFFFF, it = 0;
   for (int j = lane; j < n; j += 64) {   // (a lane's moves ascend: a tie keeps the lower number)
@@ -195,6 +234,7 @@ struct PoolImproveDev {
   signed char* cur = nullptr; size_t cur_cap = 0; double* Z = nullptr; size_t z_cap = 0;
   double* cur_obj = nullptr; int* act = nullptr; int* cnt = nullptr; int4* moves = nullptr; PoolWord* words = nullptr;
   miqp_fixed_result_c* res = nullptr; double* best_obj = nullptr; int* best_idx = nullptr;
+  int* ent_inst = nullptr; int* ent_fam = nullptr; int* off = nullptr;   // what the kernels read per entry since they serve many handles: 0, the handle's filter; the scan
   static constexpr int NB_MAX = MIQP_POOL_MAX * POOL_MOVES_MAX;   // neighbours of a pass
   bool ensure(size_t fl, size_t row) {
     // (each of the fixed-size buffers on its own: an allocation that failed half-way is taken up where it stopped, nothing is allocated twice)
@@ -206,6 +246,9 @@ struct PoolImproveDev {
     if (!best_obj) HIP_OK(hipMalloc((void**)&best_obj, (NB_MAX / FB_CHUNK + 1) * sizeof(double)));
     if (!best_idx) HIP_OK(hipMalloc((void**)&best_idx, (NB_MAX / FB_CHUNK + 1) * sizeof(int)));
     if (!moves) HIP_OK(hipMalloc((void**)&moves, (size_t)NB_MAX * sizeof(int4)));
+    if (!ent_inst) HIP_OK(hipMalloc((void**)&ent_inst, MIQP_POOL_MAX * sizeof(int)));
+    if (!ent_fam) HIP_OK(hipMalloc((void**)&ent_fam, MIQP_POOL_MAX * sizeof(int)));
+    if (!off) HIP_OK(hipMalloc((void**)&off, (MIQP_POOL_MAX + 1) * sizeof(int)));
     if (MIQP_POOL_MAX * fl > cur_cap) {
       if (cur) (void)hipFree(cur);
       cur = nullptr; cur_cap = 0;
@@ -243,10 +286,13 @@ bool pool_improve_run(DevCtx& X, PoolImproveDev& G, const FixedBatchCall& call, 
   HIP_OK(hipMemsetAsync(B.batch_inst, 0, (size_t)FB_CHUNK * 4, st));
   HIP_OK(hipMemcpyAsync(G.cur, fix, (size_t)m * fl, hipMemcpyHostToDevice, st));
   HIP_OK(hipMemsetAsync(G.cnt, 0, MIQP_POOL_MAX * sizeof(int), st)); HIP_OK(hipMemsetAsync(G.act, 0, MIQP_POOL_MAX * sizeof(int), st));
+  HIP_OK(hipMemsetAsync(G.ent_inst, 0, MIQP_POOL_MAX * sizeof(int), st)); HIP_OK(hipMemsetAsync(G.off, 0, (MIQP_POOL_MAX + 1) * sizeof(int), st));
+  HIP_OK(hipMemsetD32Async((hipDeviceptr_t)G.ent_fam, fam, MIQP_POOL_MAX, st));
   DevBuf Bp = B; Bp.qp_tol = QP_TOL_FINAL; Bp.use_cutoff = 0; Bp.ws_on = 0;
   PoolImproveArgs A;
   A.cur = G.cur; A.cur_obj = G.cur_obj; A.act = G.act; A.cnt = G.cnt; A.moves = G.moves; A.words = G.words; A.res = G.res; A.pool_fix = B.pool_fix;
-  A.dims = dims; A.fam = fam; A.fixlen = (int)fl; A.m = m;
+  A.ent_inst = G.ent_inst; A.ent_fam = G.ent_fam; A.off = G.off; A.batch_inst = B.batch_inst;
+  A.dims = dims; A.fixlen = (int)fl; A.m = m;
   const size_t gen_lds = 3 * fl + (size_t)pool_sites(dims) * sizeof(int);
   if (gen_lds > POOL_MOVES_LDS_MAX) { O.err = "miqp_solver_pool_improve: the fix record of this shape does not fit the LDS of pool_moves_kernel three times"; std::fprintf(stderr, "[miqp_gpu] %s (%zu bytes)\n", O.err.c_str(), gen_lds); return false; }
   HIP_OK(hipFuncSetAttribute((const void*)pool_moves_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gen_lds));
@@ -273,8 +319,9 @@ bool pool_improve_run(DevCtx& X, PoolImproveDev& G, const FixedBatchCall& call, 
   // behind a pass: its pick, the moves of the next one, and the words of both to the host
   std::vector<PoolWord> words(m); std::vector<int> cnt(m);
   auto finish_pass = [&](int own) -> bool {
-    hipLaunchKernelGGL(pool_pick_kernel, dim3(m), dim3(64), 0, st, A, own);
+    hipLaunchKernelGGL(pool_pick_kernel, dim3(m), dim3(64), 0, st, A, 0, (int)PoolImproveDev::NB_MAX, own);   // (at most MIQP_POOL_MAX entries: one slice)
     hipLaunchKernelGGL(pool_moves_kernel, dim3(m), dim3(64), gen_lds, st, A);
+    hipLaunchKernelGGL(pool_offsets_kernel, dim3(1), dim3(256), 0, st, A);
     HIP_OK(hipGetLastError());
     HIP_OK(hipEventRecord(X.ev1, st));
     HIP_OK(hipMemcpyAsync(words.data(), G.words, (size_t)m * sizeof(PoolWord), hipMemcpyDeviceToHost, st));

@@ -117,6 +117,10 @@ def load_library():
     L.miqp_solver_solve_decisions.restype = C.c_int
     L.miqp_solver_solve_decisions.argtypes = [vp, C.POINTER(C.c_byte), C.c_int, C.POINTER(FixedResultC), C.POINTER(C.c_int)]
     L.miqp_solver_pool_improve.restype = C.c_int; L.miqp_solver_pool_improve.argtypes = [vp, C.c_int, C.POINTER(PoolImproveC), C.c_int]
+    L.miqp_solver_pool_improve_multi.restype = C.c_int
+    L.miqp_solver_pool_improve_multi.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.POINTER(PoolImproveC), C.c_int, C.POINTER(C.c_int)]
+    L.miqp_gpu_pool_improve_plan.restype = C.c_int
+    L.miqp_gpu_pool_improve_plan.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_int]
     L.miqp_solver_solve_fixed_multi.restype = C.c_int
     L.miqp_solver_solve_fixed_multi.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(C.POINTER(RawResultsC)), C.POINTER(C.c_int), C.POINTER(FixedResultC), C.POINTER(C.c_int)]
     L.miqp_solver_pool_solve_multi.restype = C.c_int
@@ -150,7 +154,8 @@ EXPORTED_SYMBOLS = ["miqp_solver_create", "miqp_solver_destroy", "miqp_solver_se
                     "miqp_solver_set_pool", "miqp_solver_pool_count", "miqp_solver_pool_found", "miqp_solver_pool_solve", "miqp_solver_pool_record", "miqp_gpu_pool_max",
                     "miqp_solver_solve_fixed_multi", "miqp_solver_pool_solve_multi",
                     "miqp_solver_set_pool_filter", "miqp_gpu_pool_signature", "miqp_solver_pool_signature", "miqp_solver_pool_found_decisions",
-                    "miqp_gpu_pool_moves", "miqp_gpu_pool_moves_max", "miqp_gpu_pool_improve_size", "miqp_solver_solve_decisions", "miqp_solver_pool_improve"]
+                    "miqp_gpu_pool_moves", "miqp_gpu_pool_moves_max", "miqp_gpu_pool_improve_size", "miqp_solver_solve_decisions", "miqp_solver_pool_improve",
+                    "miqp_solver_pool_improve_multi", "miqp_gpu_pool_improve_plan"]
 
 
 # a row of CplexWrapper.launchPlan (NodeLaunch in csrc/miqp_gpu.hip)
@@ -794,6 +799,46 @@ def solve_solution_pools(wrappers):
         b = a[h * cap:h * cap + counts[h]]
         res.append((b["status"].copy(), b["objective"].copy(), b["violation"].copy(), b["iterations"].copy(), b["route"].copy()))
     return res
+
+
+def improve_solution_pools(wrappers, max_passes=8, cap=None):
+    """the solution pools of many wrappers hill-climbed inside their manoeuvre classes in one device call (miqp_solver_pool_improve_multi): per
+    wrapper (moved, before, after, moves, status) - the arrays its own improveSolutionPool(max_passes) returns, bit for bit, and ``moved`` what
+    that call returns as rc: the wrapper's entries with moves > 0.  ``cap``: entries per wrapper that take part (None: the largest
+    solutionPoolCount() among the wrappers).  The wrappers may differ in their filters; one without a pool gets empty arrays and is left alone.
+    Behind it solutionPoolFoundDecisions / solutionPoolFound of every wrapper report the improved records; call solve_solution_pools afterwards.
+    Raises RuntimeError where the library refuses the call (wrappers of different shape, a wrapper with entries and no filter, no device), on -2
+    with the first non-empty lastError() among the wrappers; a refused call leaves every pool alone."""
+    L = load_library()
+    n = len(wrappers)
+    cap = max([w.solutionPoolCount() for w in wrappers] + [1]) if cap is None else int(cap)
+    out = (PoolImproveC * (max(n, 1) * max(cap, 1)))()
+    counts = (C.c_int * max(n, 1))()
+    hs = (C.c_void_p * max(n, 1))(*[w._h for w in wrappers])
+    rc = L.miqp_solver_pool_improve_multi(hs, n, int(max_passes), out, cap, counts)
+    if rc < 0:
+        why = next((w.lastError() for w in wrappers if w.lastError()), "") if rc == -2 else ""   # (a filterless handle is named in ITS last error)
+        raise RuntimeError("miqp_solver_pool_improve_multi failed (%d)%s" % (rc, ": " + why if why else ""))
+    a = np.frombuffer(out, dtype=np.dtype([("before", "<f8"), ("after", "<f8"), ("moves", "<i4"), ("status", "<i4")]), count=n * cap)
+    res = []
+    for h in range(n):
+        b = a[h * cap:h * cap + counts[h]]
+        res.append((int((b["moves"] > 0).sum()), b["before"].copy(), b["after"].copy(), b["moves"].copy(), b["status"].copy()))
+    return res
+
+
+def pool_improve_plan(move_counts):
+    """the slices of a pass of improve_solution_pools for these per-entry move counts (miqp_gpu_pool_improve_plan): the list slice_first, entry
+    s the first entry of slice s and the last one len(move_counts) - runs of whole entries whose (clamped) moves fit 8192 results, formed greedily
+    in entry order.  Needs no device."""
+    c = np.ascontiguousarray(move_counts, dtype=np.int32)
+    if c.ndim != 1 or c.size == 0:
+        raise ValueError("a non-empty vector of move counts expected")
+    first = np.zeros(c.size + 2, dtype=np.int32)
+    ns = load_library().miqp_gpu_pool_improve_plan(c.ctypes.data_as(C.POINTER(C.c_int)), c.size, first.ctypes.data_as(C.POINTER(C.c_int)), first.size)
+    if ns < 1:
+        raise RuntimeError("miqp_gpu_pool_improve_plan failed (%d)" % ns)
+    return [int(x) for x in first[:ns + 1]]
 
 
 def certify_last_timing():
