@@ -237,6 +237,17 @@ class CplexWrapper {
     results.resize(rc >= 0 ? (size_t)n : 0);
     return rc;
   }
+  // exploreSolutionPool: the free places of a FILTERED pool filled with neighbouring manoeuvre classes on the device (miqp_solver_pool_explore;
+  // IloCplex::populate for a CPLEX user), one record per ADDED entry in pool order behind the old ones; returns their number, < 0 on failure (-2: the
+  // filter is not in 1 .. 15 or has neither MIQP_POOL_BY_OBSTACLE nor MIQP_POOL_BY_CAR_CAR; the pool is untouched then).  max_rel >= 0 admits only
+  // objectives within max_rel * |objective of entry 0| above entry 0's.  Call solveSolutionPool afterwards.
+  int exploreSolutionPool(std::vector<miqp_pool_explore_c>& added, int max_passes = 4, double max_rel = -1.0) {
+    added.assign((size_t)miqp_gpu_pool_max(), miqp_pool_explore_c{-1, 0, 0, 0, 0, 0, 0, 0, std::nan("")});
+    if (!h_) { added.clear(); return -1; }
+    const int rc = miqp_solver_pool_explore(h_, max_passes, max_rel, added.data(), (int)added.size());
+    added.resize(rc > 0 ? (size_t)rc : 0);
+    return rc;
+  }
   int solveDecisions(const std::vector<signed char>& decisions, int n, std::vector<miqp_fixed_result_c>& results, int* best = nullptr) {
     results.assign(n > 0 ? (size_t)n : 0, miqp_fixed_result_c{2, -1, 0, 0, std::nan(""), std::nan("")});
     int d[6];

@@ -387,6 +387,44 @@ int miqp_solver_pool_improve_multi(miqp_solver_t* const* solvers, int n, int max
  * miqp_solver_pool_improve_multi itself calls. */
 int miqp_gpu_pool_improve_plan(const int* move_counts, int entries, int* slice_first, int cap);
 
+/* ---- the free places of a FILTERED pool filled with neighbouring manoeuvre classes (IloCplex::populate for a CPLEX user).  The pool
+ * holds leaves the search evaluated, and the search prunes everything beyond its gap: a manoeuvre that is clearly worse than the optimum but valid -
+ * the car passes the obstacle on the other side - usually never becomes a leaf.  Opt-in, behind the solve; nothing changes unless it is called. ----
+ * A JUMP is a move (first, stride, count, value) of the families MIQP_POOL_BY_OBSTACLE and MIQP_POOL_BY_CAR_CAR that are in `families`; region and
+ * environment sites have none.  A GROUP is the five point-sites of one (car, obstacle) or the four group-sites of one car pair: its bytes of one step
+ * are contiguous.  A RUN of a group or of a single site is a maximal range [i0, i1] inside 1 .. N - 1 over which all its bytes are decided (>= 0) and
+ * constant.  For every run and every alternative v - an obstacle edge 0 .. max_lines - 1 (never the soft alternative max_lines, which a run may hold
+ * and be jumped from), a car/car alternative 0 .. 3 - all bytes of the group (stride 1, one contiguous range) or of the site (its own stride) over
+ * the run take v.  A candidate is skipped when its bytes all hold v already, and when the signature under `families` is the same behind it: for
+ * every site it writes, the nearest decided bytes before and behind the run are (a, v) or (v, a), a the site's byte in the run - the run then
+ * only moves a change point, which is a move of the climb.  So every jump changes the signature.  Step 0 and undecided bytes are never written.
+ * Order: obstacle groups by c * O + o, pairs, then the sites in the order of the signature's sites; inside each the runs by i0, then v ascending; at
+ * most miqp_gpu_pool_moves_max() per record, the first ones in that order.
+ * miqp_gpu_pool_jumps: the jumps of a record of D decision bytes, 4 ints each, into moves4[4 * cap].  Returns their number; -1 NULL pointers, a
+ * non-positive dimension or max_lines < 0; -2 families outside 1 .. 15 or with neither the obstacle nor the car/car family; -3 cap too small.
+ * Pure host code: no handle, no device. */
+int miqp_gpu_pool_jumps(int cars, int steps, int obstacles, int max_lines, int families, const signed char* decisions, int* moves4, int cap);
+/* sizeof(miqp_pool_explore_c) of the built library (binding check) */
+int miqp_gpu_pool_explore_size(void);
+/* one device-resident loop: pass 1 takes the jumps of every kept entry, pass p > 1 those of the entries pass p - 1 added.  All neighbours of a pass
+ * are solved as nodes of the fixed-batch chain at the tight tolerance; then the feasible ones are visited in ascending (objective, neighbour number
+ * - entry by entry, jump by jump), and one whose signature under the handle's filter is not in the pool yet - the entries admitted earlier in the
+ * pass included - is appended while a place is free (the handle's capacity); the first neighbour of a new class is that class's best of the pass.
+ * max_rel < 0: no cost cap; else a neighbour is admitted only when objective - obj0 <= max_rel * |obj0|, obj0 what miqp_solver_pool_found reports
+ * for entry 0 (each operation rounded on its own).  Ends when the pool is full, a pass admitted nothing or had no jumps, or after max_passes passes.
+ * No existing entry is changed or moved.  Results are a function of the records alone: the call is reproducible bit for bit.
+ * Afterwards miqp_solver_pool_count, miqp_solver_pool_found (tight-tolerance objectives for the added entries) and
+ * miqp_solver_pool_found_decisions include the added entries behind the old ones (no re-sort); out[k], k < return value, describes them in that
+ * order.  A refined pool the handle held is dropped; miqp_solver_pool_improve and miqp_solver_pool_solve work on the larger pool as on any other.
+ * Returns the number of entries added; 0 also for an empty or a full pool (no device is touched); -1 invalid arguments (NULL, cap < 0, max_rel NaN)
+ * or no instance; -2 the handle's filter is not in 1 .. 15 or has neither the obstacle nor the car/car family, max_passes outside 1 .. 64, or cap
+ * below the free places; -3 no device / kernel image / HIP error, or a shape whose fix record does not fit the LDS of a workgroup twice beside the
+ * 8192 objectives of a pass (2 x record bytes + 64 KB > 160 KB: miqp_solver_last_error says so).  On every failure the pool is untouched.
+ * miqp_solver_last_error is cleared at the start of the call.
+ * miqp_solver_last_timing: out[0] the whole call, out[1] of which on the device, out[2] passes run, out[3] neighbours solved, out[4] their
+ * iterations, out[5] 1 when the last allowed pass still admitted something (with places still free miqp_solver_last_error says so), else 0. */
+int miqp_solver_pool_explore(miqp_solver_t* s, int max_passes, double max_rel, miqp_pool_explore_c* out, int cap);
+
 /* 1 when instances of this shape (NrCars, N) have the dual active-set launches - one or two cars, a horizon of up to 20 steps - else 0 (their node
  * relaxations are interior point solves).  Pure host code: no device is needed or touched.  A call switches the launches off with MIQP_AS=0 */
 int miqp_gpu_has_active_set(int num_cars, int num_steps);

@@ -182,6 +182,16 @@ typedef struct miqp_pool_improve_c {
   int status;       /* 0; 1 the entry's own QP did not come out feasible at the tight tolerance: the entry is left as it was */
 } miqp_pool_improve_c;
 
+/* One entry ADDED by miqp_solver_pool_explore: the jump that led to it and its QP at the tight tolerance. */
+typedef struct miqp_pool_explore_c {
+  int parent;       /* the entry of the pool it jumped from (an old entry, or one an earlier pass added) */
+  int pass;         /* the pass that added it, 1 .. max_passes */
+  int first, stride, count, value;   /* the jump: the parent's decision bytes d[first + k * stride], k < count, took `value` */
+  int iterations;   /* interior point iterations of its node */
+  int reserved;     /* 0 */
+  double objective; /* with the constant cost of step 0; what miqp_solver_pool_found reports for the entry */
+} miqp_pool_explore_c;
+
 #ifdef __cplusplus
 }
 #endif

@@ -1686,6 +1686,7 @@ bool solve_batch_impl(miqp_solver_t* const* S, int n, int* statuses, const Split
 #include "fixed_multi.hip"
 #include "pool_improve.hip"
 #include "pool_improve_multi.hip"
+#include "pool_explore.hip"
 
 // ================================================================================================
 //  C ABI

@@ -1,0 +1,401 @@
+// pool_explore.hip - the free places of a filtered solution pool filled with NEIGHBOURING manoeuvre classes (miqp_solver_pool_explore).  DESIGN.md 6h.
+//
+// Counterpart of IloCplex::populate for a CPLEX user.  The pool holds leaves the branch and bound evaluated, and the search prunes everything beyond
+// its gap: a manoeuvre that is clearly worse than the optimum but valid - the car passes the obstacle on the other side - usually never becomes a
+// leaf, and a caller who asked for 16 fallbacks gets one.  The climb (pool_improve.hip) moves inside a class; this file steps ACROSS classes:
+//
+//   a JUMP is a move (first, stride, count, value) of the families MIQP_POOL_BY_OBSTACLE and MIQP_POOL_BY_CAR_CAR that are in the filter.
+//   A UNIT is a group - the five point-sites of one (car, obstacle), or the four group-sites of one car pair: their bytes of one step are contiguous
+//   in the record - or one site.  A RUN of a unit is a maximal range [i0, i1] inside 1 .. N - 1 over which every byte of the unit is decided (>= 0)
+//   and the unit's bytes stay what they are.  For every run and every alternative v (an obstacle edge 0 .. L - 1 - never the soft alternative L, which
+//   a run may hold and be jumped from - or a car/car alternative 0 .. 3) all bytes of the unit over the run take v: of a group one contiguous range
+//   of stride 1 (all points of a car have to change edge together to pass on the other side), of a site its bytes at the site's stride.  A
+//   candidate whose bytes all hold v already is skipped, and so is one behind which the signature is the same - which happens exactly when, for
+//   every site it writes, the decided bytes around the run are (p, q) = (a, v) or (v, a), a the site's byte in the run: the run then only moves a
+//   change point, which is a move of the climb, not a jump.  Step 0 and undecided bytes are never written.  Order: obstacle groups by c * O + o,
+//   pairs, then the sites in pool_site order; inside a unit the runs by i0, then v ascending; at most POOL_MOVES_MAX per record, the first ones.
+//
+// pool_unit_jumps below is that definition, once, for the host (miqp_gpu_pool_jumps) and the device (pool_jumps_kernel).
+//
+// The call, per pass, all on the solver stream (pass 1 expands every kept entry, pass p > 1 the entries pass p - 1 added):
+//   pool_jumps_kernel      one wavefront per place of the pool: the record staged in LDS, one lane per unit (in a loop when there are more units
+//                          than lanes) counts its jumps, a wave scan over the per-unit counts numbers them, the lanes write them to the move table
+//   pool_offsets_kernel, pool_neighbour_kernel, launch_ipm_batch, fixed_batch_collect_kernel
+//                          the climb's, unchanged, chunk by chunk: at most 16 entries of 512 jumps are the 8192 results the climb holds - no slices
+//   pool_admit_kernel      ONE wavefront: the objectives of the pass's feasible neighbours within the cost cap staged in LDS; then, as long as a
+//                          place is free, the smallest (objective, neighbour number) by wave reduction, its patched record and that record's signature
+//                          under the handle's filter built in LDS, compared with the signatures of everything in the pool - the entries admitted
+//                          earlier in this pass included; a new signature is appended behind the pool: decision bytes, objective, signature and
+//                          the `out` record.  The visiting order makes the first neighbour of a new class that class's best of the pass.  No
+//                          existing entry is changed or moved.
+// Owner computes: no atomics, no lock, no wavefront waits on another, no scratch; records move as 16-byte loads and stores.  The host waits once per
+// pass and reads the number admitted, their `out` records and the jump counts of the next pass.
+#pragma once
+
+namespace {
+
+constexpr int POOL_EXPLORE_PASSES_MAX = 64;
+constexpr size_t POOL_EXPLORE_LDS_MAX = 160 * 1024;   // dynamic LDS of either kernel: the LDS of a gfx950 workgroup; a larger shape is refused with a message
+
+struct PoolJumpDims { PoolDims d; int L; };   // PoolDims and the edge count of an obstacle (max_lines_obstacles)
+
+__host__ __device__ inline int pool_jump_groups(const PoolDims& d) { return d.C * d.O + d.NP; }
+__host__ __device__ inline int pool_jump_units(const PoolDims& d) { return pool_jump_groups(d) + pool_sites(d); }
+
+// unit u of a record: byte k (k < width) of step i lies at base + i * row + k; alts alternatives 0 .. alts - 1; alts == 0: the unit has no jumps
+struct PoolUnit { int base, row, width, alts; };
+__host__ __device__ inline PoolUnit pool_jump_unit(const PoolJumpDims& J, int fam, int u) {
+  const PoolDims& d = J.d;
+  const int f_obs = d.C * d.N * 6, f_c2c = f_obs + d.C * d.O * d.N * 5;
+  const int obs = (fam & POOL_FAM_OBSTACLE) ? J.L : 0, c2c = (fam & POOL_FAM_CAR_CAR) ? 4 : 0;
+  if (u < d.C * d.O) return PoolUnit{f_obs + u * d.N * 5, 5, 5, obs};
+  u -= d.C * d.O;
+  if (u < d.NP) return PoolUnit{f_c2c + u * d.N * 4, 4, 4, c2c};
+  u -= d.NP;
+  const PoolSite t = pool_site(d, u);
+  return PoolUnit{t.first, t.step, 1, t.family == POOL_FAM_OBSTACLE ? obs : t.family == POOL_FAM_CAR_CAR ? c2c : 0};
+}
+
+// the jumps of unit u in their order; emit(j, move) receives jump j of the unit, the number of jumps is returned
+template <class Emit>
+__host__ __device__ inline int pool_unit_jumps(const PoolJumpDims& J, int fam, int u, const signed char* rec, Emit emit) {
+  const PoolUnit t = pool_jump_unit(J, fam, u);
+  const int N = J.d.N;
+  if (t.alts <= 0) return 0;
+  int n = 0;
+  for (int i0 = 1; i0 < N;) {
+    const signed char* const r0 = rec + t.base + i0 * t.row;
+    bool decided = true;
+    for (int k = 0; k < t.width; ++k) decided = decided && r0[k] >= 0;
+    if (!decided) { i0++; continue; }
+    int i1 = i0;
+    for (; i1 + 1 < N; ++i1) {
+      bool same = true;
+      for (int k = 0; k < t.width; ++k) same = same && r0[k] == r0[(i1 + 1 - i0) * t.row + k];
+      if (!same) break;
+    }
+    for (int v = 0; v < t.alts; ++v) {
+      bool changes = false;   // the signature of some site the jump writes
+      for (int k = 0; k < t.width && !changes; ++k) {
+        const int a = r0[k];
+        if (a == v) continue;
+        int p = -1, q = -1;   // the decided bytes of the site around the run
+        for (int i = i0 - 1; i >= 1 && p < 0; --i) p = rec[t.base + i * t.row + k];
+        for (int i = i1 + 1; i < N && q < 0; ++i) q = rec[t.base + i * t.row + k];
+        changes = !((p == a && q == v) || (p == v && q == a));
+      }
+      if (!changes) continue;
+      emit(n, PoolMove{t.base + i0 * t.row, t.width == 1 ? t.row : 1, t.width * (i1 - i0 + 1), v});
+      n++;
+    }
+    i0 = i1 + 1;
+  }
+  return n;
+}
+
+// "within the cost cap": objective - obj0 <= max_rel |obj0|, every operation rounded on its own on both sides so that host code can restate it
+__host__ __device__ inline bool pool_within_cap(double obj0, double obj, double max_rel) {
+  if (max_rel < 0.0) return true;
+#ifdef __HIP_DEVICE_COMPILE__
+  return __dsub_rn(obj, obj0) <= __dmul_rn(max_rel, fabs(obj0));
+#else
+  volatile double over = obj - obj0; volatile double room = max_rel * std::fabs(obj0);
+  return over <= room;
+#endif
+}
+
+struct PoolExploreArgs {
+  PoolImproveArgs A;              // the climb's: cur = the places of the pool, act = expand it in this pass, cnt, moves, off, res, ent_fam; A.m = places
+  int L;                          // edge count of an obstacle
+  signed char* sig;               // [places] the signatures of the pool's entries under the handle's filter
+  int* state;                     // [0] entries in the pool, [1] admitted by the last pass, [2] iterations of the last pass's neighbours
+  miqp_pool_explore_c* out;       // [places] the records of the last pass's admitted entries
+  double obj0, max_rel; int pass;
+};
+
+__global__ __launch_bounds__(64) void pool_jumps_kernel(const PoolExploreArgs E) {
+  extern __shared__ uint4 pj_lds[];   // the record; behind it one int per unit
+  const PoolImproveArgs& A = E.A;
+  const int e = blockIdx.x, lane = threadIdx.x, chunks = A.fixlen >> 4;
+  const PoolJumpDims J{A.dims, E.L};
+  const int nunits = pool_jump_units(A.dims);
+  if (e >= A.m) return;
+  if (!A.act[e]) { if (lane == 0) A.cnt[e] = 0; return; }
+  const signed char* const rec = (const signed char*)pj_lds;
+  int* const ucnt = (int*)(pj_lds + chunks);
+  const uint4* src = (const uint4*)(A.cur + (size_t)e * A.fixlen);
+  for (int c = lane; c < chunks; c += 64) pj_lds[c] = src[c];
+  __syncthreads();
+  const int fam = A.ent_fam[e];
+  for (int u = lane; u < nunits; u += 64) ucnt[u] = pool_unit_jumps(J, fam, u, rec, [](int, const PoolMove&) {});
+  __syncthreads();
+  int total = 0;   // exclusive scan of the per-unit counts, 64 units at a time
+  for (int u0 = 0; u0 < nunits; u0 += 64) {
+    const int c = u0 + lane < nunits ? ucnt[u0 + lane] : 0;
+    int x = c;
+    for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(x, o, 64); if (lane >= o) x += y; }
+    if (u0 + lane < nunits) ucnt[u0 + lane] = total + x - c;
+    total += __shfl(x, 63, 64);
+  }
+  __syncthreads();
+  int4* const out = A.moves + (size_t)e * POOL_MOVES_MAX;
+  for (int u = lane; u < nunits; u += 64) {
+    const int off = ucnt[u];
+    if (off >= POOL_MOVES_MAX) continue;
+    (void)pool_unit_jumps(J, fam, u, rec, [&](int j, const PoolMove& mv) { if (off + j < POOL_MOVES_MAX) out[off + j] = make_int4(mv.first, mv.stride, mv.count, mv.value); });
+  }
+  if (lane == 0) A.cnt[e] = min(total, POOL_MOVES_MAX);
+}
+
+// record j of the pool into LDS and its signature behind it (the whole wavefront calls)
+__device__ inline void pool_admit_signature(const PoolExploreArgs& E, uint4* rec4, uint4* sg4, int fam, int lane) {
+  const int nsites = pool_sites(E.A.dims);
+  __syncthreads();
+  for (int s = lane; s < nsites; s += 64) pool_site_signature(E.A.dims, fam, s, (const signed char*)rec4, (signed char*)sg4);
+  __syncthreads();
+}
+
+constexpr double POOL_ADMIT_NONE = 1e308;   // in the staged objectives: not feasible, beyond the cap, or visited
+
+__global__ __launch_bounds__(64) void pool_admit_kernel(const PoolExploreArgs E, int nb_max) {
+  extern __shared__ uint4 pa_lds[];   // the candidate's record, its signature; behind them one objective per neighbour of the pass
+  const PoolImproveArgs& A = E.A;
+  const int lane = threadIdx.x, chunks = A.fixlen >> 4, K = A.m;
+  uint4* const cand = pa_lds; uint4* const csig = cand + chunks;
+  double* const key = (double*)(csig + chunks);
+  const int fam = A.ent_fam[0];
+  const int n0 = min(max(E.state[0], 0), K), total = min(max(A.off[K], 0), nb_max);
+  uint4* const pool = (uint4*)A.cur; uint4* const sig = (uint4*)E.sig;
+  // the signatures of the entries that have none yet: all of them in pass 1, later the ones the pass before appended (their signature is written
+  // with them) - so only pass 1 builds any
+  if (E.pass == 1)
+    for (int j = 0; j < n0; ++j) {
+      for (int c = lane; c < chunks; c += 64) { cand[c] = pool[(size_t)j * chunks + c]; csig[c] = make_uint4(~0u, ~0u, ~0u, ~0u); }
+      pool_admit_signature(E, cand, csig, fam, lane);
+      for (int c = lane; c < chunks; c += 64) sig[(size_t)j * chunks + c] = csig[c];
+    }
+  int it = 0;
+  for (int g = lane; g < total; g += 64) {
+    const miqp_fixed_result_c r = A.res[g];
+    it += r.iterations;
+    key[g] = r.status == 0 && r.objective < POOL_ADMIT_NONE && pool_within_cap(E.obj0, r.objective, E.max_rel) ? r.objective : POOL_ADMIT_NONE;
+  }
+  for (int d = 32; d >= 1; d >>= 1) it += __shfl_xor(it, d, 64);
+  __syncthreads();
+  int n = n0, added = 0;
+  while (n < K) {
+    double bo = POOL_ADMIT_NONE; int bg = 0x7FFFFFFF;
+    for (int g = lane; g < total; g += 64) {   // (a lane's neighbours ascend: a tie keeps the lower number)
+      const double o = key[g];
+      if (o < bo) { bo = o; bg = g; }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+      const double oo = __shfl_xor(bo, d, 64); const int og = __shfl_xor(bg, d, 64);
+      if (oo < bo || (oo == bo && og < bg)) { bo = oo; bg = og; }
+    }
+    if (bg == 0x7FFFFFFF) break;
+    __syncthreads();
+    if (lane == 0) key[bg] = POOL_ADMIT_NONE;
+    int e = 0;   // off[e] <= bg < off[e + 1]: at most 16 places
+    for (int j = 1; j < K; ++j) if (A.off[j] <= bg) e = j;
+    const int jm = bg - A.off[e];
+    if (jm < 0 || jm >= POOL_MOVES_MAX || e >= n0) { __syncthreads(); continue; }
+    const int4 mv = A.moves[(size_t)e * POOL_MOVES_MAX + jm];
+    for (int c = lane; c < chunks; c += 64) {
+      uint4 v = pool[(size_t)e * chunks + c];
+      for (int k = 0; k < mv.z; ++k) { const int p = mv.x + k * mv.y - c * 16; if ((unsigned)p < 16u) pool_patch_byte(v, p, mv.w); }
+      cand[c] = v; csig[c] = make_uint4(~0u, ~0u, ~0u, ~0u);
+    }
+    pool_admit_signature(E, cand, csig, fam, lane);
+    bool known = false;
+    for (int j = 0; j < n && !known; ++j) known = pool_cmp(csig, sig + (size_t)j * chunks, chunks, lane) == 0;
+    if (known) continue;
+    for (int c = lane; c < chunks; c += 64) { pool[(size_t)n * chunks + c] = cand[c]; sig[(size_t)n * chunks + c] = csig[c]; }
+    if (lane == 0) {
+      A.cur_obj[n] = bo;
+      miqp_pool_explore_c o;
+      o.parent = e; o.pass = E.pass; o.first = mv.x; o.stride = mv.y; o.count = mv.z; o.value = mv.w; o.iterations = A.res[bg].iterations; o.reserved = 0; o.objective = bo;
+      E.out[added] = o;
+    }
+    n++; added++;
+    __syncthreads();   // (the appended signature is compared with the next candidate's)
+  }
+  for (int j = lane; j < K; j += 64) A.act[j] = j >= n0 && j < n ? 1 : 0;   // the next pass expands what this one added
+  if (lane == 0) { E.state[0] = n; E.state[1] = added; E.state[2] = it; }
+}
+
+// buffers of the call beside the climb's (PoolImproveDev), cached per device (grown, not shrunk)
+struct PoolExploreDev {
+  signed char* sig = nullptr; size_t sig_cap = 0; int* state = nullptr; miqp_pool_explore_c* out = nullptr;
+  bool ensure(size_t fl) {
+    if (!state) HIP_OK(hipMalloc((void**)&state, 4 * sizeof(int)));
+    if (!out) HIP_OK(hipMalloc((void**)&out, MIQP_POOL_MAX * sizeof(miqp_pool_explore_c)));
+    if (MIQP_POOL_MAX * fl > sig_cap) {
+      if (sig) (void)hipFree(sig);
+      sig = nullptr; sig_cap = 0;
+      HIP_OK(hipMalloc((void**)&sig, MIQP_POOL_MAX * fl));
+      sig_cap = MIQP_POOL_MAX * fl;
+    }
+    return true;
+  }
+};
+std::map<int, PoolExploreDev> g_pool_explore_dev;   // by device ordinal; used under the device lock
+
+struct PoolExploreOut {
+  std::vector<miqp_pool_explore_c> added;
+  std::vector<signed char> fix; std::vector<double> obj;   // the places of the pool at the end
+  int passes = 0; long neighbours = 0, iterations = 0; bool still_adding = false; float dev_ms = 0.0f;
+  std::string err;
+};
+
+// false: HIP error (nothing of the handle has been touched).  n: entries in the pool, K: its places
+bool pool_explore_run(DevCtx& X, PoolImproveDev& G, PoolExploreDev& Q, const FixedBatchCall& call, int fam, int L, const signed char* fix, int n, int K, double obj0,
+                      double max_rel, int max_passes, PoolExploreOut& O) {
+  DevBuf& B = X.B; hipStream_t st = X.stream; const Layout& Y = call.Y;
+  const size_t fl = (size_t)Y.fixlen, row = (size_t)Y.N * Y.nz;
+  const PoolDims dims = pool_dims(Y);
+  const size_t jump_lds = fl + (size_t)pool_jump_units(dims) * sizeof(int), admit_lds = 2 * fl + (size_t)PoolImproveDev::NB_MAX * sizeof(double);
+  if (std::max(jump_lds, admit_lds) > POOL_EXPLORE_LDS_MAX) {
+    O.err = "miqp_solver_pool_explore: the fix record of this shape does not fit the LDS of pool_admit_kernel twice beside the objectives of a pass";
+    std::fprintf(stderr, "[miqp_gpu] %s (%zu bytes)\n", O.err.c_str(), std::max(jump_lds, admit_lds)); return false;
+  }
+  HIP_OK(hipFuncSetAttribute((const void*)pool_jumps_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)jump_lds));
+  HIP_OK(hipFuncSetAttribute((const void*)pool_admit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)admit_lds));
+  std::vector<int> ident(FB_CHUNK); for (int k = 0; k < FB_CHUNK; ++k) ident[k] = k;
+  std::vector<int> act(MIQP_POOL_MAX, 0); for (int k = 0; k < n; ++k) act[k] = 1;
+  const int state0[4] = {n, 0, 0, 0};
+  HIP_OK(hipMemcpyAsync((void*)B.inst_d, call.D.data(), call.D.size() * 8, hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync((void*)B.inst_i, call.T.data(), call.T.size() * 4, hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(B.batch_node, ident.data(), (size_t)FB_CHUNK * 4, hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemsetAsync(B.batch_inst, 0, (size_t)FB_CHUNK * 4, st));
+  HIP_OK(hipMemsetAsync(G.cur, 0xFF, (size_t)MIQP_POOL_MAX * fl, st));
+  HIP_OK(hipMemcpyAsync(G.cur, fix, (size_t)n * fl, hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(G.act, act.data(), MIQP_POOL_MAX * sizeof(int), hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(Q.state, state0, sizeof state0, hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemsetAsync(G.cnt, 0, MIQP_POOL_MAX * sizeof(int), st)); HIP_OK(hipMemsetAsync(G.cur_obj, 0, MIQP_POOL_MAX * sizeof(double), st));
+  HIP_OK(hipMemsetAsync(G.ent_inst, 0, MIQP_POOL_MAX * sizeof(int), st)); HIP_OK(hipMemsetAsync(G.off, 0, (MIQP_POOL_MAX + 1) * sizeof(int), st));
+  HIP_OK(hipMemsetD32Async((hipDeviceptr_t)G.ent_fam, fam, MIQP_POOL_MAX, st));
+  DevBuf Bp = B; Bp.qp_tol = QP_TOL_FINAL; Bp.use_cutoff = 0; Bp.ws_on = 0;
+  PoolExploreArgs E;
+  PoolImproveArgs& A = E.A;
+  A.cur = G.cur; A.cur_obj = G.cur_obj; A.act = G.act; A.cnt = G.cnt; A.moves = G.moves; A.words = G.words; A.res = G.res; A.pool_fix = B.pool_fix;
+  A.ent_inst = G.ent_inst; A.ent_fam = G.ent_fam; A.off = G.off; A.batch_inst = B.batch_inst;
+  A.dims = dims; A.fixlen = (int)fl; A.m = K;   // (every place of the pool is an entry of the kernels: a free one is not expanded and has no jumps)
+  E.L = L; E.sig = Q.sig; E.state = Q.state; E.out = Q.out; E.obj0 = obj0; E.max_rel = max_rel; E.pass = 0;
+  // `total` neighbours of a pass through the chain, a chunk at a time (the per-chunk resets of fixed_batch_run, as the climb has them)
+  auto solve_nodes = [&](int total) -> bool {
+    for (int c0 = 0, j = 0; c0 < total; c0 += FB_CHUNK, ++j) {
+      const int bc = std::min(FB_CHUNK, total - c0);
+      hipLaunchKernelGGL(pool_neighbour_kernel, dim3((bc + 3) / 4), dim3(256), 0, st, A, c0, bc, 0);
+      HIP_OK(hipGetLastError());
+      HIP_OK(hipMemsetD32Async((hipDeviceptr_t)B.batch_count, bc, 1, st));
+      HIP_OK(hipMemsetAsync(B.pool_big, 0, (size_t)bc, st)); HIP_OK(hipMemsetAsync(B.batch_large, 0, (size_t)bc, st)); HIP_OK(hipMemsetAsync(B.batch_depth, 0, (size_t)bc * 4, st));
+      HIP_OK(hipMemsetAsync(B.inst_nodes, 0, 8, st)); HIP_OK(hipMemsetAsync(B.inst_iters, 0, 8, st)); HIP_OK(hipMemsetAsync(B.stat_rowiters, 0, 8, st));
+      launch_ipm_batch(X, Bp, bc, st);
+      FixedBatchArgs F;
+      F.ovf_list = B.ovf_list; F.ovf_count = B.ovf_count; F.ovf2_list = B.ovf2_list; F.ovf2_count = B.ovf2_count;
+      F.batch_ok = B.batch_ok; F.batch_it = B.batch_it; F.batch_obj = B.batch_obj; F.batch_viol = B.batch_viol; F.batch_Z = B.batch_Z;
+      F.res = G.res + c0; F.Z = G.Z; F.best_obj = G.best_obj + j; F.best_idx = G.best_idx + j;
+      F.bc = bc; F.base = c0; F.row_doubles = (int)row; F.onchip = X.oc_grid > 0 ? 1 : 0; F.big = X.ocb_grid > 0 ? 1 : 0; F.cobj = call.cobj;
+      hipLaunchKernelGGL(fixed_batch_collect_kernel, dim3(1 + std::min(FB_ROW_BLOCKS, (bc + FB_NT / 64 - 1) / (FB_NT / 64))), dim3(FB_NT), 0, st, F);
+      HIP_OK(hipGetLastError());
+    }
+    return true;
+  };
+  // behind a pass (admit: not in front of the first one): the jumps of the next one, and what the host needs of both
+  std::vector<int> cnt(MIQP_POOL_MAX); int state[4] = {n, 0, 0, 0}; std::vector<miqp_pool_explore_c> rec(MIQP_POOL_MAX);
+  auto finish_pass = [&](bool admit) -> bool {
+    if (admit) hipLaunchKernelGGL(pool_admit_kernel, dim3(1), dim3(64), admit_lds, st, E, (int)PoolImproveDev::NB_MAX);
+    hipLaunchKernelGGL(pool_jumps_kernel, dim3(K), dim3(64), jump_lds, st, E);
+    hipLaunchKernelGGL(pool_offsets_kernel, dim3(1), dim3(256), 0, st, A);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipEventRecord(X.ev1, st));
+    HIP_OK(hipMemcpyAsync(cnt.data(), G.cnt, MIQP_POOL_MAX * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(state, Q.state, sizeof state, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(rec.data(), Q.out, MIQP_POOL_MAX * sizeof(miqp_pool_explore_c), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st)); HIP_OK(hipGetLastError());
+    float ms = 0.0f; (void)hipEventElapsedTime(&ms, X.ev0, X.ev1); O.dev_ms += ms;
+    return true;
+  };
+  HIP_OK(hipEventRecord(X.ev0, st));
+  if (!finish_pass(false)) return false;
+  int have = n;
+  for (;;) {
+    long total = 0;
+    for (int k = 0; k < K; ++k) { if (cnt[k] < 0 || cnt[k] > POOL_MOVES_MAX) { std::fprintf(stderr, "[miqp_gpu] miqp_solver_pool_explore: jump count %d of entry %d\n", cnt[k], k); return false; } total += cnt[k]; }
+    if (total == 0 || total > PoolImproveDev::NB_MAX || O.passes == max_passes || have >= K) break;
+    E.pass = O.passes + 1;
+    HIP_OK(hipEventRecord(X.ev0, st));
+    if (!solve_nodes((int)total) || !finish_pass(true)) return false;
+    if (state[0] != have + state[1] || state[1] < 0 || state[0] > K) { std::fprintf(stderr, "[miqp_gpu] miqp_solver_pool_explore: %d entries behind %d, %d admitted\n", state[0], have, state[1]); return false; }
+    O.passes++; O.neighbours += total; O.iterations += state[2];
+    for (int k = 0; k < state[1]; ++k) O.added.push_back(rec[k]);
+    have = state[0];
+    O.still_adding = state[1] > 0 && O.passes == max_passes;
+    if (state[1] == 0) break;
+  }
+  O.fix.resize((size_t)have * fl); O.obj.resize(have);
+  HIP_OK(hipMemcpy(O.fix.data(), G.cur, (size_t)have * fl, hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(O.obj.data(), G.cur_obj, (size_t)have * sizeof(double), hipMemcpyDeviceToHost));
+  return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int miqp_gpu_pool_explore_size(void) { return (int)sizeof(miqp_pool_explore_c); }
+
+int miqp_gpu_pool_jumps(int cars, int steps, int obstacles, int max_lines, int families, const signed char* decisions, int* moves4, int cap) {
+  if (!decisions || !moves4 || cars <= 0 || steps <= 0 || obstacles < 0 || max_lines < 0) return -1;
+  if (families < 1 || families >= POOL_FAM_TIMING || !(families & (POOL_FAM_OBSTACLE | POOL_FAM_CAR_CAR))) return -2;
+  const PoolJumpDims J{PoolDims{cars, steps, obstacles, cars * (cars - 1) / 2}, max_lines};
+  std::vector<PoolMove> mv;
+  for (int u = 0, n = pool_jump_units(J.d); u < n && (int)mv.size() < POOL_MOVES_MAX; ++u)
+    (void)pool_unit_jumps(J, families, u, decisions, [&](int, const PoolMove& m) { if ((int)mv.size() < POOL_MOVES_MAX) mv.push_back(m); });
+  if (cap < (int)mv.size()) return -3;
+  for (size_t k = 0; k < mv.size(); ++k) { moves4[4 * k] = mv[k].first; moves4[4 * k + 1] = mv[k].stride; moves4[4 * k + 2] = mv[k].count; moves4[4 * k + 3] = mv[k].value; }
+  return (int)mv.size();
+}
+
+int miqp_solver_pool_explore(miqp_solver_t* s, int max_passes, double max_rel, miqp_pool_explore_c* out, int cap) {
+  if (s) s->err.clear();   // (miqp_solver_last_error speaks of this call from here on)
+  if (!s || !s->has_inst || !out || cap < 0 || max_rel != max_rel) return -1;
+  if (s->pool_fam < 1 || s->pool_fam >= POOL_FAM_TIMING || !(s->pool_fam & (POOL_FAM_OBSTACLE | POOL_FAM_CAR_CAR))) return -2;
+  if (max_passes < 1 || max_passes > POOL_EXPLORE_PASSES_MAX) return -2;
+  const int n = miqp_solver_pool_count(s), K = std::min(s->pool_cap, MIQP_POOL_MAX);
+  if (n == 0 || n >= K) return 0;   // (nothing to jump from, or no free place: no device is touched)
+  if (cap < K - n) return -2;
+  { int ndev = 0; if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return -3; }
+  miqp_solver_t* one[1] = {s};
+  BatchShape bs = batch_layout(one, 1);
+  if (!bs.ok || bs.Y.fixlen != s->pool_fixlen || s->pool_fix.size() < (size_t)n * bs.Y.fixlen || s->pool_obj.size() < (size_t)n) return -1;
+  const Layout& Y = bs.Y; const size_t fl = (size_t)Y.fixlen;
+  const double t_call = wall_s();
+  FixedBatchCall call;
+  if (call.open(s, Y) != 0) return -3;
+  PoolImproveDev& G = g_pool_improve_dev[call.X->device]; PoolExploreDev& Q = g_pool_explore_dev[call.X->device];
+  PoolExploreOut O;
+  if (!G.ensure(fl, (size_t)Y.N * Y.nz) || !Q.ensure(fl) ||
+      !pool_explore_run(*call.X, G, Q, call, s->pool_fam, s->inst.L, s->pool_fix.data(), n, K, s->pool_obj[0], max_rel, max_passes, O)) {
+    (void)hipStreamSynchronize(call.X->stream); if (!O.err.empty()) s->err = O.err; return -3;
+  }
+  const int added = (int)O.added.size();
+  if ((int)O.obj.size() != n + added || n + added > K) return -3;
+  // the old entries stay as the handle holds them; the added ones go behind them
+  s->pool_fix.resize((size_t)n * fl); s->pool_obj.resize(n);
+  s->pool_fix.insert(s->pool_fix.end(), O.fix.begin() + (size_t)n * fl, O.fix.end());
+  s->pool_obj.insert(s->pool_obj.end(), O.obj.begin() + n, O.obj.end());
+  s->pool_n = n + added;
+  for (int k = 0; k < added; ++k) out[k] = O.added[k];
+  s->pr_n = 0; std::vector<char>().swap(s->pr_ok); std::vector<signed char>().swap(s->pr_fix); std::vector<double>().swap(s->pr_Z);
+  s->timing[0] = wall_s() - t_call; s->timing[1] = O.dev_ms * 1e-3; s->timing[2] = O.passes; s->timing[3] = (double)O.neighbours; s->timing[4] = (double)O.iterations; s->timing[5] = O.still_adding ? 1 : 0;
+  if (O.still_adding && n + added < K) {
+    char msg[200]; std::snprintf(msg, sizeof msg, "miqp_solver_pool_explore: the last of %d passes still added an entry and places are free; more passes may fill them", max_passes);
+    s->err = msg;
+  }
+  return added;
+}
+
+}  // extern "C"

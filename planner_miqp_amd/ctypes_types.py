@@ -104,6 +104,12 @@ class PoolImproveC(C.Structure):
     _fields_ = [("before", C.c_double), ("after", C.c_double), ("moves", C.c_int), ("status", C.c_int)]
 
 
+class PoolExploreC(C.Structure):
+    """miqp_pool_explore_c (include/miqp_types.h): one entry CplexWrapper.exploreSolutionPool added"""
+    _fields_ = [("parent", C.c_int), ("pass_", C.c_int), ("first", C.c_int), ("stride", C.c_int), ("count", C.c_int), ("value", C.c_int),
+                ("iterations", C.c_int), ("reserved", C.c_int), ("objective", C.c_double)]
+
+
 class SolverOptsC(C.Structure):
     _fields_ = [("precision", C.c_int), ("device", C.c_int), ("nodes_per_round", C.c_int),
                 ("max_open_nodes", C.c_int), ("gap_override", C.c_double), ("verbose", C.c_int)]

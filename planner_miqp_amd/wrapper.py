@@ -12,7 +12,7 @@ import numpy as np
 # (four concurrent launches per round + the null stream: see miqp_gpu.hip - effective when set before the process's first HIP call)
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
-from .ctypes_types import (Certificate, CertificateC, FixedResultC, ModelParameters, ModelParamsC, PoolImproveC, RawResults, RawResultsC, SolutionPropertiesC, SolverOptsC,
+from .ctypes_types import (Certificate, CertificateC, FixedResultC, ModelParameters, ModelParamsC, PoolExploreC, PoolImproveC, RawResults, RawResultsC, SolutionPropertiesC, SolverOptsC,
                            c_double_p)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -121,6 +121,10 @@ def load_library():
     L.miqp_solver_pool_improve_multi.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.POINTER(PoolImproveC), C.c_int, C.POINTER(C.c_int)]
     L.miqp_gpu_pool_improve_plan.restype = C.c_int
     L.miqp_gpu_pool_improve_plan.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_int]
+    L.miqp_gpu_pool_jumps.restype = C.c_int
+    L.miqp_gpu_pool_jumps.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_byte), C.POINTER(C.c_int), C.c_int]
+    L.miqp_gpu_pool_explore_size.restype = C.c_int; L.miqp_gpu_pool_explore_size.argtypes = []
+    L.miqp_solver_pool_explore.restype = C.c_int; L.miqp_solver_pool_explore.argtypes = [vp, C.c_int, C.c_double, C.POINTER(PoolExploreC), C.c_int]
     L.miqp_solver_solve_fixed_multi.restype = C.c_int
     L.miqp_solver_solve_fixed_multi.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(C.POINTER(RawResultsC)), C.POINTER(C.c_int), C.POINTER(FixedResultC), C.POINTER(C.c_int)]
     L.miqp_solver_pool_solve_multi.restype = C.c_int
@@ -131,6 +135,9 @@ def load_library():
     if L.miqp_gpu_pool_improve_size() != C.sizeof(PoolImproveC):
         raise RuntimeError("libmiqp_gpu.so and ctypes_types.PoolImproveC disagree on miqp_pool_improve_c (%d / %d bytes): rebuild the library"
                            % (L.miqp_gpu_pool_improve_size(), C.sizeof(PoolImproveC)))
+    if L.miqp_gpu_pool_explore_size() != C.sizeof(PoolExploreC):
+        raise RuntimeError("libmiqp_gpu.so and ctypes_types.PoolExploreC disagree on miqp_pool_explore_c (%d / %d bytes): rebuild the library"
+                           % (L.miqp_gpu_pool_explore_size(), C.sizeof(PoolExploreC)))
     L.miqp_gpu_version.restype = C.c_char_p
     _LIB = L
     return L
@@ -155,7 +162,8 @@ EXPORTED_SYMBOLS = ["miqp_solver_create", "miqp_solver_destroy", "miqp_solver_se
                     "miqp_solver_solve_fixed_multi", "miqp_solver_pool_solve_multi",
                     "miqp_solver_set_pool_filter", "miqp_gpu_pool_signature", "miqp_solver_pool_signature", "miqp_solver_pool_found_decisions",
                     "miqp_gpu_pool_moves", "miqp_gpu_pool_moves_max", "miqp_gpu_pool_improve_size", "miqp_solver_solve_decisions", "miqp_solver_pool_improve",
-                    "miqp_solver_pool_improve_multi", "miqp_gpu_pool_improve_plan"]
+                    "miqp_solver_pool_improve_multi", "miqp_gpu_pool_improve_plan",
+                    "miqp_gpu_pool_jumps", "miqp_gpu_pool_explore_size", "miqp_solver_pool_explore"]
 
 
 # a row of CplexWrapper.launchPlan (NodeLaunch in csrc/miqp_gpu.hip)
@@ -211,6 +219,26 @@ def pool_moves(cars, steps, obstacles, families, decisions):
                                            out.ctypes.data_as(C.POINTER(C.c_int)), cap)
     if n < 0:
         raise ValueError("miqp_gpu_pool_moves refused the arguments (%d)" % n)
+    return out[:n].copy()
+
+
+def pool_jumps(cars, steps, obstacles, max_lines, families, decisions):
+    """the jumps of a record's D decision bytes to neighbouring manoeuvre classes under ``families`` (miqp_gpu_pool_jumps): an int32 array [n, 4]
+    of (first, stride, count, value) as pool_moves returns them - group jumps (all five points of a (car, obstacle), all four group-sites of a car
+    pair, over a run of steps with constant decided bytes) in front of the jumps of single sites, every alternative 0 .. max_lines - 1 of an
+    obstacle edge or 0 .. 3 of a car/car byte; every one changes pool_signature; at most pool_moves_max().  A pure function on bytes: needs no
+    wrapper and no device.  Raises ValueError where the library refuses the arguments (families outside 1 .. 15, or without POOL_BY_OBSTACLE and
+    POOL_BY_CAR_CAR)."""
+    d = np.ascontiguousarray(decisions, dtype=np.int8)
+    D = _decision_len(int(cars), int(steps), int(obstacles))
+    if d.ndim != 1 or d.size < D or D <= 0:
+        raise ValueError("%d decision bytes given, the shape has %d" % (d.size, D))
+    cap = pool_moves_max()
+    out = np.empty((cap, 4), dtype=np.int32)
+    n = load_library().miqp_gpu_pool_jumps(int(cars), int(steps), int(obstacles), int(max_lines), int(families), d.ctypes.data_as(C.POINTER(C.c_byte)),
+                                           out.ctypes.data_as(C.POINTER(C.c_int)), cap)
+    if n < 0:
+        raise ValueError("miqp_gpu_pool_jumps refused the arguments (%d)" % n)
     return out[:n].copy()
 
 
@@ -608,6 +636,21 @@ class CplexWrapper:
         m = min(self.solutionPoolCount(), n) if rc >= 0 else 0
         a = np.frombuffer(out, dtype=np.dtype([("before", "<f8"), ("after", "<f8"), ("moves", "<i4"), ("status", "<i4")]), count=m)
         return rc, a["before"].copy(), a["after"].copy(), a["moves"].copy(), a["status"].copy()
+
+    def exploreSolutionPool(self, max_passes=4, max_rel=-1.0):
+        """the free places of a FILTERED pool filled with neighbouring manoeuvre classes in one device-resident loop (miqp_solver_pool_explore;
+        IloCplex::populate for a CPLEX user): pass 1 solves every jump of pool_jumps of every kept entry at the tight tolerance, pass p > 1 those of
+        the entries pass p - 1 added; the best feasible neighbour of every class the pool does not hold yet is appended while a place is free.
+        ``max_rel`` >= 0 admits only objectives within max_rel * |objective of entry 0| above entry 0's.  Returns (rc, added): rc the number of
+        entries added - or the library's code < 0: -2 the filter is not in 1 .. 15 or has neither POOL_BY_OBSTACLE nor POOL_BY_CAR_CAR, or
+        max_passes not in 1 .. 64; -3 no device; the pool is untouched then - and one dict per added entry, in pool order behind the old entries
+        (parent, pass, first, stride, count, value, iterations, objective; empty for rc <= 0).  Old entries keep their bytes and places.  A
+        refined pool is dropped: call solveSolutionPool afterwards."""
+        n = pool_max()
+        out = (PoolExploreC * n)()
+        rc = int(self._L.miqp_solver_pool_explore(self._h, int(max_passes), float(max_rel), out, n))
+        return rc, [dict(parent=o.parent, **{"pass": o.pass_}, first=o.first, stride=o.stride, count=o.count, value=o.value, iterations=o.iterations,
+                         objective=float(o.objective)) for o in out[:max(rc, 0)]]
 
     def solveDecisions(self, decisions):
         """the continuous QPs of many DECISION records of this wrapper's instance in one device call (miqp_solver_solve_decisions): ``decisions`` is
