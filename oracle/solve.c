@@ -858,6 +858,15 @@ static void fill_results(const dmodel* M, const signed char* comp, const double*
       for (int o = 0; o < O; ++o) {
         for (int pt = 0; pt < 5; ++pt) {
           int ignored = i >= 1 && FIX_OBS(M, comp, c, o, i, pt) >= L;
+          /* a point that starts inside a soft obstacle: the record carries its slack (the raw model's cardinality row at step 0), by
+           * step0_check's own predicate - no edge holds within FEAS_TOL at the initial state - so exactly where that charged the price */
+          if (i == 0 && I->obs_soft[o]) {
+            double Z0[ORC_NZMAX]; memset(Z0, 0, sizeof(Z0));
+            for (int cc = 0; cc < C; ++cc) for (int k = 0; k < 6; ++k) Z0[6 * cc + k] = I->x0[cc * 6 + k];
+            int any = 0;
+            for (int kk = 0; kk < L && !any; ++kk) { tmp.n = 0; obs_row(M, &tmp, c, o, 0, pt, kk, 0); if (row_val(M, &tmp.r[0], Z0) <= FEAS_TOL) any = 1; }
+            ignored = !any;
+          }
           for (int kk = 0; kk < L; ++kk) {
             tmp.n = 0; obs_row(M, &tmp, c, o, i, pt, kk, j);
             orow rr = tmp.r[0]; rr.stage = 0;
@@ -1074,11 +1083,15 @@ int orc_solve_fixed_tol(const oinst* I, const miqp_raw_results_c* f, miqp_raw_re
         for (int e = 0; e < E; ++e)
           if (nw[pt][(c * E + e) * N + i] == 0) { env_rows(M, &rows, c, i, pt, e, j); FIX_ENV(M, comp, c, i, pt) = (signed char)e; }
       for (int o = 0; o < O; ++o)
-        for (int pt = 0; pt < 5; ++pt)
+        for (int pt = 0; pt < 5; ++pt) {
+          /* a point of a soft obstacle marked as ignored: no row, the constant price instead (the precedence of the device's fix_from_results) */
+          int so = pt == 0 ? f->slackvarsObstacle[(c * O + o) * N + i] : f->slackvarsObstacle_front[((c * O + o) * N + i) * 4 + pt - 1];
+          if (so >= 1 && I->obs_soft[o]) { FIX_OBS(M, comp, c, o, i, pt) = (signed char)L; continue; }
           for (int k = 0; k < L; ++k) {
             int d = pt == 0 ? f->deltacc[((c * O + o) * N + i) * L + k] : f->deltacc_front[(((c * O + o) * N + i) * L + k) * 4 + pt - 1];
             if (d == 0) { obs_row(M, &rows, c, o, i, pt, k, j); FIX_OBS(M, comp, c, o, i, pt) = (signed char)k; }
           }
+        }
     }
   for (int p = 0; p < I->NP; ++p) {
     int c1, c2; pair_cars(I, p, &c1, &c2);
@@ -1093,7 +1106,7 @@ int orc_solve_fixed_tol(const oinst* I, const miqp_raw_results_c* f, miqp_raw_re
   }
   qpres q; qp_solve_tol(M, rows.r, rows.n, &q, qp_tol);
   double cobj0 = 0; (void)step0_check(M, &cobj0); /* the constant cost of step 0 (car/car slack of the initial state), as orc_solve and the device report it */
-  if (objective) *objective = q.obj + cobj0;
+  if (objective) *objective = q.obj + const_cost(M, comp) + cobj0;
   if (iters) *iters = q.it;
   int rc = (q.ok && q.viol <= FEAS_TOL) ? 0 : 1;
   if (res && rc == 0) {

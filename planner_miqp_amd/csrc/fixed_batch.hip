@@ -27,6 +27,21 @@ constexpr int FB_CAP = 65536;     // entries per call (include/miqp_gpu.h)
 constexpr int FB_NT = 256;
 constexpr int FB_ROW_BLOCKS = 256;
 
+// The price of the obstacle points a fix record ignores (byte L at a point of a soft obstacle: WEIGHTS_SLACK_OBSTACLE each, a constant of the node's
+// QP).  No node kernel charges it - eval_kernel adds it for the search - so the collect kernels do, from the chunk's fix records in pool_fix.
+struct SoftCost {
+  const signed char* fix;     // slot 0 of pool_fix: node k of a chunk is slot k
+  const double* inst_d;       // the instances' tables (the weight is D[d_w] of the node's instance)
+  int fixlen, f_obs, n_obs, L, dstride, d_w;   // n_obs = C * O * N * 5 bytes from f_obs on
+};
+
+__device__ inline double soft_cost(const SoftCost& S, int k, int inst) {
+  const signed char* f = S.fix + (size_t)k * S.fixlen + S.f_obs;
+  int n = 0;
+  for (int q = 0; q < S.n_obs; ++q) n += f[q] >= S.L ? 1 : 0;
+  return n > 0 ? __dmul_rn((double)n, S.inst_d[(size_t)inst * S.dstride + S.d_w]) : 0.0;   // (a rounded product, never fused into the sum: the bits of the host's in miqp_solver_solve_fixed)
+}
+
 struct FixedBatchArgs {
   const int* ovf_list; const int* ovf_count; const int* ovf2_list; const int* ovf2_count;
   const int* batch_ok; const int* batch_it; const double* batch_obj; const double* batch_viol; const double* batch_Z;
@@ -36,6 +51,7 @@ struct FixedBatchArgs {
   int bc, base, row_doubles;  // nodes of the chunk, index in the call of its first node, N * nz (even: nz = 8 per car)
   int onchip, big;            // the shape has the on-chip kernel / its larger variant
   double cobj;                // constant cost of step 0 (step0_check)
+  SoftCost soft;
 };
 
 __global__ __launch_bounds__(FB_NT) void fixed_batch_collect_kernel(const FixedBatchArgs A) {
@@ -66,7 +82,7 @@ __global__ __launch_bounds__(FB_NT) void fixed_batch_collect_kernel(const FixedB
   // pass 2: verdict, objective, iterations and violation of each node; the lane's best feasible one (its nodes ascend: a tie keeps the lower index)
   double bo = 1e308; int bi = 0x7FFFFFFF;
   for (int k = tid; k < A.bc; k += FB_NT) {
-    const int ok = A.batch_ok[k]; const double viol = A.batch_viol[k], obj = A.batch_obj[k] + A.cobj;
+    const int ok = A.batch_ok[k]; const double viol = A.batch_viol[k], obj = A.batch_obj[k] + (A.cobj + soft_cost(A.soft, k, 0));
     const int st = (!ok || viol > FEAS_TOL) ? 1 : 0;
     R[k].status = st; R[k].iterations = A.batch_it[k]; R[k].reserved = 0; R[k].objective = obj; R[k].violation = viol;
     if (st == 0 && obj < bo) { bo = obj; bi = k; }
@@ -122,6 +138,12 @@ struct FixedBatchDev {
 };
 std::map<int, FixedBatchDev> g_fixed_batch_dev;   // by device ordinal; used under the device lock (DevCtx::mu of lane 0)
 
+SoftCost soft_cost_args(const DevBuf& B, const Layout& Y) {
+  SoftCost S;
+  S.fix = B.pool_fix; S.inst_d = B.inst_d; S.fixlen = Y.fixlen; S.f_obs = Y.f_obs; S.n_obs = Y.C * Y.O * Y.N * 5; S.L = Y.L; S.dstride = Y.dstride; S.d_w = Y.d_misc + 1;
+  return S;
+}
+
 // the int arrays fix_from_results reads
 bool fixed_record_ok(const miqp_raw_results_c& r) {
   const void* need[] = {r.notWithinEnvironmentRear, r.notWithinEnvironmentFrontUbUb, r.notWithinEnvironmentFrontLbUb, r.notWithinEnvironmentFrontUbLb, r.notWithinEnvironmentFrontLbLb,
@@ -171,7 +193,7 @@ bool fixed_batch_run(DevCtx& X, FixedBatchDev& G, const Layout& Y, const std::ve
     A.ovf_list = B.ovf_list; A.ovf_count = B.ovf_count; A.ovf2_list = B.ovf2_list; A.ovf2_count = B.ovf2_count;
     A.batch_ok = B.batch_ok; A.batch_it = B.batch_it; A.batch_obj = B.batch_obj; A.batch_viol = B.batch_viol; A.batch_Z = B.batch_Z;
     A.res = G.d_res + c0; A.Z = G.d_Z + (size_t)c0 * row; A.best_obj = G.d_best_obj + j; A.best_idx = G.d_best_idx + j;
-    A.bc = bc; A.base = c0; A.row_doubles = (int)row; A.onchip = X.oc_grid > 0 ? 1 : 0; A.big = X.ocb_grid > 0 ? 1 : 0; A.cobj = cobj;
+    A.bc = bc; A.base = c0; A.row_doubles = (int)row; A.onchip = X.oc_grid > 0 ? 1 : 0; A.big = X.ocb_grid > 0 ? 1 : 0; A.cobj = cobj; A.soft = soft_cost_args(B, Y);
     hipLaunchKernelGGL(fixed_batch_collect_kernel, dim3(1 + std::min(FB_ROW_BLOCKS, (bc + FB_NT / 64 - 1) / (FB_NT / 64))), dim3(FB_NT), 0, st, A);
     HIP_OK(hipGetLastError());
   }

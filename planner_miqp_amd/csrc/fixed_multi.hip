@@ -33,6 +33,7 @@ struct FixedMultiArgs {
   double* seg_obj; int* seg_idx;   // of the chunk's first segment: the minimum of each and its index within the handle (-1: none feasible)
   int bc, base, nseg, n_inst, row_doubles;   // nodes of the chunk, node of the call of its first, segments, handles of the call, N * nz
   int onchip, big;
+  SoftCost soft;              // the price of the ignored points, per node from its fix record and its instance's weight
 };
 
 __global__ __launch_bounds__(FB_NT) void fixed_multi_collect_kernel(const FixedMultiArgs A) {
@@ -62,18 +63,18 @@ __global__ __launch_bounds__(FB_NT) void fixed_multi_collect_kernel(const FixedM
   // pass 2: verdict, objective, iterations and violation of each node
   for (int k = tid; k < A.bc; k += FB_NT) {
     const int inst = A.batch_inst[k];
-    const int ok = A.batch_ok[k]; const double viol = A.batch_viol[k], obj = A.batch_obj[k] + ((unsigned)inst < (unsigned)A.n_inst ? A.cobj[inst] : 0.0);
+    const int ok = A.batch_ok[k]; const double viol = A.batch_viol[k], obj = A.batch_obj[k] + ((unsigned)inst < (unsigned)A.n_inst ? A.cobj[inst] + soft_cost(A.soft, k, inst) : 0.0);
     R[k].status = (!ok || viol > FEAS_TOL) ? 1 : 0; R[k].iterations = A.batch_it[k]; R[k].reserved = 0; R[k].objective = obj; R[k].violation = viol;
   }
+  __syncthreads();   // (pass 3 reads the objectives pass 2 wrote: each carries the price of its own record's ignored points)
   // pass 3: the minimum of every segment, a wavefront per segment at a time (a lane's nodes ascend: a tie keeps the lower index)
   for (int s = wave; s < A.nseg; s += FB_NT / 64) {
     const int a = max(0, min(A.seg[s], A.bc)), b = max(a, min(A.seg[s + 1], A.bc));
     const int inst = a < b ? A.batch_inst[a] : -1;
     const bool known = (unsigned)inst < (unsigned)A.n_inst;
-    const double c = known ? A.cobj[inst] : 0.0;
     double bo = 1e308; int bi = 0x7FFFFFFF;
     for (int k = a + lane; k < b; k += 64) {
-      const int ok = A.batch_ok[k]; const double viol = A.batch_viol[k], obj = A.batch_obj[k] + c;
+      const int ok = A.batch_ok[k]; const double viol = A.batch_viol[k], obj = R[k].objective;
       if (ok && !(viol > FEAS_TOL) && obj < bo) { bo = obj; bi = k; }
     }
 #pragma unroll
@@ -175,7 +176,7 @@ bool fixed_multi_run(DevCtx& X, FixedBatchDev& G, FixedMultiDev& M, const Layout
     A.batch_ok = B.batch_ok; A.batch_it = B.batch_it; A.batch_obj = B.batch_obj; A.batch_viol = B.batch_viol; A.batch_Z = B.batch_Z; A.batch_inst = B.batch_inst;
     A.cobj = M.d_cobj; A.hfirst = M.d_hfirst; A.seg = M.d_seg;
     A.res = G.d_res + c0; A.Z = G.d_Z + (size_t)c0 * row; A.seg_obj = M.d_sobj + sfirst[j]; A.seg_idx = M.d_sidx + sfirst[j];
-    A.bc = bc; A.base = c0; A.nseg = ns; A.n_inst = n_inst; A.row_doubles = (int)row; A.onchip = X.oc_grid > 0 ? 1 : 0; A.big = X.ocb_grid > 0 ? 1 : 0;
+    A.bc = bc; A.base = c0; A.nseg = ns; A.n_inst = n_inst; A.row_doubles = (int)row; A.onchip = X.oc_grid > 0 ? 1 : 0; A.big = X.ocb_grid > 0 ? 1 : 0; A.soft = soft_cost_args(B, Y);
     hipLaunchKernelGGL(fixed_multi_collect_kernel, dim3(1 + std::min(FB_ROW_BLOCKS, (bc + FB_NT / 64 - 1) / (FB_NT / 64))), dim3(FB_NT), 0, st, A);
     HIP_OK(hipGetLastError());
   }

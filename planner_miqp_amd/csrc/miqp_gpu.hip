@@ -907,6 +907,13 @@ void fill_results(const HostInst& I, const Layout& Y, const double* D, const int
         for (int pt = 0; pt < 5; ++pt) {
           bool ignored = i >= 1 && comp[Y.f_obs + ((c * O + o) * N + i) * 5 + pt] >= L;
           G.point(c, i, q, z, OBS_PT_H[pt][0], OBS_PT_H[pt][1], X, Yc);
+          // a point that STARTS inside a soft obstacle is ignored by the constant step 0: the record says so, or it breaks the cardinality row of the
+          // raw model at step 0.  The predicate is step0_check's own (no edge holds within FEAS_TOL), so the slack entry is 1 exactly where that charged the price
+          if (i == 0 && I.obs_soft[o]) {
+            double X0, Y0; G.point(c, 0, 0, nullptr, OBS_PT_H[pt][0], OBS_PT_H[pt][1], X0, Y0);   // (the initial state, as step0_check reads it)
+            bool any = false; for (int k = 0; k < L && !any; ++k) any = G.obs_viol(o, 0, k, X0, Y0) <= FEAS_TOL;
+            ignored = !any;
+          }
           for (int k = 0; k < L; ++k) {
             int d = (G.obs_viol(o, i, k, X, Yc) <= tol && !ignored) ? 0 : 1;
             if (pt == 0) r->deltacc[((c * O + o) * N + i) * L + k] = d; else r->deltacc_front[(((c * O + o) * N + i) * L + k) * 4 + pt - 1] = d;
@@ -2241,7 +2248,14 @@ int miqp_solver_solve_fixed(miqp_solver_t* s, const miqp_raw_results_c* fixed, m
   if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) return -3;
   s->fixed_route = X.oc_grid <= 0 ? 3 : ovf == 0 ? 0 : (X.ocb_grid > 0 && ovf2 == 0) ? 1 : 2;
   HostGeo G{s->inst, Y, D.data(), T.data()}; double cobj = 0; (void)step0_check(G, cobj);
-  if (objective) *objective = obj + cobj;
+  // the points the record ignores cost WEIGHTS_SLACK_OBSTACLE each: a constant no node kernel charges (eval_kernel adds it for the search, soft_cost of
+  // fixed_batch.hip for the batch calls, in this order of operations)
+  int nign = 0; for (int q = 0; q < Y.C * Y.O * Y.N * 5; ++q) nign += fix[Y.f_obs + q] >= Y.L;
+  // (the product is ROUNDED before the sum, as __dmul_rn rounds it in soft_cost: the volatile keeps a host compiler that may fuse - an FMA target
+  // with fp-contract on - from doing so, or the batch calls would differ from this one in the last bit)
+  volatile double soft = nign > 0 ? (double)nign * D[Y.d_misc + 1] : 0.0;
+  const double konst = cobj + soft;
+  if (objective) *objective = obj + konst;
   if (iterations) *iterations = it;
   if (!ok || viol > FEAS_TOL) return 1;
   if (out) {

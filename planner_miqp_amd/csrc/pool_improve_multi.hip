@@ -127,7 +127,7 @@ bool pool_improve_multi_run(DevCtx& X, PoolImproveDev& G, PoolImproveMultiDev& M
         F.batch_ok = B.batch_ok; F.batch_it = B.batch_it; F.batch_obj = B.batch_obj; F.batch_viol = B.batch_viol; F.batch_Z = B.batch_Z; F.batch_inst = B.batch_inst;
         F.cobj = FM.d_cobj; F.hfirst = nullptr; F.seg = nullptr; F.seg_obj = nullptr; F.seg_idx = nullptr;   // (nseg = 0: the climb picks per entry, the kernel reads none of the four)
         F.res = G.res + k0; F.Z = G.Z;   // (the climb has no use for the trajectories: one chunk's worth is written over)
-        F.bc = bc; F.base = k0; F.nseg = 0; F.n_inst = n_inst; F.row_doubles = (int)row; F.onchip = X.oc_grid > 0 ? 1 : 0; F.big = X.ocb_grid > 0 ? 1 : 0;
+        F.bc = bc; F.base = k0; F.nseg = 0; F.n_inst = n_inst; F.row_doubles = (int)row; F.onchip = X.oc_grid > 0 ? 1 : 0; F.big = X.ocb_grid > 0 ? 1 : 0; F.soft = soft_cost_args(B, Y);
         hipLaunchKernelGGL(fixed_multi_collect_kernel, dim3(1 + std::min(FB_ROW_BLOCKS, (bc + FB_NT / 64 - 1) / (FB_NT / 64))), dim3(FB_NT), 0, st, F);
         HIP_OK(hipGetLastError());
       }

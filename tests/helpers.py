@@ -69,6 +69,10 @@ NODE_SHAPES = {
     "c2n6e2pent": ((2, 6, 32, 2, 1, 5), 0, {"ahead": 10.0, "spacing": 6.0, "shift": 66.0, "piece1_top": 0.5}),
     "c2n20a": ("cfg4", 10, {}), "c2n20b": ("cfg4", 4, {}), "c2n20c": ("cfg4", 1013, {}),
     "mini3": ("mini3", 1, {"spacing": 6.0}), "mini4": ("mini4", 0, {"spacing": 4.0}),
+    # three cars WITH an obstacle (mini3 has none): the wide kernel's obstacle rows, and its soft levels below.  With spacing 6 an obstacle 12 m ahead of
+    # car 0 lies on car 2's start: with a hard obstacle the instance is infeasible on every seed tried (0 to 10), and so it is at 16, 18, 19 and 20 m.
+    # At 22 m seed 0 is feasible, its front-point rows bind, and the largest spread over its levels is 1.4e-8.
+    "c3n6o": ((3, 6, 32, 1, 1), 0, {"ahead": 22.0, "spacing": 6.0}),
 }
 # the shape on which each class of leaf rows binds on its own: with only that class decided the oracle's objective lies above the regions-only one
 CLASS_BINDS_ON = {"env_front": ["c2n6e2pent"], "obs_rear": ["c1n6r16hex", "c1n21o", "c2n20a"], "obs_front": ["c1n2r32o", "c1n6r16hex", "c2n6e2pent", "c2n20b"],
@@ -206,6 +210,88 @@ def infeasible_record(r, cls, key, alt):
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# soft levels: the canonical complete record of a node shape on the SAME instance with one obstacle made soft (obstacle_is_soft a mask,
+# WEIGHTS_SLACK_OBSTACLE = SOFT_WEIGHT), and a chosen set of that obstacle's points (car, step >= 1, point 0..4) marked as ignored: every deltacc
+# entry of the point 1 and its slack entry 1, everything else decided as in the record.  Both solvers turn such a point into the byte L of their
+# fix records: no row, SOFT_WEIGHT added to the objective.  Removing rows keeps a feasible QP feasible, so every soft level is feasible.
+# (shape, mask): the smallest shapes that reach each launch - N = 2; L = 6 (byte L is not 4); two cars with L = 5 and two environment pieces; cfg4's
+# shape, four obstacles, so the soft flag is indexed per obstacle and a hard obstacle stands beside the soft one (two masks, two seeds); the
+# memory-backed kernel without an on-chip stage; the wide kernel of three cars.
+SOFT_WEIGHT = 0.37
+SOFT_CASES = [("c1n2r32o", (1,)), ("c1n6r16hex", (1,)), ("c2n6e2pent", (1,)), ("c2n20a", (0, 1, 0, 0)), ("c2n20a", (1, 0, 0, 0)), ("c2n20b", (0, 1, 0, 0)),
+              ("c1n21o", (1,)), ("c3n6o", (1,))]
+SOFT_LEVELS = ["soft_all", "soft_rear", "soft_front", "soft_odd_steps", "soft_step1", "soft_third_undecided"]
+_SOFT = {}
+
+
+def soft_tag(name, mask):
+    return name + "/" + "".join(str(m) for m in mask)
+
+
+# Point sets replaced by the degeneracy rule (test_node_records_cpu.py: the oracle's states move by less than 1e-5 between QP_TOL_FINAL and a tolerance 100
+# times looser).  c2n20b's soft_third_undecided with the odd steps ignored moves by 1.38e-5 (its hard 'third' level alone by 1.7e-6; the soft obstacle's
+# rows are slack on this seed, so the ignored points add only their price); with the EVEN steps ignored it moves by 3.0e-6.
+SOFT_EVEN_STEPS = {("c2n20b", (0, 1, 0, 0), "soft_third_undecided")}
+
+
+def soft_points(name, dims, mask, level):
+    """the ignored points (car, obstacle, step, point) of a soft level; point 0 is the rear point, 1..4 the front points in deltacc_front's order"""
+    C_, N, R, E, O, L = dims
+    o = list(mask).index(1)
+    odd = 0 if (name, tuple(mask), level) in SOFT_EVEN_STEPS else 1
+    keep = {"soft_all": lambda i, pt: True, "soft_rear": lambda i, pt: pt == 0, "soft_front": lambda i, pt: pt >= 1,
+            "soft_odd_steps": lambda i, pt: i % 2 == 1, "soft_step1": lambda i, pt: i == 1, "soft_third_undecided": lambda i, pt: i % 2 == odd}[level]
+    return [(c, o, i, pt) for c in range(C_) for i in range(1, N) for pt in range(5) if keep(i, pt)]
+
+
+def mark_ignored(r, points):
+    """in place: the points' deltacc entries all 1 and their slack entries 1"""
+    for c, o, i, pt in points:
+        if pt == 0:
+            r.deltacc[c, o, i, :] = 1; r.slackvarsObstacle[c, o, i] = 1
+        else:
+            r.deltacc_front[c, o, i, :, pt - 1] = 1; r.slackvarsObstacle_front[c, o, i, pt - 1] = 1
+
+
+def ignored_points(r):
+    """the points (car, obstacle, step, point) whose slack entry is 1 in a record, sorted"""
+    return sorted([(c, o, i, 0) for c, o, i in zip(*np.nonzero(r.slackvarsObstacle))] + [(c, o, i, q + 1) for c, o, i, q in zip(*np.nonzero(r.slackvarsObstacle_front))])
+
+
+def soft_levels(name, rec, mask):
+    """{level: (record, ignored points)} of the canonical complete record of a shape for SOFT_LEVELS; soft_third_undecided starts from the 'third' level
+    of relax_levels, so that bytes L, -1 and decided bytes stand side by side in one fix record"""
+    out = {}
+    for level in SOFT_LEVELS:
+        r = copy_record(relax_levels(rec, RELAX_SEED[name])["third"][0] if level == "soft_third_undecided" else rec)
+        pts = soft_points(name, rec.dims, mask, level)
+        mark_ignored(r, pts)
+        out[level] = (r, sorted(pts))
+    return out
+
+
+def _generate(name):
+    from planner_miqp_amd import synthetic
+    cfg, seed, tweaks = NODE_SHAPES[name]
+    p = synthetic.generate(cfg, seed, gap=1e-7, max_time=30)
+    tweak_instance(p, **tweaks)
+    return p
+
+
+def soft_instance(oracle, name, mask):
+    """(parameters, oracle handle, dims, canonical complete record) of a soft case: the parameters of NODE_SHAPES[name] generated again with the mask and
+    the weight set - a second handle; node_instance's own stays hard - and the record of node_instance (no new search).  Kept for the session."""
+    if (name, mask) not in _SOFT:
+        p0, h0, dims, rec = node_instance(oracle, name)
+        p = _generate(name)
+        assert len(mask) == dims[4] and sum(mask) == 1
+        p.obstacle_is_soft = [int(m) for m in mask]
+        p.WEIGHTS_SLACK_OBSTACLE = SOFT_WEIGHT
+        _SOFT[(name, mask)] = (p, oracle.from_params(p, 10), dims, rec)
+    return _SOFT[(name, mask)]
+
+
 _INCUMBENTS = {}
 NODE_LIMIT = 800   # nodes of the oracle's dive for the incumbent; nothing else ends it (no time limit), so the record is the same on every machine
 
@@ -241,10 +327,7 @@ def node_instance(oracle, name):
     incumbents of its dive (loose gap, ended by NODE_LIMIT nodes and by no clock: the same record on every machine, which the expected-route
     table of test_node_qp_gpu.py relies on), not an optimum - canonicalised.  Kept for the session."""
     if name not in _INCUMBENTS:
-        from planner_miqp_amd import synthetic
-        cfg, seed, tweaks = NODE_SHAPES[name]
-        p = synthetic.generate(cfg, seed, gap=1e-7, max_time=30)
-        tweak_instance(p, **tweaks)
+        p = _generate(name)
         h = oracle.from_params(p, 10)
         dims = oracle.dims(p)
         st, res, props = oracle.solve(h, dims, gap=0.5, time_limit=1e9, max_nodes=NODE_LIMIT)

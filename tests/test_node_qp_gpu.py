@@ -12,8 +12,8 @@ they are switched on by the mask bytes at f_c2n of a fix record, which only the 
 record has no field for them, fix_from_results leaves them at -1 (decode_row and slot_maybe then skip every slot of the class), and the oracle has no
 row of that meaning.  They stay covered end to end only.
 
-Out of scope: soft obstacles (the oracle's solve_fixed has no slack or constant-cost path for them; test_soft_obstacle_can_be_ignored_at_its_price
-covers them end to end) and the active-set kernels (solve_fixed runs the interior point chain only).
+Soft obstacles - fix records that ignore points of an obstacle, the byte L and its price - are held against the oracle in the same way in
+test_node_qp_soft_gpu.py.  Out of scope: the active-set kernels (solve_fixed runs the interior point chain only).
 All tests here need a real MI355X: run with  python -m pytest tests/test_node_qp_gpu.py -m gpu."""
 import numpy as np
 import pytest
@@ -34,7 +34,7 @@ CASES = [(name, level) for name in H.NODE_SHAPES for level in H.level_names(H.sh
 # 2 the memory-backed kernel behind them, 3 the memory-backed kernel of a shape without an on-chip kernel (more than 20 steps, three and four cars).
 # Found on the device when the test was written; a shift of a capacity or of the number of rows the decode finds shows here.  With two cars the
 # region rows alone fill the standard block from 8 steps on, so every level of "mini" and the region-only levels of cfg4's shape are the larger block's.
-_NO_ONCHIP = ("c1n21o", "c1n40o", "mini3", "mini4")
+_NO_ONCHIP = ("c1n21o", "c1n40o", "mini3", "mini4", "c3n6o")
 _CFG4 = ("c2n20a", "c2n20b", "c2n20c")
 EXPECTED_ROUTE = {(name, level): 3 if name in _NO_ONCHIP else 0 for name, level in CASES}
 EXPECTED_ROUTE.update({("mini", level): 1 for level in ("complete", "third", "two_thirds", "regions_only")})
