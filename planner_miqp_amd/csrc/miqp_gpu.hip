@@ -1688,11 +1688,10 @@ bool solve_batch_impl(miqp_solver_t* const* S, int n, int* statuses, const Split
 }  // namespace
 
 #include "certify.hip"
+#include "fixed_chain.hip"
 #include "fixed_batch.hip"
 #include "solution_pool.hip"
-#include "fixed_multi.hip"
 #include "pool_improve.hip"
-#include "pool_improve_multi.hip"
 #include "pool_explore.hip"
 
 // ================================================================================================
@@ -2249,7 +2248,7 @@ int miqp_solver_solve_fixed(miqp_solver_t* s, const miqp_raw_results_c* fixed, m
   s->fixed_route = X.oc_grid <= 0 ? 3 : ovf == 0 ? 0 : (X.ocb_grid > 0 && ovf2 == 0) ? 1 : 2;
   HostGeo G{s->inst, Y, D.data(), T.data()}; double cobj = 0; (void)step0_check(G, cobj);
   // the points the record ignores cost WEIGHTS_SLACK_OBSTACLE each: a constant no node kernel charges (eval_kernel adds it for the search, soft_cost of
-  // fixed_batch.hip for the batch calls, in this order of operations)
+  // fixed_chain.hip for the batch calls, in this order of operations)
   int nign = 0; for (int q = 0; q < Y.C * Y.O * Y.N * 5; ++q) nign += fix[Y.f_obs + q] >= Y.L;
   // (the product is ROUNDED before the sum, as __dmul_rn rounds it in soft_cost: the volatile keeps a host compiler that may fuse - an FMA target
   // with fp-contract on - from doing so, or the batch calls would differ from this one in the last bit)

@@ -20,7 +20,7 @@
 // The call, per pass, all on the solver stream (pass 1 expands every kept entry, pass p > 1 the entries pass p - 1 added):
 //   pool_jumps_kernel      one wavefront per place of the pool: the record staged in LDS, one lane per unit (in a loop when there are more units
 //                          than lanes) counts its jumps, a wave scan over the per-unit counts numbers them, the lanes write them to the move table
-//   pool_offsets_kernel, pool_neighbour_kernel, launch_ipm_batch, fixed_batch_collect_kernel
+//   pool_offsets_kernel, pool_neighbour_kernel, fixed_chunk
 //                          the climb's, unchanged, chunk by chunk: at most 16 entries of 512 jumps are the 8192 results the climb holds - no slices
 //   pool_admit_kernel      ONE wavefront: the objectives of the pass's feasible neighbours within the cost cap staged in LDS; then, as long as a
 //                          place is free, the smallest (objective, neighbour number) by wave reduction, its patched record and that record's signature
@@ -225,7 +225,7 @@ __global__ __launch_bounds__(64) void pool_admit_kernel(const PoolExploreArgs E,
   if (lane == 0) { E.state[0] = n; E.state[1] = added; E.state[2] = it; }
 }
 
-// buffers of the call beside the climb's (PoolImproveDev), cached per device (grown, not shrunk)
+// buffers of the call beside the climb's (PoolImproveDev, PoolEntryDev), cached per device (grown, not shrunk)
 struct PoolExploreDev {
   signed char* sig = nullptr; size_t sig_cap = 0; int* state = nullptr; miqp_pool_explore_c* out = nullptr;
   bool ensure(size_t fl) {
@@ -250,10 +250,11 @@ struct PoolExploreOut {
 };
 
 // false: HIP error (nothing of the handle has been touched).  n: entries in the pool, K: its places
-bool pool_explore_run(DevCtx& X, PoolImproveDev& G, PoolExploreDev& Q, const FixedBatchCall& call, int fam, int L, const signed char* fix, int n, int K, double obj0,
-                      double max_rel, int max_passes, PoolExploreOut& O) {
-  DevBuf& B = X.B; hipStream_t st = X.stream; const Layout& Y = call.Y;
-  const size_t fl = (size_t)Y.fixlen, row = (size_t)Y.N * Y.nz;
+bool pool_explore_run(const FixedCall& call, int fam, int L, const signed char* fix, int n, int K, double obj0, double max_rel, int max_passes, PoolExploreOut& O) {
+  DevCtx& X = *call.X; DevBuf& B = X.B; hipStream_t st = X.stream; const Layout& Y = call.Y;
+  const size_t fl = (size_t)Y.fixlen;
+  PoolImproveDev& R = g_pool_improve_dev[X.device]; PoolEntryDev& G = g_pool_entry_dev[X.device]; PoolExploreDev& Q = g_pool_explore_dev[X.device];
+  if (!R.ensure((size_t)Y.N * Y.nz) || !G.ensure(MIQP_POOL_MAX, fl) || !Q.ensure(fl)) return false;
   const PoolDims dims = pool_dims(Y);
   const size_t jump_lds = fl + (size_t)pool_jump_units(dims) * sizeof(int), admit_lds = 2 * fl + (size_t)PoolImproveDev::NB_MAX * sizeof(double);
   if (std::max(jump_lds, admit_lds) > POOL_EXPLORE_LDS_MAX) {
@@ -262,12 +263,8 @@ bool pool_explore_run(DevCtx& X, PoolImproveDev& G, PoolExploreDev& Q, const Fix
   }
   HIP_OK(hipFuncSetAttribute((const void*)pool_jumps_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)jump_lds));
   HIP_OK(hipFuncSetAttribute((const void*)pool_admit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)admit_lds));
-  std::vector<int> ident(FB_CHUNK); for (int k = 0; k < FB_CHUNK; ++k) ident[k] = k;
   std::vector<int> act(MIQP_POOL_MAX, 0); for (int k = 0; k < n; ++k) act[k] = 1;
   const int state0[4] = {n, 0, 0, 0};
-  HIP_OK(hipMemcpyAsync((void*)B.inst_d, call.D.data(), call.D.size() * 8, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync((void*)B.inst_i, call.T.data(), call.T.size() * 4, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(B.batch_node, ident.data(), (size_t)FB_CHUNK * 4, hipMemcpyHostToDevice, st));
   HIP_OK(hipMemsetAsync(B.batch_inst, 0, (size_t)FB_CHUNK * 4, st));
   HIP_OK(hipMemsetAsync(G.cur, 0xFF, (size_t)MIQP_POOL_MAX * fl, st));
   HIP_OK(hipMemcpyAsync(G.cur, fix, (size_t)n * fl, hipMemcpyHostToDevice, st));
@@ -276,30 +273,20 @@ bool pool_explore_run(DevCtx& X, PoolImproveDev& G, PoolExploreDev& Q, const Fix
   HIP_OK(hipMemsetAsync(G.cnt, 0, MIQP_POOL_MAX * sizeof(int), st)); HIP_OK(hipMemsetAsync(G.cur_obj, 0, MIQP_POOL_MAX * sizeof(double), st));
   HIP_OK(hipMemsetAsync(G.ent_inst, 0, MIQP_POOL_MAX * sizeof(int), st)); HIP_OK(hipMemsetAsync(G.off, 0, (MIQP_POOL_MAX + 1) * sizeof(int), st));
   HIP_OK(hipMemsetD32Async((hipDeviceptr_t)G.ent_fam, fam, MIQP_POOL_MAX, st));
-  DevBuf Bp = B; Bp.qp_tol = QP_TOL_FINAL; Bp.use_cutoff = 0; Bp.ws_on = 0;
+  const DevBuf Bp = fixed_chain_settings(B);
   PoolExploreArgs E;
   PoolImproveArgs& A = E.A;
-  A.cur = G.cur; A.cur_obj = G.cur_obj; A.act = G.act; A.cnt = G.cnt; A.moves = G.moves; A.words = G.words; A.res = G.res; A.pool_fix = B.pool_fix;
+  A.cur = G.cur; A.cur_obj = G.cur_obj; A.act = G.act; A.cnt = G.cnt; A.moves = G.moves; A.words = G.words; A.res = R.res; A.pool_fix = B.pool_fix;
   A.ent_inst = G.ent_inst; A.ent_fam = G.ent_fam; A.off = G.off; A.batch_inst = B.batch_inst;
   A.dims = dims; A.fixlen = (int)fl; A.m = K;   // (every place of the pool is an entry of the kernels: a free one is not expanded and has no jumps)
   E.L = L; E.sig = Q.sig; E.state = Q.state; E.out = Q.out; E.obj0 = obj0; E.max_rel = max_rel; E.pass = 0;
-  // `total` neighbours of a pass through the chain, a chunk at a time (the per-chunk resets of fixed_batch_run, as the climb has them)
+  // `total` neighbours of a pass through the chain, a chunk at a time, as the climb sends them (no segments, the trajectories written over)
   auto solve_nodes = [&](int total) -> bool {
-    for (int c0 = 0, j = 0; c0 < total; c0 += FB_CHUNK, ++j) {
+    for (int c0 = 0; c0 < total; c0 += FB_CHUNK) {
       const int bc = std::min(FB_CHUNK, total - c0);
       hipLaunchKernelGGL(pool_neighbour_kernel, dim3((bc + 3) / 4), dim3(256), 0, st, A, c0, bc, 0);
       HIP_OK(hipGetLastError());
-      HIP_OK(hipMemsetD32Async((hipDeviceptr_t)B.batch_count, bc, 1, st));
-      HIP_OK(hipMemsetAsync(B.pool_big, 0, (size_t)bc, st)); HIP_OK(hipMemsetAsync(B.batch_large, 0, (size_t)bc, st)); HIP_OK(hipMemsetAsync(B.batch_depth, 0, (size_t)bc * 4, st));
-      HIP_OK(hipMemsetAsync(B.inst_nodes, 0, 8, st)); HIP_OK(hipMemsetAsync(B.inst_iters, 0, 8, st)); HIP_OK(hipMemsetAsync(B.stat_rowiters, 0, 8, st));
-      launch_ipm_batch(X, Bp, bc, st);
-      FixedBatchArgs F;
-      F.ovf_list = B.ovf_list; F.ovf_count = B.ovf_count; F.ovf2_list = B.ovf2_list; F.ovf2_count = B.ovf2_count;
-      F.batch_ok = B.batch_ok; F.batch_it = B.batch_it; F.batch_obj = B.batch_obj; F.batch_viol = B.batch_viol; F.batch_Z = B.batch_Z;
-      F.res = G.res + c0; F.Z = G.Z; F.best_obj = G.best_obj + j; F.best_idx = G.best_idx + j;
-      F.bc = bc; F.base = c0; F.row_doubles = (int)row; F.onchip = X.oc_grid > 0 ? 1 : 0; F.big = X.ocb_grid > 0 ? 1 : 0; F.cobj = call.cobj; F.soft = soft_cost_args(B, call.Y);
-      hipLaunchKernelGGL(fixed_batch_collect_kernel, dim3(1 + std::min(FB_ROW_BLOCKS, (bc + FB_NT / 64 - 1) / (FB_NT / 64))), dim3(FB_NT), 0, st, F);
-      HIP_OK(hipGetLastError());
+      if (!fixed_chunk(X, Bp, Y, call.dev(), 1, FixedChunk{bc, c0, R.res + c0, R.Z})) return false;
     }
     return true;
   };
@@ -373,12 +360,10 @@ int miqp_solver_pool_explore(miqp_solver_t* s, int max_passes, double max_rel, m
   if (!bs.ok || bs.Y.fixlen != s->pool_fixlen || s->pool_fix.size() < (size_t)n * bs.Y.fixlen || s->pool_obj.size() < (size_t)n) return -1;
   const Layout& Y = bs.Y; const size_t fl = (size_t)Y.fixlen;
   const double t_call = wall_s();
-  FixedBatchCall call;
-  if (call.open(s, Y) != 0) return -3;
-  PoolImproveDev& G = g_pool_improve_dev[call.X->device]; PoolExploreDev& Q = g_pool_explore_dev[call.X->device];
+  FixedCall call;
+  if (call.open(one, 1, Y) != 0) return -3;
   PoolExploreOut O;
-  if (!G.ensure(fl, (size_t)Y.N * Y.nz) || !Q.ensure(fl) ||
-      !pool_explore_run(*call.X, G, Q, call, s->pool_fam, s->inst.L, s->pool_fix.data(), n, K, s->pool_obj[0], max_rel, max_passes, O)) {
+  if (!pool_explore_run(call, s->pool_fam, s->inst.L, s->pool_fix.data(), n, K, s->pool_obj[0], max_rel, max_passes, O)) {
     (void)hipStreamSynchronize(call.X->stream); if (!O.err.empty()) s->err = O.err; return -3;
   }
   const int added = (int)O.added.size();

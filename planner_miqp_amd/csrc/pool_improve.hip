@@ -1,5 +1,6 @@
-// pool_improve.hip - every kept entry of the solution pool hill-climbed inside its own manoeuvre class (miqp_solver_pool_improve), and decision
-// records through the fixed-batch chain (miqp_solver_solve_decisions).  DESIGN.md 6f.
+// pool_improve.hip - every kept entry of the solution pool hill-climbed inside its own manoeuvre class, for one handle (miqp_solver_pool_improve) and for
+// the pools of many in one device call (miqp_solver_pool_improve_multi; the slices of a pass as a pure host function, miqp_gpu_pool_improve_plan), and
+// decision records through the fixed chain (miqp_solver_solve_decisions).  DESIGN.md 6f, 6g.
 //
 // The manoeuvre filter (solution_pool.hip) keeps one entry per class, and what it keeps is the smallest LEAF of the class the search happened to
 // evaluate, not the class's best trajectory.  What separates such a leaf from a good one is WHEN a car changes its alternative, not WHAT it changes
@@ -24,12 +25,26 @@
 //   pool_neighbour_kernel  one wavefront per node of the chunk being launched: neighbour number -> (entry, move) by binary search in the scan, the
 //                          entry's current record in 16-byte loads, the move patched in registers, 16-byte stores into slot k of pool_fix; the
 //                          entry's instance into slot k of batch_inst
-//   launch_ipm_batch       the chain of the fixed batch with its settings (QP_TOL_FINAL, no cutoff, cold start), fixed_batch_collect_kernel behind it
+//   fixed_chunk            the chain of the fixed calls with its resets and settings and fixed_collect_kernel behind it, without segments (fixed_chain.hip)
 //   pool_pick_kernel       one wavefront per entry over its contiguous range of results: the feasible neighbour of the lowest objective, ties to the
 //                          lower move number; accepted when it is below the entry's objective by more than 1e-9 (1 + |objective|) - then the move is
 //                          patched into the entry's current record and the objective replaced
-// The kernels serve the entries of MANY handles as well (pool_improve_multi.hip: per entry its handle's index and filter; the results of a pass kept a
-// SLICE of entries at a time); this file's call is their one-handle case - every entry instance 0 and the handle's filter, one slice.
+// MANY HANDLES.  The product's path is a drained queue of hundreds to thousands of handles, and a loop of one-handle calls over them pays per handle a
+// device lock, a compile_instance, an upload of the tables, per pass a chain of launches that is as long for 19 neighbours as for 1024, and per pass a
+// host synchronisation.  So the climb is written over the entries of n handles, numbered handle-major in the caller's order: every entry carries its
+// handle's index in the call (ent_inst, which pool_neighbour_kernel writes to batch_inst beside the node's record, so that the node kernels read that
+// handle's tables) and its handle's filter (ent_fam, which pool_moves_kernel reads); the dims are common (batch_layout).  ONE pass of the call is one
+// pass of every handle that still moves, and the neighbours of all of them fill common launch groups of FB_CHUNK nodes.  Per entry nothing else
+// differs, so a handle's entries get the same bits whatever else is in the call: a node's answer is a function of its record and its instance's
+// tables alone.  miqp_solver_pool_improve is the call with one handle.
+//
+// SLICES.  The results of a pass are not all kept at once: a slice is a run of whole entries whose neighbours fit PoolImproveDev::NB_MAX results,
+// formed greedily in entry order (miqp_gpu_pool_improve_plan; the host loop calls that very function).  Per slice: its nodes in chunks of FB_CHUNK
+// through pool_neighbour_kernel and fixed_chunk into the slice's results, pool_pick_kernel over the slice's entries.  Behind the last slice
+// pool_moves_kernel and pool_offsets_kernel for the next pass.  The host knows the counts of a pass from the read-back of the pass before, enqueues
+// all slices without waiting and synchronises once per pass.  Pass 0 - every entry's own record - is the same loop with one node per entry.
+// Device memory: entries x (record + POOL_MOVES_MAX moves of 16 bytes + a few words), grown, not shrunk, cached per device, beside the fixed slice
+// buffers; it does not depend on the number of neighbours.
 // Owner computes: no atomics, no lock, no wavefront waits on another, no scratch.  The host reads back, per pass, one (accepted, iterations,
 // objective) triple and one move count per entry.  An entry that did not move in a pass is not expanded again: its record, hence its neighbours and
 // their answers, would be the ones just rejected.  (The literal loop - every live entry expanded in every pass - ends on the same records and
@@ -90,7 +105,7 @@ struct PoolWord { int accepted, iterations; double objective; };   // what the h
 
 struct PoolImproveArgs {
   signed char* cur; double* cur_obj; int* act; int* cnt; int4* moves; PoolWord* words;   // per entry: current record and objective, expand it in the next pass, moves of this pass
-  const int* ent_inst; const int* ent_fam;   // per entry: its handle's index in the call (0 in the single call) and that handle's filter
+  const int* ent_inst; const int* ent_fam;   // per entry: its handle's index in the call and that handle's filter
   int* off;                         // [m + 1] exclusive scan of the clamped move counts (pool_offsets_kernel): neighbour off[e] + j is move j of entry e, off[m] the pass total
   const miqp_fixed_result_c* res;   // of the first node of the SLICE being picked (a slice: a run of whole entries whose nodes fit NB_MAX results)
   signed char* pool_fix;            // the chain's fix records: slot k of the chunk
@@ -229,32 +244,12 @@ __global__ __launch_bounds__(64) void pool_pick_kernel(const PoolImproveArgs A, 
 }
 
 // ---------------------------------------------------------------------------------------------------------------- device cache
-// buffers of the climb, cached per device like FixedBatchDev and never taken from the solver's pools (grown, not shrunk)
+// buffers of the climb and the explore, cached per device like FixedDev and never taken from the solver's pools (grown, not shrunk).  The slice buffers:
 struct PoolImproveDev {
-  signed char* cur = nullptr; size_t cur_cap = 0; double* Z = nullptr; size_t z_cap = 0;
-  double* cur_obj = nullptr; int* act = nullptr; int* cnt = nullptr; int4* moves = nullptr; PoolWord* words = nullptr;
-  miqp_fixed_result_c* res = nullptr; double* best_obj = nullptr; int* best_idx = nullptr;
-  int* ent_inst = nullptr; int* ent_fam = nullptr; int* off = nullptr;   // what the kernels read per entry since they serve many handles: 0, the handle's filter; the scan
-  static constexpr int NB_MAX = MIQP_POOL_MAX * POOL_MOVES_MAX;   // neighbours of a pass
-  bool ensure(size_t fl, size_t row) {
-    // (each of the fixed-size buffers on its own: an allocation that failed half-way is taken up where it stopped, nothing is allocated twice)
-    if (!cur_obj) HIP_OK(hipMalloc((void**)&cur_obj, MIQP_POOL_MAX * sizeof(double)));
-    if (!act) HIP_OK(hipMalloc((void**)&act, MIQP_POOL_MAX * sizeof(int)));
-    if (!cnt) HIP_OK(hipMalloc((void**)&cnt, MIQP_POOL_MAX * sizeof(int)));
-    if (!words) HIP_OK(hipMalloc((void**)&words, MIQP_POOL_MAX * sizeof(PoolWord)));
+  miqp_fixed_result_c* res = nullptr; double* Z = nullptr; size_t z_cap = 0;
+  static constexpr int NB_MAX = MIQP_POOL_MAX * POOL_MOVES_MAX;   // results of a slice
+  bool ensure(size_t row) {
     if (!res) HIP_OK(hipMalloc((void**)&res, (size_t)NB_MAX * sizeof(miqp_fixed_result_c)));
-    if (!best_obj) HIP_OK(hipMalloc((void**)&best_obj, (NB_MAX / FB_CHUNK + 1) * sizeof(double)));
-    if (!best_idx) HIP_OK(hipMalloc((void**)&best_idx, (NB_MAX / FB_CHUNK + 1) * sizeof(int)));
-    if (!moves) HIP_OK(hipMalloc((void**)&moves, (size_t)NB_MAX * sizeof(int4)));
-    if (!ent_inst) HIP_OK(hipMalloc((void**)&ent_inst, MIQP_POOL_MAX * sizeof(int)));
-    if (!ent_fam) HIP_OK(hipMalloc((void**)&ent_fam, MIQP_POOL_MAX * sizeof(int)));
-    if (!off) HIP_OK(hipMalloc((void**)&off, (MIQP_POOL_MAX + 1) * sizeof(int)));
-    if (MIQP_POOL_MAX * fl > cur_cap) {
-      if (cur) (void)hipFree(cur);
-      cur = nullptr; cur_cap = 0;
-      HIP_OK(hipMalloc((void**)&cur, MIQP_POOL_MAX * fl));
-      cur_cap = MIQP_POOL_MAX * fl;
-    }
     if ((size_t)FB_CHUNK * row > z_cap) {   // (the collect kernel copies the chunk's trajectories: the climb has no use for them, one chunk's worth is written over)
       if (Z) (void)hipFree(Z);
       Z = nullptr; z_cap = 0;
@@ -266,92 +261,200 @@ struct PoolImproveDev {
 };
 std::map<int, PoolImproveDev> g_pool_improve_dev;   // by device ordinal; used under the device lock
 
+// ... and the per-entry buffers: never fewer than the MIQP_POOL_MAX places the explore fills
+struct PoolEntryDev {
+  signed char* cur = nullptr; size_t cur_cap = 0;
+  double* cur_obj = nullptr; int* act = nullptr; int* cnt = nullptr; int* off = nullptr; int* ent_inst = nullptr; int* ent_fam = nullptr;
+  int4* moves = nullptr; PoolWord* words = nullptr; size_t ent_cap = 0;
+  void drop_entries() {
+    if (cur_obj) (void)hipFree(cur_obj); if (act) (void)hipFree(act); if (cnt) (void)hipFree(cnt); if (off) (void)hipFree(off);
+    if (ent_inst) (void)hipFree(ent_inst); if (ent_fam) (void)hipFree(ent_fam); if (moves) (void)hipFree(moves); if (words) (void)hipFree(words);
+    cur_obj = nullptr; act = nullptr; cnt = nullptr; off = nullptr; ent_inst = nullptr; ent_fam = nullptr; moves = nullptr; words = nullptr; ent_cap = 0;
+  }
+  bool ensure(size_t m, size_t fl) {
+    static_assert(MIQP_POOL_MAX <= 64, "the smallest allocation holds a pool");
+    if (m > ent_cap) {
+      drop_entries();
+      size_t want = 64; while (want < m) want <<= 1;
+      HIP_OK(hipMalloc((void**)&cur_obj, want * sizeof(double))); HIP_OK(hipMalloc((void**)&act, want * sizeof(int))); HIP_OK(hipMalloc((void**)&cnt, want * sizeof(int)));
+      HIP_OK(hipMalloc((void**)&off, (want + 1) * sizeof(int))); HIP_OK(hipMalloc((void**)&ent_inst, want * sizeof(int))); HIP_OK(hipMalloc((void**)&ent_fam, want * sizeof(int)));
+      HIP_OK(hipMalloc((void**)&words, want * sizeof(PoolWord))); HIP_OK(hipMalloc((void**)&moves, want * POOL_MOVES_MAX * sizeof(int4)));
+      ent_cap = want;   // (set when all eight are there: a failure half-way is taken up from the start)
+    }
+    if (m * fl > cur_cap) {
+      if (cur) (void)hipFree(cur);
+      cur = nullptr; cur_cap = 0;
+      size_t want = 64 * fl; while (want < m * fl) want <<= 1;
+      HIP_OK(hipMalloc((void**)&cur, want));
+      cur_cap = want;
+    }
+    return true;
+  }
+};
+std::map<int, PoolEntryDev> g_pool_entry_dev;   // by device ordinal; used under the device lock
+
+// the slices of a pass, greedily in entry order: an entry opens a new slice when its (clamped) moves do not fit the results left of the current one
+int pool_improve_slices(const int* move_counts, int entries, int* slice_first, int cap) {
+  int ns = 1, sum = 0;
+  for (int e = 0; e < entries; ++e) {
+    const int c = std::min(std::max(move_counts[e], 0), POOL_MOVES_MAX);
+    if (sum + c > PoolImproveDev::NB_MAX) { ns++; sum = 0; }
+    sum += c;
+  }
+  if (ns + 1 > cap) return -3;
+  ns = 0; sum = 0; slice_first[0] = 0;
+  for (int e = 0; e < entries; ++e) {
+    const int c = std::min(std::max(move_counts[e], 0), POOL_MOVES_MAX);
+    if (sum + c > PoolImproveDev::NB_MAX) { slice_first[++ns] = e; sum = 0; }
+    sum += c;
+  }
+  slice_first[++ns] = entries;
+  return ns;
+}
+
 struct PoolImproveOut {
-  std::vector<PoolWord> first;          // pass 0
-  std::vector<double> after; std::vector<int> moves;
-  std::vector<signed char> fix;         // the m records at the end
-  int passes = 0; long neighbours = 0, iterations = 0; bool still_moving = false; float dev_ms = 0.0f;
+  std::vector<PoolWord> first;   // pass 0, per entry
+  std::vector<double> after; std::vector<int> moves;   // per entry
+  std::vector<signed char> fix;  // the m records at the end
+  std::vector<int> passes; std::vector<long> neighbours, iterations; std::vector<char> still_moving;   // per handle
+  float dev_ms = 0.0f;
   std::string err;
 };
 
-// false: HIP error (nothing of the handle has been touched)
-bool pool_improve_run(DevCtx& X, PoolImproveDev& G, const FixedBatchCall& call, int fam, const signed char* fix, int m, int max_passes, PoolImproveOut& O) {
-  DevBuf& B = X.B; hipStream_t st = X.stream; const Layout& Y = call.Y;
+// m entries of the call's handles (einst[e] ascending: the handle of entry e; efam[e] its filter; hfirst[h] .. hfirst[h + 1] the entries of handle h;
+// `name`: the entry point, for the messages).  false: HIP error or the LDS refusal (O.err); nothing of any handle has been touched
+bool pool_improve_run(const FixedCall& call, const char* name, const signed char* fix, const std::vector<int>& einst, const std::vector<int>& efam, const std::vector<int>& hfirst,
+                      int m, int max_passes, PoolImproveOut& O) {
+  DevCtx& X = *call.X; const Layout& Y = call.Y; const int n_inst = call.n;
+  DevBuf& B = X.B; hipStream_t st = X.stream;
   const size_t fl = (size_t)Y.fixlen, row = (size_t)Y.N * Y.nz;
+  PoolImproveDev& G = g_pool_improve_dev[X.device]; PoolEntryDev& M = g_pool_entry_dev[X.device];
+  if (!G.ensure(row) || !M.ensure((size_t)m, fl)) return false;
   const PoolDims dims = pool_dims(Y);
-  std::vector<int> ident(FB_CHUNK); for (int k = 0; k < FB_CHUNK; ++k) ident[k] = k;
-  HIP_OK(hipMemcpyAsync((void*)B.inst_d, call.D.data(), call.D.size() * 8, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync((void*)B.inst_i, call.T.data(), call.T.size() * 4, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(B.batch_node, ident.data(), (size_t)FB_CHUNK * 4, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemsetAsync(B.batch_inst, 0, (size_t)FB_CHUNK * 4, st));
-  HIP_OK(hipMemcpyAsync(G.cur, fix, (size_t)m * fl, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemsetAsync(G.cnt, 0, MIQP_POOL_MAX * sizeof(int), st)); HIP_OK(hipMemsetAsync(G.act, 0, MIQP_POOL_MAX * sizeof(int), st));
-  HIP_OK(hipMemsetAsync(G.ent_inst, 0, MIQP_POOL_MAX * sizeof(int), st)); HIP_OK(hipMemsetAsync(G.off, 0, (MIQP_POOL_MAX + 1) * sizeof(int), st));
-  HIP_OK(hipMemsetD32Async((hipDeviceptr_t)G.ent_fam, fam, MIQP_POOL_MAX, st));
-  DevBuf Bp = B; Bp.qp_tol = QP_TOL_FINAL; Bp.use_cutoff = 0; Bp.ws_on = 0;
-  PoolImproveArgs A;
-  A.cur = G.cur; A.cur_obj = G.cur_obj; A.act = G.act; A.cnt = G.cnt; A.moves = G.moves; A.words = G.words; A.res = G.res; A.pool_fix = B.pool_fix;
-  A.ent_inst = G.ent_inst; A.ent_fam = G.ent_fam; A.off = G.off; A.batch_inst = B.batch_inst;
-  A.dims = dims; A.fixlen = (int)fl; A.m = m;
   const size_t gen_lds = 3 * fl + (size_t)pool_sites(dims) * sizeof(int);
-  if (gen_lds > POOL_MOVES_LDS_MAX) { O.err = "miqp_solver_pool_improve: the fix record of this shape does not fit the LDS of pool_moves_kernel three times"; std::fprintf(stderr, "[miqp_gpu] %s (%zu bytes)\n", O.err.c_str(), gen_lds); return false; }
+  if (gen_lds > POOL_MOVES_LDS_MAX) { O.err = std::string(name) + ": the fix record of this shape does not fit the LDS of pool_moves_kernel three times"; std::fprintf(stderr, "[miqp_gpu] %s (%zu bytes)\n", O.err.c_str(), gen_lds); return false; }
   HIP_OK(hipFuncSetAttribute((const void*)pool_moves_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gen_lds));
-  // `total` nodes of a pass through the chain, a chunk at a time (the per-chunk resets of fixed_batch_run)
-  auto solve_nodes = [&](int total, int own) -> bool {
-    for (int c0 = 0, j = 0; c0 < total; c0 += FB_CHUNK, ++j) {
-      const int bc = std::min(FB_CHUNK, total - c0);
-      hipLaunchKernelGGL(pool_neighbour_kernel, dim3((bc + 3) / 4), dim3(256), 0, st, A, c0, bc, own);
-      HIP_OK(hipGetLastError());
-      HIP_OK(hipMemsetD32Async((hipDeviceptr_t)B.batch_count, bc, 1, st));
-      HIP_OK(hipMemsetAsync(B.pool_big, 0, (size_t)bc, st)); HIP_OK(hipMemsetAsync(B.batch_large, 0, (size_t)bc, st)); HIP_OK(hipMemsetAsync(B.batch_depth, 0, (size_t)bc * 4, st));
-      HIP_OK(hipMemsetAsync(B.inst_nodes, 0, 8, st)); HIP_OK(hipMemsetAsync(B.inst_iters, 0, 8, st)); HIP_OK(hipMemsetAsync(B.stat_rowiters, 0, 8, st));
-      launch_ipm_batch(X, Bp, bc, st);
-      FixedBatchArgs F;
-      F.ovf_list = B.ovf_list; F.ovf_count = B.ovf_count; F.ovf2_list = B.ovf2_list; F.ovf2_count = B.ovf2_count;
-      F.batch_ok = B.batch_ok; F.batch_it = B.batch_it; F.batch_obj = B.batch_obj; F.batch_viol = B.batch_viol; F.batch_Z = B.batch_Z;
-      F.res = G.res + c0; F.Z = G.Z; F.best_obj = G.best_obj + j; F.best_idx = G.best_idx + j;
-      F.bc = bc; F.base = c0; F.row_doubles = (int)row; F.onchip = X.oc_grid > 0 ? 1 : 0; F.big = X.ocb_grid > 0 ? 1 : 0; F.cobj = call.cobj; F.soft = soft_cost_args(B, call.Y);
-      hipLaunchKernelGGL(fixed_batch_collect_kernel, dim3(1 + std::min(FB_ROW_BLOCKS, (bc + FB_NT / 64 - 1) / (FB_NT / 64))), dim3(FB_NT), 0, st, F);
+  HIP_OK(hipMemcpyAsync(M.cur, fix, (size_t)m * fl, hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(M.ent_inst, einst.data(), (size_t)m * 4, hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(M.ent_fam, efam.data(), (size_t)m * 4, hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemsetAsync(M.cnt, 0, (size_t)m * sizeof(int), st)); HIP_OK(hipMemsetAsync(M.act, 0, (size_t)m * sizeof(int), st)); HIP_OK(hipMemsetAsync(M.off, 0, (size_t)(m + 1) * sizeof(int), st));
+  const DevBuf Bp = fixed_chain_settings(B);
+  PoolImproveArgs A;
+  A.cur = M.cur; A.cur_obj = M.cur_obj; A.act = M.act; A.cnt = M.cnt; A.moves = M.moves; A.words = M.words; A.res = G.res; A.pool_fix = B.pool_fix;
+  A.ent_inst = M.ent_inst; A.ent_fam = M.ent_fam; A.off = M.off; A.batch_inst = B.batch_inst;
+  A.dims = dims; A.fixlen = (int)fl; A.m = m;
+  std::vector<PoolWord> words(m); std::vector<int> cnt(m), first(m + 2), offh(m + 1);
+  // one pass: counts[e] nodes of entry e (own: one each, the entry's own record), slice by slice; behind it the moves of the next pass and the read-back
+  auto run_pass = [&](const std::vector<int>& counts, int own) -> bool {
+    const int ns = miqp_gpu_pool_improve_plan(counts.data(), m, first.data(), m + 2);
+    if (ns < 1) return false;
+    offh[0] = 0;
+    for (int e = 0; e < m; ++e) offh[e + 1] = offh[e] + counts[e];
+    HIP_OK(hipEventRecord(X.ev0, st));
+    for (int s = 0; s < ns; ++s) {
+      const int e0 = first[s], e1 = first[s + 1], nodes = offh[e1] - offh[e0];
+      if (nodes > PoolImproveDev::NB_MAX) { std::fprintf(stderr, "[miqp_gpu] %s: a slice of %d nodes\n", name, nodes); return false; }
+      for (int k0 = 0; k0 < nodes; k0 += FB_CHUNK) {
+        const int bc = std::min(FB_CHUNK, nodes - k0);
+        hipLaunchKernelGGL(pool_neighbour_kernel, dim3((bc + 3) / 4), dim3(256), 0, st, A, offh[e0] + k0, bc, own);
+        HIP_OK(hipGetLastError());
+        // (no segments: the climb picks per entry; it has no use for the trajectories, one chunk's worth is written over)
+        if (!fixed_chunk(X, Bp, Y, call.dev(), n_inst, FixedChunk{bc, k0, G.res + k0, G.Z})) return false;
+      }
+      if (e1 > e0) hipLaunchKernelGGL(pool_pick_kernel, dim3(e1 - e0), dim3(64), 0, st, A, e0, (int)PoolImproveDev::NB_MAX, own);
       HIP_OK(hipGetLastError());
     }
-    return true;
-  };
-  // behind a pass: its pick, the moves of the next one, and the words of both to the host
-  std::vector<PoolWord> words(m); std::vector<int> cnt(m);
-  auto finish_pass = [&](int own) -> bool {
-    hipLaunchKernelGGL(pool_pick_kernel, dim3(m), dim3(64), 0, st, A, 0, (int)PoolImproveDev::NB_MAX, own);   // (at most MIQP_POOL_MAX entries: one slice)
     hipLaunchKernelGGL(pool_moves_kernel, dim3(m), dim3(64), gen_lds, st, A);
     hipLaunchKernelGGL(pool_offsets_kernel, dim3(1), dim3(256), 0, st, A);
     HIP_OK(hipGetLastError());
     HIP_OK(hipEventRecord(X.ev1, st));
-    HIP_OK(hipMemcpyAsync(words.data(), G.words, (size_t)m * sizeof(PoolWord), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(cnt.data(), G.cnt, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(words.data(), M.words, (size_t)m * sizeof(PoolWord), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(cnt.data(), M.cnt, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st)); HIP_OK(hipGetLastError());
     float ms = 0.0f; (void)hipEventElapsedTime(&ms, X.ev0, X.ev1); O.dev_ms += ms;
     return true;
   };
-  HIP_OK(hipEventRecord(X.ev0, st));
-  if (!solve_nodes(m, 1) || !finish_pass(1)) return false;
+  if (!run_pass(std::vector<int>(m, 1), 1)) return false;
   O.first = words; O.after.resize(m); O.moves.assign(m, 0);
   for (int k = 0; k < m; ++k) O.after[k] = words[k].objective;
-  for (;;) {
+  O.passes.assign(n_inst, 0); O.neighbours.assign(n_inst, 0); O.iterations.assign(n_inst, 0); O.still_moving.assign(n_inst, 0);
+  std::vector<long> th(n_inst);
+  for (int pass = 0;;) {
     long total = 0;
-    for (int k = 0; k < m; ++k) { if (cnt[k] < 0 || cnt[k] > POOL_MOVES_MAX) { std::fprintf(stderr, "[miqp_gpu] miqp_solver_pool_improve: move count %d of entry %d\n", cnt[k], k); return false; } total += cnt[k]; }
-    if (total == 0 || O.passes == max_passes) break;
-    HIP_OK(hipEventRecord(X.ev0, st));
-    if (!solve_nodes((int)total, 0) || !finish_pass(0)) return false;
-    O.passes++; O.neighbours += total;
+    std::fill(th.begin(), th.end(), 0L);
+    for (int k = 0; k < m; ++k) { if (cnt[k] < 0 || cnt[k] > POOL_MOVES_MAX) { std::fprintf(stderr, "[miqp_gpu] %s: move count %d of entry %d\n", name, cnt[k], k); return false; } total += cnt[k]; th[einst[k]] += cnt[k]; }
+    if (total == 0 || pass == max_passes) break;
+    const std::vector<int> counts = cnt;   // (run_pass reads the next pass's counts into cnt)
+    if (!run_pass(counts, 0)) return false;
+    pass++;
     bool any = false;
-    for (int k = 0; k < m; ++k) {
-      O.iterations += words[k].iterations;
-      if (words[k].accepted) { any = true; O.moves[k]++; O.after[k] = words[k].objective; }
+    // a handle without neighbours in this pass has stopped: its figures stay
+    for (int h = 0; h < n_inst; ++h) {
+      if (th[h] == 0) continue;
+      O.passes[h]++; O.neighbours[h] += th[h];
+      bool any_h = false;
+      for (int k = hfirst[h]; k < hfirst[h + 1]; ++k) {
+        O.iterations[h] += words[k].iterations;
+        if (words[k].accepted) { any_h = true; O.moves[k]++; O.after[k] = words[k].objective; }
+      }
+      O.still_moving[h] = any_h && pass == max_passes ? 1 : 0;
+      any = any || any_h;
     }
-    O.still_moving = any && O.passes == max_passes;
     if (!any) break;
   }
   O.fix.resize((size_t)m * fl);
-  HIP_OK(hipMemcpy(O.fix.data(), G.cur, (size_t)m * fl, hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(O.fix.data(), M.cur, (size_t)m * fl, hipMemcpyDeviceToHost));
   return true;
+}
+
+// What the handles receive of a climb: per handle with entries its out records (out + h * stride), the moved records and objectives of its pool, its
+// last_timing and, when it still moved in the last pass, its last error; counts[h] (may be NULL) the entries.  Returns the entries that moved
+int pool_improve_store(const FixedCall& call, const char* name, const std::vector<int>& hfirst, const PoolImproveOut& O, int max_passes, double t_call, miqp_pool_improve_c* out, int stride, int* counts) {
+  const size_t fl = (size_t)call.Y.fixlen;
+  const double call_s = wall_s() - t_call;
+  int moved = 0;
+  for (int h = 0; h < call.n; ++h) {
+    miqp_solver_t* s = call.S[h]; const int ent = hfirst[h + 1] - hfirst[h];
+    if (counts) counts[h] = ent;
+    if (ent == 0) continue;   // (left alone: its last error and last timing stay those of what it did last)
+    s->timing[0] = call_s; s->timing[1] = O.dev_ms * 1e-3; s->timing[2] = O.passes[h]; s->timing[3] = (double)O.neighbours[h]; s->timing[4] = (double)O.iterations[h]; s->timing[5] = O.still_moving[h] ? 1 : 0;
+    miqp_pool_improve_c* const o = out + (size_t)h * stride;
+    for (int k = 0; k < ent; ++k) {
+      const int e = hfirst[h] + k;
+      const bool live = O.first[e].accepted != 0;
+      o[k].before = O.first[e].objective; o[k].after = live ? O.after[e] : o[k].before; o[k].moves = live ? O.moves[e] : 0; o[k].status = live ? 0 : 1;
+      if (!live) continue;   // (an entry whose own QP is not feasible at the tight tolerance stays as it was found)
+      std::memcpy(s->pool_fix.data() + (size_t)k * fl, O.fix.data() + (size_t)e * fl, fl);
+      s->pool_obj[k] = o[k].after;
+      if (o[k].moves > 0) moved++;
+    }
+    s->pr_n = 0; std::vector<char>().swap(s->pr_ok); std::vector<signed char>().swap(s->pr_fix); std::vector<double>().swap(s->pr_Z);
+    if (O.still_moving[h]) {
+      char msg[200]; std::snprintf(msg, sizeof msg, "%s: an entry still moved in the last of %d passes; more passes may improve the pool further", name, max_passes);
+      s->err = msg;
+    }
+  }
+  return moved;
+}
+
+// the climb of the first ent[h] entries of every handle of an open call.  Entries that moved, or -3 (the handles with entries then carry the run's refusal, if it gave one)
+int pool_improve_call(const FixedCall& call, const char* name, const std::vector<int>& ent, int max_passes, double t_call, miqp_pool_improve_c* out, int stride, int* counts) {
+  const int n = call.n; const size_t fl = (size_t)call.Y.fixlen;
+  std::vector<int> hfirst(n + 1, 0);
+  for (int h = 0; h < n; ++h) hfirst[h + 1] = hfirst[h] + ent[h];
+  const int m = hfirst[n];
+  std::vector<signed char> fix((size_t)m * fl); std::vector<int> einst(m), efam(m);
+  for (int h = 0; h < n; ++h) {
+    if (ent[h] > 0) std::memcpy(fix.data() + (size_t)hfirst[h] * fl, call.S[h]->pool_fix.data(), (size_t)ent[h] * fl);
+    for (int k = hfirst[h]; k < hfirst[h + 1]; ++k) { einst[k] = h; efam[k] = call.S[h]->pool_fam; }
+  }
+  PoolImproveOut O;
+  if (!pool_improve_run(call, name, fix.data(), einst, efam, hfirst, m, max_passes, O)) {
+    (void)hipStreamSynchronize(call.X->stream);
+    if (!O.err.empty()) for (int h = 0; h < n; ++h) if (ent[h] > 0) call.S[h]->err = O.err;
+    return -3;
+  }
+  return pool_improve_store(call, name, hfirst, O, max_passes, t_call, out, stride, counts);
 }
 
 // a decision record against the instance's tables: every byte is -1 (undecided) or an alternative of its site
@@ -409,13 +512,13 @@ int miqp_solver_solve_decisions(miqp_solver_t* s, const signed char* decisions, 
   if (n > FB_CAP) return -5;
   const double t_call = wall_s();
   if (best) *best = -1;
-  for (int k = 0; k < n; ++k) { out[k].status = 2; out[k].route = -1; out[k].iterations = 0; out[k].reserved = 0; out[k].objective = std::nan(""); out[k].violation = std::nan(""); }
+  fixed_refuse(out, n);
   miqp_solver_t* one[1] = {s};
   BatchShape bs = batch_layout(one, 1);
   if (!bs.ok) return -2;
   const Layout& Y = bs.Y;
   const size_t fl = (size_t)Y.fixlen, D = (size_t)Y.f_c2n;
-  // the tables for the range check, before any device is asked for: a call whose records are all refused touches none.  FixedBatchCall::open
+  // the tables for the range check, before any device is asked for: a call whose records are all refused touches none.  FixedCall::open
   // compiles the instance again for the run - deliberately: its tables belong to the call object, and one compile is small beside the chain
   std::vector<double> Dt(Y.dstride); std::vector<int> T(Y.istride);
   compile_instance(s->inst, Y, Dt.data(), T.data());
@@ -423,26 +526,12 @@ int miqp_solver_solve_decisions(miqp_solver_t* s, const signed char* decisions, 
   for (int k = 0; k < n; ++k) if (decisions_in_range(s->inst, Y, T.data(), decisions + (size_t)k * D)) where.push_back(k);
   const int m = (int)where.size();
   if (m == 0) return 0;   // (nothing to run: no device is touched)
-  FixedBatchCall call;
-  if (call.open(s, Y) != 0) return -3;
+  FixedCall call;
+  if (call.open(one, 1, Y) != 0) return -3;
   std::vector<signed char> fix((size_t)m * fl, (signed char)-1);
   for (int c = 0; c < m; ++c) std::memcpy(fix.data() + (size_t)c * fl, decisions + (size_t)where[c] * D, D);
-  s->setup[0] = wall_s() - t_call;
-  std::vector<miqp_fixed_result_c> tmp; std::vector<double> Z, bo; std::vector<int> bi; float dev_ms = 0.0f;
-  if (call.run(fix, m, tmp, Z, bo, bi, dev_ms) != 0) return -3;
-  for (int c = 0; c < m; ++c) out[where[c]] = tmp[c];
-  {
-    double b = 0; int at = -1;
-    for (size_t j = 0; j < bo.size(); ++j) if (bi[j] >= 0 && bi[j] < m && (at < 0 || bo[j] < b)) { b = bo[j]; at = bi[j]; }
-    if (best) *best = at < 0 ? -1 : where[at];
-  }
-  s->fb_n = n; s->fb_slot.assign(n, -1);   // (miqp_solver_fixed_batch_record hands out the trajectories of this call too)
-  for (int c = 0; c < m; ++c) if (tmp[c].status == 0) s->fb_slot[where[c]] = c;
-  s->fb_Z.swap(Z); s->fb_fix.swap(fix);
-  const int nch = (m + FB_CHUNK - 1) / FB_CHUNK;
-  s->timing[0] = wall_s() - t_call; s->timing[1] = dev_ms * 1e-3; s->timing[2] = nch; s->timing[3] = m; s->timing[4] = 0; s->timing[5] = 0;
-  for (int c = 0; c < m; ++c) s->timing[4] += tmp[c].iterations;
-  return 0;
+  const int first[2] = {0, n};   // (miqp_solver_fixed_batch_record hands out the trajectories of this call too)
+  return fixed_answer(call, fix, std::vector<int>(m, 0), where, {0, m}, first, out, best, t_call);
 }
 
 int miqp_solver_pool_improve(miqp_solver_t* s, int max_passes, miqp_pool_improve_c* out, int cap) {
@@ -456,29 +545,44 @@ int miqp_solver_pool_improve(miqp_solver_t* s, int max_passes, miqp_pool_improve
   miqp_solver_t* one[1] = {s};
   BatchShape bs = batch_layout(one, 1);
   if (!bs.ok || bs.Y.fixlen != s->pool_fixlen || s->pool_fix.size() < (size_t)m * bs.Y.fixlen) return -1;
-  const Layout& Y = bs.Y; const size_t fl = (size_t)Y.fixlen;
   const double t_call = wall_s();
-  FixedBatchCall call;
-  if (call.open(s, Y) != 0) return -3;
-  PoolImproveDev& G = g_pool_improve_dev[call.X->device];
-  PoolImproveOut O;
-  if (!G.ensure(fl, (size_t)Y.N * Y.nz) || !pool_improve_run(*call.X, G, call, s->pool_fam, s->pool_fix.data(), m, max_passes, O)) { (void)hipStreamSynchronize(call.X->stream); if (!O.err.empty()) s->err = O.err; return -3; }
-  int moved = 0;
-  for (int k = 0; k < m; ++k) {
-    const bool live = O.first[k].accepted != 0;
-    out[k].before = O.first[k].objective; out[k].after = live ? O.after[k] : out[k].before; out[k].moves = live ? O.moves[k] : 0; out[k].status = live ? 0 : 1;
-    if (!live) continue;   // (an entry whose own QP is not feasible at the tight tolerance stays as it was found)
-    std::memcpy(s->pool_fix.data() + (size_t)k * fl, O.fix.data() + (size_t)k * fl, fl);
-    s->pool_obj[k] = out[k].after;
-    if (out[k].moves > 0) moved++;
+  FixedCall call;
+  if (call.open(one, 1, bs.Y) != 0) return -3;
+  return pool_improve_call(call, "miqp_solver_pool_improve", {m}, max_passes, t_call, out, 0, nullptr);
+}
+
+int miqp_gpu_pool_improve_plan(const int* move_counts, int entries, int* slice_first, int cap) {
+  if (!move_counts || !slice_first || entries <= 0 || cap < 0) return -1;
+  return pool_improve_slices(move_counts, entries, slice_first, cap);
+}
+
+int miqp_solver_pool_improve_multi(miqp_solver_t* const* solvers, int n, int max_passes, miqp_pool_improve_c* out, int cap, int* counts) {
+  if (!solvers || !out || !counts || n <= 0 || cap < 1) return -1;
+  if (max_passes < 1 || max_passes > POOL_IMPROVE_PASSES_MAX) return -2;
+  BatchShape bs;
+  if (const int rc = fixed_multi_check(solvers, n, bs)) return rc;
+  const Layout& Y = bs.Y; const size_t fl = (size_t)Y.fixlen;
+  std::vector<int> ent(n); int m = 0;   // the entries of every handle
+  for (int h = 0; h < n; ++h) {
+    const miqp_solver_t* s = solvers[h];
+    ent[h] = std::min(miqp_solver_pool_count(s), cap);
+    if (ent[h] > 0 && (s->pool_fixlen != Y.fixlen || s->pool_fix.size() < (size_t)ent[h] * fl || s->pool_obj.size() < (size_t)ent[h])) return -1;
+    m += ent[h];
   }
-  s->pr_n = 0; std::vector<char>().swap(s->pr_ok); std::vector<signed char>().swap(s->pr_fix); std::vector<double>().swap(s->pr_Z);
-  s->timing[0] = wall_s() - t_call; s->timing[1] = O.dev_ms * 1e-3; s->timing[2] = O.passes; s->timing[3] = (double)O.neighbours; s->timing[4] = (double)O.iterations; s->timing[5] = O.still_moving ? 1 : 0;
-  if (O.still_moving) {
-    char msg[200]; std::snprintf(msg, sizeof msg, "miqp_solver_pool_improve: an entry still moved in the last of %d passes; more passes may improve the pool further", max_passes);
-    s->err = msg;
-  }
-  return moved;
+  for (int h = 0; h < n; ++h)   // (a handle that kept nothing is left alone whatever its filter)
+    if (ent[h] > 0 && (solvers[h]->pool_fam < 1 || solvers[h]->pool_fam >= POOL_FAM_TIMING)) {
+      char msg[200]; std::snprintf(msg, sizeof msg, "miqp_solver_pool_improve_multi: handle %d of the call kept entries under filter %d; the climb needs a filter in 1 .. 15", h, solvers[h]->pool_fam);
+      solvers[h]->err = msg;
+      return -2;
+    }
+  if (m > FB_CAP) return -5;
+  if (m == 0) { for (int h = 0; h < n; ++h) counts[h] = 0; return 0; }   // (nothing to run: no device is touched)
+  for (int h = 0; h < n; ++h) if (ent[h] > 0) solvers[h]->err.clear();   // (miqp_solver_last_error of a handle with entries speaks of this call from here on)
+  { int ndev = 0; if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return -3; }
+  const double t_call = wall_s();
+  FixedCall call;
+  if (call.open(solvers, n, Y) != 0) return -3;
+  return pool_improve_call(call, "miqp_solver_pool_improve_multi", ent, max_passes, t_call, out, cap, counts);
 }
 
 }  // extern "C"

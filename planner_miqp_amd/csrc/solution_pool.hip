@@ -1,4 +1,5 @@
-// solution_pool.hip - the K best distinct integer solutions of a solve (miqp_solver_set_pool, _pool_count, _pool_found, _pool_solve, _pool_record).
+// solution_pool.hip - the K best distinct integer solutions of a solve (miqp_solver_set_pool, _pool_count, _pool_found, _pool_solve, _pool_solve_multi,
+// _pool_record).
 //
 // Counterpart of the CPLEX solution pool (IloCplex::getSolnPoolNsolns, getObjValue(i), getValues(x, i)), which a user of the reference reaches through the
 // IloCplex its wrapper owns; the reference source itself has no call site for it.  A solve returns its incumbent; every other integer-feasible leaf the
@@ -26,7 +27,7 @@
 // of two cars x 8 steps, capacity 8: 0.2 GB); with a filter in the call n_inst x stride x fixlen + 4 n_inst more (the signatures, the family sets).
 // A rank of a tree split keeps the pool of its own search; pools are not exchanged.
 //
-// Refinement: pool entries were found at node tolerance; miqp_solver_pool_solve sends them through the fixed-batch chain (fixed_batch.hip) at the tight
+// Refinement: pool entries were found at node tolerance; miqp_solver_pool_solve sends them through the fixed chain (fixed_chain.hip) at the tight
 // tolerance.  What the caller gets per entry is what miqp_solver_solve_fixed answers for the entry's RawResults record: the call re-labels each record
 // with the canonical binaries of its own solution (fill_results / fix_from_results: the first alternative that holds) and solves again until the labels stay.
 // Entries that end with the same labels are one solution under several names - the optimum of one record also holds the alternatives of the other, so
@@ -395,6 +396,89 @@ bool pool_read_back(const DevCtx& X, miqp_solver_t* const* S, int n, const Resul
   return true;
 }
 
+// The refinement of the first ent[h] pool entries of every handle of an open call (`name`: the entry point, for its messages).  Passes: the entries
+// of the handles whose labels moved in the pass before (the first pass: all) run through the chain and are re-labelled with the canonical binaries
+// of their own solutions, at most POOL_PASSES times.  Then, per handle, entries whose records carry the same binaries are ONE solution (the optimum
+// of one holds the alternatives of the other too, so both QPs have the same strictly convex minimiser), and under the handle's filter so are
+// entries whose final labels have one signature (pool_same_entry): the first in pool order stays, the handle's pool shrinks with it.  The handle
+// keeps what miqp_solver_pool_record hands out and its last_timing; kept[h] receives its answers.  false: HIP error
+bool pool_refine(FixedCall& call, const int* ent, const char* name, double t_call, std::vector<std::vector<miqp_fixed_result_c>>& kept_out) {
+  const int n = call.n; miqp_solver_t* const* solvers = call.S;
+  const Layout& Y = call.Y; const size_t fl = (size_t)Y.fixlen, row = (size_t)Y.N * Y.nz;
+  // per handle: the labels its entries are solved with, those of their own solutions (the ones a caller of miqp_solver_solve_fixed would send for
+  // its record), the last answers
+  struct PerHandle { std::vector<signed char> fix, canon; std::vector<miqp_fixed_result_c> tmp; std::vector<double> Z; int passes = 0; bool moving = true; };
+  std::vector<PerHandle> H(n);
+  for (int h = 0; h < n; ++h) { H[h].moving = ent[h] > 0; H[h].fix.assign(solvers[h]->pool_fix.begin(), solvers[h]->pool_fix.begin() + (size_t)ent[h] * fl); H[h].canon.resize((size_t)ent[h] * fl); }
+  float dev_ms = 0.0f;
+  for (int pass = 0; pass < POOL_PASSES; ++pass) {
+    std::vector<int> live, inst, lfirst;
+    std::vector<signed char> fix;
+    for (int h = 0; h < n; ++h) if (H[h].moving) { live.push_back(h); lfirst.push_back((int)inst.size()); inst.insert(inst.end(), ent[h], h); fix.insert(fix.end(), H[h].fix.begin(), H[h].fix.end()); }
+    if (live.empty()) break;
+    const int m = (int)inst.size();
+    std::vector<miqp_fixed_result_c> tmp; std::vector<double> Z; std::vector<int> hbest; float ms = 0.0f; int g = 0;
+    if (call.run(fix, inst, m, tmp, Z, hbest, ms, g) != 0) return false;
+    dev_ms += ms;
+    fixed_threads((int)live.size(), 4, [&](int q) {
+      const int h = live[q], c0 = lfirst[q]; miqp_solver_t* s = solvers[h]; PerHandle& P = H[h];
+      P.tmp.assign(tmp.begin() + c0, tmp.begin() + c0 + ent[h]); P.Z.assign(Z.begin() + (size_t)c0 * row, Z.begin() + (size_t)(c0 + ent[h]) * row);
+      P.passes++;
+      OwnedResults R(s->inst); std::vector<signed char> one, full;
+      for (int k = 0; k < ent[h]; ++k) {
+        std::memcpy(P.canon.data() + (size_t)k * fl, P.fix.data() + (size_t)k * fl, fl);
+        if (P.tmp[k].status != 0) continue;
+        full.assign(P.fix.begin() + (size_t)k * fl, P.fix.begin() + (size_t)(k + 1) * fl);
+        for (auto& b : full) if (b < 0) b = 0;
+        fill_results(s->inst, Y, call.tabD(h), call.tabT(h), full.data(), P.Z.data() + (size_t)k * row, &R.r);
+        (void)fix_from_results(s->inst, Y, call.tabT(h), &R.r, one);
+        std::memcpy(P.canon.data() + (size_t)k * fl, one.data(), fl);
+      }
+      // when the labels are the ones just solved with, that call answers with these bits; at the last pass the answers stay those of the labels they were solved with
+      P.moving = P.canon != P.fix;
+      if (P.moving && P.passes < POOL_PASSES) P.fix = P.canon;
+    });
+  }
+  const double call_s = wall_s() - t_call;
+  kept_out.assign(n, {});
+  for (int h = 0; h < n; ++h) {
+    miqp_solver_t* s = solvers[h]; PerHandle& P = H[h]; const int m = ent[h];
+    s->timing[0] = call_s; s->timing[1] = dev_ms * 1e-3; s->timing[2] = P.passes; s->timing[3] = 0; s->timing[4] = 0; s->timing[5] = 0;
+    if (m == 0) continue;
+    if (P.moving) {   // not seen on any instance so far; the entries are then answers to the labels of the last pass, not yet to those of their own records
+      char msg[220]; std::snprintf(msg, sizeof msg, "%s: the labels of the pool entries still moved after %d passes; an entry may differ from what miqp_solver_solve_fixed answers for its record", name, P.passes);
+      s->err = msg; std::fprintf(stderr, "[miqp_gpu] %s\n", msg);
+    }
+    std::vector<miqp_fixed_result_c>& tmp = P.tmp; std::vector<signed char>& fix = P.fix; std::vector<signed char>& canon = P.canon; std::vector<double>& Z = P.Z;
+    int kept = 0;
+    for (int k = 0; k < m; ++k) {
+      bool dup = false;
+      for (int j = 0; j < kept && !dup; ++j) dup = tmp[k].status == 0 && tmp[j].status == 0 && pool_same_entry(Y, s->pool_fam, canon.data() + (size_t)k * fl, canon.data() + (size_t)j * fl);
+      if (dup) continue;
+      if (kept != k) {
+        tmp[kept] = tmp[k]; s->pool_obj[kept] = s->pool_obj[k];
+        std::memmove(fix.data() + (size_t)kept * fl, fix.data() + (size_t)k * fl, fl); std::memmove(canon.data() + (size_t)kept * fl, canon.data() + (size_t)k * fl, fl);
+        std::memmove(s->pool_fix.data() + (size_t)kept * fl, s->pool_fix.data() + (size_t)k * fl, fl);
+        std::memmove(Z.data() + (size_t)kept * row, Z.data() + (size_t)k * row, row * sizeof(double));
+      }
+      kept++;
+    }
+    if (kept < m) {   // (entries behind `cap`, not refined by this call, move up unchanged)
+      s->pool_obj.erase(s->pool_obj.begin() + kept, s->pool_obj.begin() + m);
+      s->pool_fix.erase(s->pool_fix.begin() + (size_t)kept * fl, s->pool_fix.begin() + (size_t)m * fl);
+      s->pool_n -= m - kept;
+    }
+    fix.resize((size_t)kept * fl); Z.resize((size_t)kept * row); tmp.resize(kept);
+    s->pr_n = kept; s->pr_ok.assign(kept, 0);
+    for (int k = 0; k < kept; ++k) s->pr_ok[k] = tmp[k].status == 0 ? 1 : 0;
+    s->pr_Z.swap(Z); s->pr_fix.swap(fix);
+    s->timing[3] = kept; s->timing[5] = P.moving ? 1 : 0;
+    for (int k = 0; k < kept; ++k) s->timing[4] += tmp[k].iterations;
+    kept_out[h].swap(tmp);
+  }
+  return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -471,81 +555,43 @@ int miqp_solver_pool_solve(miqp_solver_t* s, miqp_fixed_result_c* out, int cap) 
   miqp_solver_t* one[1] = {s};
   BatchShape bs = batch_layout(one, 1);
   if (!bs.ok || bs.Y.fixlen != s->pool_fixlen) return -1;
-  const Layout& Y = bs.Y; const size_t fl = (size_t)Y.fixlen, row = (size_t)Y.N * Y.nz;
   const double t_call = wall_s();
-  FixedBatchCall call;
-  if (call.open(s, Y) != 0) return -3;
-  std::vector<signed char> fix(s->pool_fix.begin(), s->pool_fix.begin() + (size_t)m * fl);
-  std::vector<miqp_fixed_result_c> tmp; std::vector<double> Z, bo; std::vector<int> bi; float dev_ms = 0.0f, ms = 0.0f;
-  int passes = 0; bool moving = false;
-  std::vector<signed char> canon((size_t)m * fl);   // per entry: the labels of its own solution (those a caller of miqp_solver_solve_fixed would send for its record)
-  for (;;) {
-    if (call.run(fix, m, tmp, Z, bo, bi, ms) != 0) return -3;
-    dev_ms += ms; passes++;
-    OwnedResults R(s->inst); std::vector<signed char> one, full;
-    for (int k = 0; k < m; ++k) {
-      std::memcpy(canon.data() + (size_t)k * fl, fix.data() + (size_t)k * fl, fl);
-      if (tmp[k].status != 0) continue;
-      full.assign(fix.begin() + (size_t)k * fl, fix.begin() + (size_t)(k + 1) * fl);
-      for (auto& b : full) if (b < 0) b = 0;
-      fill_results(s->inst, Y, call.D.data(), call.T.data(), full.data(), Z.data() + (size_t)k * row, &R.r);
-      (void)fix_from_results(s->inst, Y, call.T.data(), &R.r, one);
-      std::memcpy(canon.data() + (size_t)k * fl, one.data(), fl);
-    }
-    // when the labels are the ones just solved with, that call answers with these bits; at the last pass the answers stay those of the labels they were solved with
-    moving = canon != fix;
-    if (passes == POOL_PASSES || !moving) break;
-    fix = canon;
+  FixedCall call;
+  if (call.open(one, 1, bs.Y) != 0) return -3;
+  std::vector<std::vector<miqp_fixed_result_c>> kept;
+  if (!pool_refine(call, &m, "miqp_solver_pool_solve", t_call, kept)) return -3;
+  std::copy(kept[0].begin(), kept[0].end(), out);
+  return (int)kept[0].size();
+}
+
+int miqp_solver_pool_solve_multi(miqp_solver_t* const* solvers, int n, miqp_fixed_result_c* out, int cap, int* counts) {
+  if (!solvers || !out || !counts || n <= 0 || cap < 1) return -1;
+  BatchShape bs;
+  if (const int rc = fixed_multi_check(solvers, n, bs)) return rc;
+  std::vector<int> ent(n); int total = 0;
+  for (int h = 0; h < n; ++h) {
+    ent[h] = std::min(miqp_solver_pool_count(solvers[h]), cap);
+    if (ent[h] > 0 && solvers[h]->pool_fixlen != bs.Y.fixlen) return -1;
+    total += ent[h];
   }
-  if (moving) {   // not seen on any instance so far; the entries are then answers to the labels of the last pass, not yet to those of their own records
-    char msg[200]; std::snprintf(msg, sizeof msg, "miqp_solver_pool_solve: the labels of the pool entries still moved after %d passes; an entry may differ from what miqp_solver_solve_fixed answers for its record", passes);
-    s->err = msg; std::fprintf(stderr, "[miqp_gpu] %s\n", msg);
-  }
-  // entries whose records carry the same binaries are ONE solution (the optimum of one holds the alternatives of the other too, so both QPs have the
-  // same strictly convex minimiser), and under the handle's filter so are entries whose final labels have one signature (pool_same_entry): the first
-  // in pool order stays, the handle's pool shrinks with it
-  int kept = 0;
-  for (int k = 0; k < m; ++k) {
-    bool dup = false;
-    for (int j = 0; j < kept && !dup; ++j) dup = tmp[k].status == 0 && tmp[j].status == 0 && pool_same_entry(Y, s->pool_fam, canon.data() + (size_t)k * fl, canon.data() + (size_t)j * fl);
-    if (dup) continue;
-    if (kept != k) {
-      tmp[kept] = tmp[k]; s->pool_obj[kept] = s->pool_obj[k];
-      std::memmove(fix.data() + (size_t)kept * fl, fix.data() + (size_t)k * fl, fl); std::memmove(canon.data() + (size_t)kept * fl, canon.data() + (size_t)k * fl, fl);
-      std::memmove(s->pool_fix.data() + (size_t)kept * fl, s->pool_fix.data() + (size_t)k * fl, fl);
-      std::memmove(Z.data() + (size_t)kept * row, Z.data() + (size_t)k * row, row * sizeof(double));
-    }
-    kept++;
-  }
-  if (kept < m) {   // (entries behind `cap`, not refined by this call, move up unchanged)
-    s->pool_obj.erase(s->pool_obj.begin() + kept, s->pool_obj.begin() + m);
-    s->pool_fix.erase(s->pool_fix.begin() + (size_t)kept * fl, s->pool_fix.begin() + (size_t)m * fl);
-    s->pool_n -= m - kept;
-    fix.resize((size_t)kept * fl); Z.resize((size_t)kept * row);
-  }
-  for (int k = 0; k < kept; ++k) out[k] = tmp[k];
-  s->pr_n = kept; s->pr_ok.assign(kept, 0);
-  for (int k = 0; k < kept; ++k) s->pr_ok[k] = tmp[k].status == 0 ? 1 : 0;
-  s->pr_Z.swap(Z); s->pr_fix.swap(fix);
-  s->timing[0] = wall_s() - t_call; s->timing[1] = dev_ms * 1e-3; s->timing[2] = passes; s->timing[3] = kept; s->timing[4] = 0; s->timing[5] = moving ? 1 : 0;
-  for (int k = 0; k < kept; ++k) s->timing[4] += tmp[k].iterations;
-  return kept;
+  if (total > FB_CAP) return -5;
+  for (int h = 0; h < n; ++h) { solvers[h]->pr_n = 0; counts[h] = 0; }
+  if (total == 0) return 0;   // (nothing to run: no device is touched)
+  const double t_call = wall_s();
+  FixedCall call;
+  if (call.open(solvers, n, bs.Y) != 0) return -3;
+  std::vector<std::vector<miqp_fixed_result_c>> kept;
+  if (!pool_refine(call, ent.data(), "miqp_solver_pool_solve_multi", t_call, kept)) return -3;
+  int left = 0;
+  for (int h = 0; h < n; ++h) { std::copy(kept[h].begin(), kept[h].end(), out + (size_t)h * cap); counts[h] = (int)kept[h].size(); left += counts[h]; }
+  return left;
 }
 
 int miqp_solver_pool_record(miqp_solver_t* s, int k, miqp_raw_results_c* out) {
   if (!s || !out || !s->has_inst || s->pr_n <= 0 || k < 0 || k >= s->pr_n) return -1;
   if (!s->pr_ok[k]) return 1;
   if (!dims_match(*out, s->inst)) return -2;
-  miqp_solver_t* one[1] = {s};
-  BatchShape bs = batch_layout(one, 1);
-  if (!bs.ok) return -1;
-  const Layout& Y = bs.Y;
-  std::vector<double> D(Y.dstride); std::vector<int> T(Y.istride);
-  compile_instance(s->inst, Y, D.data(), T.data());
-  std::vector<signed char> fix(s->pr_fix.begin() + (size_t)k * Y.fixlen, s->pr_fix.begin() + (size_t)(k + 1) * Y.fixlen);
-  for (auto& b : fix) if (b < 0) b = 0;
-  fill_results(s->inst, Y, D.data(), T.data(), fix.data(), s->pr_Z.data() + (size_t)k * Y.N * Y.nz, out);
-  return 0;
+  return fixed_hand_out(s, s->pr_fix, s->pr_Z, k, out);
 }
 
 }  // extern "C"

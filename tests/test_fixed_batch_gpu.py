@@ -159,6 +159,36 @@ def test_chunk_boundary(oracle):
     assert rc == 0 and _bytes(out, obj) == _bytes(b["records"][0], b["objective"][0])
 
 
+def test_best_is_the_first_minimum_within_a_lane_across_lanes_and_across_chunks(oracle):
+    """The minimum of a handle is reduced by ONE wavefront per segment of a chunk (fixed_collect_kernel of csrc/fixed_chain.hip): lane k mod 64 walks
+    nodes k, k + 64, ..., an xor tree joins the lanes, the host folds the chunks.  Two feasible records of `mini` - A, the complete level, and B, regions
+    only, which the oracle answers with a lower objective - with B at 70, 71 and 134 of 140 entries: 70 and 134 meet in one lane, 70 and 71 in
+    neighbouring ones, and best is 70.  The same list as handle 1 of a two-handle call, behind a handle of 3 records, gives the same best; and with B
+    only at 1025 of 1030 entries the minimum lies in the second launch group."""
+    (a, rca, _, obja), (b, rcb, _, objb) = _case(oracle, "mini", "complete"), _case(oracle, "mini", "regions_only")
+    assert rca == rcb == 0 and obja > objb + 1.0, (rca, rcb, obja, objb)
+    p = H.node_instance(oracle, "mini")[0]
+    batch = [a] * 140
+    for k in (70, 71, 134):
+        batch[k] = b
+    r = _run(_wrapper(oracle, "mini"), batch)
+    print("FIXEDBATCH best-in-lanes objectives A %r B %r best %d" % (float(r["objective"][0]), float(r["objective"][70]), r["best"]))
+    assert all(s == 0 for s in r["status"]) and r["objective"][70] < r["objective"][0]
+    assert r["best"] == 70
+    assert _entry_bytes(r, 70) == _entry_bytes(r, 71) == _entry_bytes(r, 134)
+    ws = []
+    for _ in range(2):
+        w = P.CplexWrapper(); w.resetParameters(p); ws.append(w)
+    multi = P.solve_fixed_multi(ws, [[a, a, a], batch])
+    assert multi[0][5] == 0 and multi[1][5] == 70, (multi[0][5], multi[1][5])
+    assert multi[1][1].tobytes() == r["objective"].tobytes()
+    chunk = P.fixed_batch_chunk()
+    assert chunk == 1024
+    big = [a] * 1030; big[1025] = b
+    st, obj, viol, it, route, best = _wrapper(oracle, "mini").solveFixedBatch(big)
+    assert all(s == 0 for s in st) and best == 1025, best
+
+
 def test_the_same_batch_twice_gives_the_same_bytes(oracle):
     """... in all five arrays, in best and in the records, with a solveFixed call in between"""
     levels, records, first = _all_levels(oracle, "c2n20a")

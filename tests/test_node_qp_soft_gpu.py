@@ -15,7 +15,7 @@ c2n6e2pent, c2n20b and c2n20a mask 1000 the soft obstacle's rows are slack and t
 What these tests found: every kernel skips the rows of a byte L (all four launches, with the states within 1e-5 of the oracle's on the levels whose
 rows bind), and NO fixed-record entry charged the price - miqp_solver_solve_fixed added the constant of step 0 alone, and so did the collect kernels of
 solveFixedBatch and solve_fixed_multi, which the pool calls share: objectives short by 0.37 per ignored point.  Fixed in miqp_solver_solve_fixed and in
-soft_cost of csrc/fixed_batch.hip.  Routes found on the device: 0 on c1n2r32o and c1n6r16hex, 1 on c2n6e2pent, 2 on c2n20a and c2n20b, 3 on c1n21o and
+soft_cost of csrc/fixed_chain.hip.  Routes found on the device: 0 on c1n2r32o and c1n6r16hex, 1 on c2n6e2pent, 2 on c2n20a and c2n20b, 3 on c1n21o and
 c3n6o, on every level of each.
 
 The raw big-M model is asked in full (violation < 1e-5, raw objective within 1e-6 of the returned one) on the five levels that decide every
