@@ -218,6 +218,33 @@ int miqp_gpu_fixed_result_size(void);
 /* nodes per launch group of miqp_solver_solve_fixed_batch: a constant of the build (no reference counterpart; no device is needed or touched) */
 int miqp_gpu_fixed_batch_chunk(void);
 
+/* DIAGNOSTIC: n fix records of the instance loaded in s (at most miqp_gpu_fixed_batch_chunk) as nodes of the dual ACTIVE-SET launches, one
+ * launch per generation and cutoff value, each node read back as the kernel left it.  No reference counterpart (the reference's node re-solves
+ * are CPLEX's, src/cplex_wrapper.cpp:158-185); no solve runs this path - it exists so that the tests can hold the kernel against the oracle
+ * node by node (tests/test_as_node_gpu.py).
+ * start (NULL: every node cold): start[k] = -1 cold; p with 0 <= p < k: node k starts from node p's final active set and the M that belongs to
+ * it, as a child starts from its parent in a search; -(p + 2): the same active set with the tag of M cleared, so that the kernel rebuilds M
+ * column by column and inverts it.  Nodes run in generations: the cold ones, then their children, and so on.
+ * block: 0 the standard block of the launches, 1 the larger one; kernel, LDS size and grid are the round planner's.
+ * cutoff (NULL: none): per node, in the units of the returned objective; a NaN or a value of 1e299 and above is none.
+ * out[n]: one miqp_as_node_c each.  info32 (may be NULL): the 32 counters of the launches' statistics summed over the call - [0] nodes
+ * finished, [1] their steps, [2] nodes not finished, [3] rows dropped, [4] infeasible, [5] cut off, [6] active rows at the end, [7] rows taken
+ * over from the parents, [8] nodes started from the parent's M, [9] starts that fell back to a cold one, [11] .. [15] why a node was not
+ * finished (no free slot, step cap, curvature, pivot of a down-date, rows off their equalities), [16] .. [19] why M was rebuilt (no ring,
+ * the parent left none, the ring has come round, another row count).
+ * Returns 0, -1 invalid arguments / no instance / block not 0 or 1, -2 shape refused (as the solve refuses it), -3 no device / kernel image /
+ * HIP error, -4 a record is refused (as miqp_solver_solve_fixed refuses it), -5 n above the chunk, -6 the shape has no active-set launches
+ * (miqp_gpu_has_active_set), -7 the launches are switched off (MIQP_AS=0), -8 start[k] names node k or a later one, -9 the device context has
+ * no launch of that block or keeps no active sets.  miqp_solver_last_error has the text.  Everything but -3 and -9 is decided without a device.
+ * The handle keeps trajectories and fix records for miqp_solver_fixed_as_record, in place of those of a miqp_solver_solve_fixed_batch call. */
+int miqp_solver_solve_fixed_as(miqp_solver_t* s, const miqp_raw_results_c* const* fixed, int n, const int* start, int block, const double* cutoff,
+                               miqp_as_node_c* out, unsigned long long* info32);
+/* the RawResults record of node k of the handle's last miqp_solver_solve_fixed_as call, as miqp_solver_fixed_batch_record builds its own:
+ * 0, 1 when node k was not solved (any status but 0), -1 bad k / nothing held, -2 sizes of out differ from the instance. */
+int miqp_solver_fixed_as_record(miqp_solver_t* s, int k, miqp_raw_results_c* out);
+/* sizeof(miqp_as_node_c) of the built library (binding check) */
+int miqp_gpu_as_node_size(void);
+
 /* ---- solution pool: the K best distinct integer solutions of a solve.  Counterpart of the CPLEX solution pool - IloCplex::getSolnPoolNsolns,
  * getObjValue(i), getValues(x, i) - which a user of the reference reaches through the IloCplex its wrapper owns; the reference source has no call
  * site for it. ----

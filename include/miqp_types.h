@@ -174,6 +174,20 @@ typedef struct miqp_fixed_result_c {
   double violation; /* worst elastic violation of the node's rows at its solution (feasible: <= 1e-6); NaN for status 2 */
 } miqp_fixed_result_c;
 
+/* Outcome of one node of miqp_solver_solve_fixed_as: what ONE launch of the dual active-set kernel decided on one fix record (a diagnostic). */
+typedef struct miqp_as_node_c {
+  int status;       /* 0 solved, 1 infeasible, 2 cut off (the dual value passed the cutoff), 3 returned unsolved because the block does not hold
+                       the node's rows, 4 returned unsolved because the method could not finish (64 active rows, step cap, loss of precision);
+                       -1 not run (the call failed before or in its launches) */
+  int steps;        /* rows added + rows dropped (0 for status 3, 4) */
+  int active;       /* rows of the final active set, as handed to the children (0 unless status 0) */
+  int reserved;     /* 0 */
+  double objective; /* status 0: primal value of the iterate; 1, 2: the dual value reached.  With the constant cost of step 0 and the price of
+                       the ignored soft-obstacle points, as miqp_solver_solve_fixed reports them; NaN for status 3, 4, -1 */
+  double bound;     /* objective minus the allowance the kernel states for it: a lower bound of the node's QP (weak duality); NaN as above */
+  double violation; /* worst row at the iterate (status 0: at most 5e-7, the kernel's own acceptance; status 1: 1); NaN as above */
+} miqp_as_node_c;
+
 /* Outcome of one entry of miqp_solver_pool_improve: the entry's own QP at the tight tolerance before the climb and its objective behind it. */
 typedef struct miqp_pool_improve_c {
   double before;    /* objective of the entry's record as found, solved at the tight tolerance (with the constant cost of step 0) */

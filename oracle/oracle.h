@@ -80,6 +80,11 @@ int orc_solve_fixed(const oinst* I, const miqp_raw_results_c* fixed, miqp_raw_re
  * answer moves with the tolerance tells a degenerate QP from a wrong one */
 int orc_solve_fixed_tol(const oinst* I, const miqp_raw_results_c* fixed, miqp_raw_results_c* res, double* objective,
                         int* iters, double qp_tol);
+/* the same solve, asked for the number of rows whose multiplier exceeds 1e-6 at its solution: the size of the active set a
+ * method that keeps one has to hold (tests/test_as_node_records_cpu.py).  The interior point stops at a complementarity mu > 0
+ * and an inactive row of slack s still carries mu / s there, so a row counts only where its multiplier also exceeds its slack.
+ * Returns what orc_solve_fixed_tol returns. */
+int orc_solve_fixed_active(const oinst* I, const miqp_raw_results_c* fixed, double qp_tol, int* n_active);
 
 /* result buffers */
 miqp_raw_results_c* orc_results_alloc(int C, int N, int R, int E, int O, int L);

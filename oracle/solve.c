@@ -1050,7 +1050,20 @@ int orc_solve_fixed(const oinst* I, const miqp_raw_results_c* f, miqp_raw_result
   return orc_solve_fixed_tol(I, f, res, objective, iters, QP_TOL_FINAL);
 }
 
+static int solve_fixed_impl(const oinst* I, const miqp_raw_results_c* f, miqp_raw_results_c* res, double* objective, int* iters, double qp_tol, int* n_active);
+
 int orc_solve_fixed_tol(const oinst* I, const miqp_raw_results_c* f, miqp_raw_results_c* res, double* objective, int* iters, double qp_tol) {
+  return solve_fixed_impl(I, f, res, objective, iters, qp_tol, NULL);
+}
+
+/* rows whose multiplier exceeds 1e-6 - and its own slack - at the solution (-1 when the record is refused; on an infeasible record the count of the last iterate) */
+int orc_solve_fixed_active(const oinst* I, const miqp_raw_results_c* f, double qp_tol, int* n_active) {
+  int n = -1; int rc = solve_fixed_impl(I, f, NULL, NULL, NULL, qp_tol, &n);
+  if (n_active) *n_active = n;
+  return rc;
+}
+
+static int solve_fixed_impl(const oinst* I, const miqp_raw_results_c* f, miqp_raw_results_c* res, double* objective, int* iters, double qp_tol, int* n_active) {
   dmodel* M = dm_new(I); int C = I->C, N = I->N, R = I->R, E = I->E, O = I->O, L = I->L, K = I->K;
   rowvec rows = {0, 0, 0};
   signed char* comp = (signed char*)malloc(M->fixlen); memset(comp, -1, M->fixlen);
@@ -1108,6 +1121,17 @@ int orc_solve_fixed_tol(const oinst* I, const miqp_raw_results_c* f, miqp_raw_re
   double cobj0 = 0; (void)step0_check(M, &cobj0); /* the constant cost of step 0 (car/car slack of the initial state), as orc_solve and the device report it */
   if (objective) *objective = q.obj + const_cost(M, comp) + cobj0;
   if (iters) *iters = q.it;
+  if (n_active) {
+    /* The interior point ends at a complementarity mu > 0 (about 1e-11 at QP_TOL_FINAL, 1e-9 at a tolerance 100 times looser), where an INACTIVE row
+     * of slack s carries lambda = mu / s: a row a millimetre off its bound would pass 1e-6 at the looser tolerance and not at the final one.  Such a
+     * row is not active at the solution (mu -> 0 takes its multiplier to 0), so a row counts only where its multiplier also dominates its slack. */
+    int na = 0;
+    for (int k = 0; k < rows.n; ++k) {
+      double sl = -row_val(M, &rows.r[k], q.Z) + (rows.r[k].a > 0.0 ? q.lam[k] / rows.r[k].a : 0.0);
+      na += (q.lam[k] > 1e-6 && q.lam[k] > sl) ? 1 : 0;
+    }
+    *n_active = na;
+  }
   int rc = (q.ok && q.viol <= FEAS_TOL) ? 0 : 1;
   if (res && rc == 0) {
     /* fill_results needs a complete record: take unset leaf choices from completion */

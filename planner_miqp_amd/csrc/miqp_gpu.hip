@@ -18,6 +18,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <tuple>
 #include <vector>
 
 #include "../../include/miqp_gpu.h"
@@ -1690,6 +1691,7 @@ bool solve_batch_impl(miqp_solver_t* const* S, int n, int* statuses, const Split
 #include "certify.hip"
 #include "fixed_chain.hip"
 #include "fixed_batch.hip"
+#include "as_fixed.hip"
 #include "solution_pool.hip"
 #include "pool_improve.hip"
 #include "pool_explore.hip"

@@ -99,6 +99,12 @@ class FixedResultC(C.Structure):
                 ("objective", C.c_double), ("violation", C.c_double)]
 
 
+class AsNodeC(C.Structure):
+    """miqp_as_node_c (include/miqp_types.h): one node of CplexWrapper.solveFixedActiveSet"""
+    _fields_ = [("status", C.c_int), ("steps", C.c_int), ("active", C.c_int), ("reserved", C.c_int),
+                ("objective", C.c_double), ("bound", C.c_double), ("violation", C.c_double)]
+
+
 class PoolImproveC(C.Structure):
     """miqp_pool_improve_c (include/miqp_types.h): one entry of CplexWrapper.improveSolutionPool"""
     _fields_ = [("before", C.c_double), ("after", C.c_double), ("moves", C.c_int), ("status", C.c_int)]

@@ -12,7 +12,7 @@ import numpy as np
 # (four concurrent launches per round + the null stream: see miqp_gpu.hip - effective when set before the process's first HIP call)
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
-from .ctypes_types import (Certificate, CertificateC, FixedResultC, ModelParameters, ModelParamsC, PoolExploreC, PoolImproveC, RawResults, RawResultsC, SolutionPropertiesC, SolverOptsC,
+from .ctypes_types import (AsNodeC, Certificate, CertificateC, FixedResultC, ModelParameters, ModelParamsC, PoolExploreC, PoolImproveC, RawResults, RawResultsC, SolutionPropertiesC, SolverOptsC,
                            c_double_p)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -99,6 +99,10 @@ def load_library():
     L.miqp_solver_fixed_batch_record.restype = C.c_int; L.miqp_solver_fixed_batch_record.argtypes = [vp, C.c_int, C.POINTER(RawResultsC)]
     L.miqp_gpu_fixed_result_size.restype = C.c_int; L.miqp_gpu_fixed_result_size.argtypes = []
     L.miqp_gpu_fixed_batch_chunk.restype = C.c_int; L.miqp_gpu_fixed_batch_chunk.argtypes = []
+    L.miqp_solver_solve_fixed_as.restype = C.c_int
+    L.miqp_solver_solve_fixed_as.argtypes = [vp, C.POINTER(C.POINTER(RawResultsC)), C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_double), C.POINTER(AsNodeC), C.POINTER(C.c_ulonglong)]
+    L.miqp_solver_fixed_as_record.restype = C.c_int; L.miqp_solver_fixed_as_record.argtypes = [vp, C.c_int, C.POINTER(RawResultsC)]
+    L.miqp_gpu_as_node_size.restype = C.c_int; L.miqp_gpu_as_node_size.argtypes = []
     L.miqp_solver_set_pool.restype = C.c_int; L.miqp_solver_set_pool.argtypes = [vp, C.c_int]
     L.miqp_solver_pool_count.restype = C.c_int; L.miqp_solver_pool_count.argtypes = [vp]
     L.miqp_solver_pool_found.restype = C.c_int; L.miqp_solver_pool_found.argtypes = [vp, c_double_p, C.c_int]
@@ -129,6 +133,9 @@ def load_library():
     L.miqp_solver_solve_fixed_multi.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(C.POINTER(RawResultsC)), C.POINTER(C.c_int), C.POINTER(FixedResultC), C.POINTER(C.c_int)]
     L.miqp_solver_pool_solve_multi.restype = C.c_int
     L.miqp_solver_pool_solve_multi.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(FixedResultC), C.c_int, C.POINTER(C.c_int)]
+    if L.miqp_gpu_as_node_size() != C.sizeof(AsNodeC):
+        raise RuntimeError("libmiqp_gpu.so and ctypes_types.AsNodeC disagree on miqp_as_node_c (%d / %d bytes): rebuild the library"
+                           % (L.miqp_gpu_as_node_size(), C.sizeof(AsNodeC)))
     if L.miqp_gpu_fixed_result_size() != C.sizeof(FixedResultC):
         raise RuntimeError("libmiqp_gpu.so and ctypes_types.FixedResultC disagree on miqp_fixed_result_c (%d / %d bytes): rebuild the library"
                            % (L.miqp_gpu_fixed_result_size(), C.sizeof(FixedResultC)))
@@ -158,6 +165,7 @@ EXPORTED_SYMBOLS = ["miqp_solver_create", "miqp_solver_destroy", "miqp_solver_se
                     "miqp_solver_certify", "miqp_solver_certify_batch", "miqp_gpu_certificate_size", "miqp_gpu_certify_last_timing",
                     "miqp_gpu_has_active_set", "miqp_solver_last_fixed_route", "miqp_solver_launch_plan",
                     "miqp_solver_solve_fixed_batch", "miqp_solver_fixed_batch_record", "miqp_gpu_fixed_result_size", "miqp_gpu_fixed_batch_chunk",
+                    "miqp_solver_solve_fixed_as", "miqp_solver_fixed_as_record", "miqp_gpu_as_node_size",
                     "miqp_solver_set_pool", "miqp_solver_pool_count", "miqp_solver_pool_found", "miqp_solver_pool_solve", "miqp_solver_pool_record", "miqp_gpu_pool_max",
                     "miqp_solver_solve_fixed_multi", "miqp_solver_pool_solve_multi",
                     "miqp_solver_set_pool_filter", "miqp_gpu_pool_signature", "miqp_solver_pool_signature", "miqp_solver_pool_found_decisions",
@@ -561,6 +569,39 @@ class CplexWrapper:
         out = RawResults(*list(d))
         oc = out.to_c()
         rc = self._L.miqp_solver_fixed_batch_record(self._h, int(k), C.byref(oc))
+        return rc, (out if rc == 0 else None)
+
+    def solveFixedActiveSet(self, records, start=None, block=0, cutoff=None):
+        """DIAGNOSTIC (miqp_solver_solve_fixed_as): the records as nodes of the dual active-set launches, each read back as the kernel left it.
+        start[k]: -1 cold, p < k from node p's final active set and its M, -(p + 2) the same with M rebuilt; block 0 the standard block, 1 the
+        larger one; cutoff[k] in the units of the objective (nan: none).  Returns (nodes, info32): a numpy record array with the fields of
+        miqp_as_node_c - status 0 solved, 1 infeasible, 2 cut off, 3 the block does not hold the rows, 4 the method could not finish - and the
+        32 counters of the launches.  Raises RuntimeError with the library's code and text where the call is refused."""
+        if self._push_inputs() != 0:
+            raise RuntimeError("invalid parameters")
+        n = len(records)
+        keep = [r.to_c() if r is not None else None for r in records]
+        ptrs = (C.POINTER(RawResultsC) * max(n, 1))(*[C.pointer(c) if c is not None else None for c in keep])
+        out = (AsNodeC * max(n, 1))()
+        info = (C.c_ulonglong * 32)()
+        st = None if start is None else (C.c_int * max(n, 1))(*[int(v) for v in start])
+        cu = None if cutoff is None else (C.c_double * max(n, 1))(*[float(v) for v in cutoff])
+        rc = self._L.miqp_solver_solve_fixed_as(self._h, ptrs, n, st, int(block), cu, out, info)
+        if rc != 0:
+            raise RuntimeError("miqp_solver_solve_fixed_as failed (%d): %s" % (rc, self.lastError()))
+        a = np.frombuffer(out, dtype=np.dtype([("status", "<i4"), ("steps", "<i4"), ("active", "<i4"), ("reserved", "<i4"),
+                                               ("objective", "<f8"), ("bound", "<f8"), ("violation", "<f8")]), count=n).copy()
+        return a, np.array(list(info), dtype=np.uint64)
+
+    def fixedActiveSetRecord(self, k):
+        """(rc, RawResults) of node ``k`` of the last solveFixedActiveSet of this wrapper, as fixedBatchRecord: rc 0 with the record, 1 (the
+        node was not solved) or -1 (no such node, nothing held) with None"""
+        d = (C.c_int * 6)()
+        if self._L.miqp_solver_get_dims(self._h, d) != 0:
+            return -1, None
+        out = RawResults(*list(d))
+        oc = out.to_c()
+        rc = self._L.miqp_solver_fixed_as_record(self._h, int(k), C.byref(oc))
         return rc, (out if rc == 0 else None)
 
     # ---- solution pool (IloCplex::getSolnPoolNsolns / getObjValue(i) / getValues(x, i) for a CPLEX user)

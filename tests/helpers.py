@@ -77,7 +77,30 @@ NODE_SHAPES = {
 # the shape on which each class of leaf rows binds on its own: with only that class decided the oracle's objective lies above the regions-only one
 CLASS_BINDS_ON = {"env_front": ["c2n6e2pent"], "obs_rear": ["c1n6r16hex", "c1n21o", "c2n20a"], "obs_front": ["c1n2r32o", "c1n6r16hex", "c2n6e2pent", "c2n20b"],
                   "c2c": ["c2n6e2pent", "c2n20a"]}
-RELAX_SEED = {name: 113 for name in NODE_SHAPES}   # seed of numpy.random.default_rng for the shape's relax levels (cfg4 seed 4 with 114: 1.7e-5 on 'third', replaced)
+# Shapes with LARGE ACTIVE SETS, for the active-set node tests alone (test_as_node_*.py; the node tests of the interior point keep the list above).  cfg3's
+# shape with the references stretched (tweak_instance): the cars are asked to go faster than their bounds allow and to pass through each other, so
+# box rows and car/car rows bind along the horizon.  The oracle's active rows per level (complete, third, two_thirds, regions_only, only_env_front,
+# only_c2c): seed 121: 48, 40, 27, 24, 24, 48; seed 107: 45, 37, 22, 19, 19, 45 - none above the 48 that the 64 slots must hold with room to spare.
+# Of these levels the larger block holds regions_only and only_c2c (the front-point rows of two environment pieces are beyond both blocks, as on
+# cfg4's shape): a cold solve of 45 and of 48 rows, a child that grows from 24 to 48, and a child that takes over a 48-row parent and drops half of its rows.
+# NOT COVERED: the load of a parent's packed triangle in MORE THAN ONE PART.  The staging room of as_onchip_kernel is (SPAN - 192 N) / 8 doubles, SPAN
+# the second and third region of oc_lds_layout: 704 doubles in the standard block at 20 steps (a triangle of up to 37 rows: 703 doubles), 1184 in the larger block (up
+# to 48 rows: 1176 doubles); shorter horizons have more room per row.  So a second part needs a FINISHED parent of 38 rows or more on the standard
+# block - which holds one car there: 2 x 19 jerks, 38 independent rows at the most, and the stretched one-car instances end at 35 or 36 - or of 49 or
+# more on the larger block.  Searched over cfg3's shape, seeds 0 to 419, cfg4's, seeds 0 to 71, and one car on 20 steps, seeds 0 to 23, stretch 1.1 to 6
+# (1900 instances), with the rule of test_node_records_cpu.py - states that move by less than 1e-5 between QP_TOL_FINAL and a tolerance 100 times
+# looser: most stretched instances break it (cfg3 seed 5 with stretch 1.5 by 2.8e-4, cfg4 seed 4 with 1.5 by 1.8e-4), and none whose held levels have 49
+# to 62 rows passes it (closest: cfg3 seed 85 with stretch 1.6, 58 rows on only_c2c, 2.2e-5).  Two cars with ONE environment piece have 42 to 44 rows on
+# every level (seed 111, stretch 1.3, 5.9e-6), but the rows of a single piece stay on whatever the record says (relax, above) and put every level of 20
+# steps beyond both blocks (found on the device).  No one-car shape has 40 rows, by the count above.
+AS_LARGE_SHAPES = {"c2n20w121": ("cfg3", 121, {"stretch": 1.2}), "c2n20w107": ("cfg3", 107, {"stretch": 1.2})}
+# FULL SLOTS: a shape whose held levels need more rows than the 64 slots, for the "no free slot" exit alone.  cfg3 seed 11 with stretch 1.4: the oracle
+# has 98 active rows on only_c2c and 66 on regions_only, the same at both tolerances, and its objective moves by 4e-10 relative between them.  Its
+# STATES move by 6e-5, so it breaks the well-posedness rule - as every instance found with 64 rows or more does (the smallest spread among 60: 1.8e-4
+# on all six levels) - and is exempt from it: what is asserted on it are a verdict, a counter and an objective, never a state.
+AS_FULL_SHAPES = {"c2n20f11": ("cfg3", 11, {"stretch": 1.4})}
+_EXTRA_SHAPES = dict(AS_LARGE_SHAPES, **AS_FULL_SHAPES)
+RELAX_SEED = {name: 113 for name in list(NODE_SHAPES) + list(_EXTRA_SHAPES)}   # seed of numpy.random.default_rng for the shape's relax levels (cfg4 seed 4 with 114: 1.7e-5 on 'third', replaced)
 
 
 def copy_record(r):
@@ -159,7 +182,7 @@ def relax(r, disjunctions):
 def shape_dims(name):
     """(cars, steps, regions, pieces, obstacles, edges) of NODE_SHAPES[name], without generating it"""
     from planner_miqp_amd import synthetic
-    cfg = NODE_SHAPES[name][0]
+    cfg = (NODE_SHAPES.get(name) or _EXTRA_SHAPES[name])[0]
     cfg = synthetic.CONFIGS[cfg] if isinstance(cfg, str) else tuple(cfg)
     return tuple(cfg[:5]) + ((cfg[5] if len(cfg) > 5 else 4) if cfg[4] > 0 else 0,)
 
@@ -202,6 +225,33 @@ INFEASIBLE_NODES = [
     ("c2n20a", "obs_rear", (0, 0, 1), 0), ("c2n20a", "obs_rear", (1, 1, 1), 1), ("c2n20a", "obs_front", (1, 0, 1, 1), 1),
     ("c2n20a", "c2c", (0, 0, 1, 0), 1), ("c2n20a", "c2c", (0, 0, 1, 2), 0),
 ]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the active-set node tests (test_as_node_records_cpu.py, test_as_node_gpu.py): the shapes that have the active-set launches, the pairs of levels a
+# node is started from (parent level, child level) and the infeasible records with the level they are made from.  On cfg4's shape the complete
+# record is beyond both on-chip blocks, so its step-1 disjunction is flipped on the level that decides that class alone, which the larger block
+# holds (the obstacle front points alone are beyond it as well: no record of that class there).
+AS_CHAIN = ["regions_only", "two_thirds", "third", "complete"]   # rows arrive, three generations
+
+
+def as_shapes():
+    from planner_miqp_amd import has_active_set
+    return [n for n in list(NODE_SHAPES) + list(AS_LARGE_SHAPES) if has_active_set(*shape_dims(n)[:2])]
+
+
+def as_first_pairs(name):
+    """first-generation (parent, child) pairs of a shape with leaf disjunctions: rows arrive, rows leave, and each class on its own; on the shapes with
+    large active sets also only_c2c -> regions_only: a parent of 45 or 48 rows of which half leave"""
+    names = level_names(shape_dims(name))
+    if len(names) == 1:
+        return []
+    return [("regions_only", "two_thirds"), ("complete", "two_thirds")] + [("regions_only", n) for n in names if n.startswith("only_")] + \
+           ([("only_c2c", "regions_only")] if name in AS_LARGE_SHAPES and "only_c2c" in names else [])
+
+
+AS_INFEASIBLE = [(n, "complete", cls, key, alt) for n, cls, key, alt in INFEASIBLE_NODES if n != "c2n20a"] + \
+                [(n, "only_" + cls, cls, key, alt) for n, cls, key, alt in INFEASIBLE_NODES if n == "c2n20a" and cls != "obs_front"]
 
 
 def infeasible_record(r, cls, key, alt):
@@ -273,7 +323,7 @@ def soft_levels(name, rec, mask):
 
 def _generate(name):
     from planner_miqp_amd import synthetic
-    cfg, seed, tweaks = NODE_SHAPES[name]
+    cfg, seed, tweaks = NODE_SHAPES.get(name) or _EXTRA_SHAPES[name]
     p = synthetic.generate(cfg, seed, gap=1e-7, max_time=30)
     tweak_instance(p, **tweaks)
     return p
@@ -296,14 +346,19 @@ _INCUMBENTS = {}
 NODE_LIMIT = 800   # nodes of the oracle's dive for the incumbent; nothing else ends it (no time limit), so the record is the same on every machine
 
 
-def tweak_instance(p, ahead=None, spacing=None, shift=None, piece1_top=None):
+def tweak_instance(p, ahead=None, spacing=None, shift=None, piece1_top=None, stretch=None):
     """in place, what synthetic.generate cannot be asked for - so that the leaf rows of a short horizon BIND:
     ahead: obstacle 0 is moved into the first car's lane, its centre that far ahead of the car (the generator puts it 20 to 80 m ahead);
     spacing: car c starts c * spacing ahead of car 0 instead of 8 m apart (the car/car rows);
     shift: cars, references and obstacles are moved that far along the road, towards the border of the two environment pieces (65 to 75 m);
-    piece1_top: the second environment piece reaches only up to this y (the first car has to have left its lane when it leaves the first piece)"""
+    piece1_top: the second environment piece reaches only up to this y (the first car has to have left its lane when it leaves the first piece);
+    stretch: every reference entry of car c moves to x0[c, 0] + stretch * (entry - x0[c, 0]) - the cars are asked to go faster than their bounds allow,
+    so the box rows bind along the horizon (the large active sets of test_as_node_gpu.py)"""
     x0 = np.array(p.IntitialState, float)
     xr = np.array(p.x_ref, float)
+    if stretch is not None:
+        for c in range(p.NumCars):
+            xr[c] = x0[c, 0] + stretch * (xr[c] - x0[c, 0])
     if spacing is not None:
         for c in range(1, p.NumCars):
             d = x0[0, 0] + c * spacing - x0[c, 0]

@@ -30,6 +30,8 @@ class Oracle:
         L.orc_solve_fixed.argtypes = [vp, C.POINTER(RawResultsC), C.POINTER(RawResultsC), C.POINTER(C.c_double), C.POINTER(C.c_int)]
         L.orc_solve_fixed_tol.restype = C.c_int
         L.orc_solve_fixed_tol.argtypes = L.orc_solve_fixed.argtypes + [C.c_double]
+        L.orc_solve_fixed_active.restype = C.c_int
+        L.orc_solve_fixed_active.argtypes = [vp, C.POINTER(RawResultsC), C.c_double, C.POINTER(C.c_int)]
         self.L = L
 
     # ---- instances
@@ -86,3 +88,10 @@ class Oracle:
         else:
             st = self.L.orc_solve_fixed_tol(h, C.byref(fc), C.byref(rc), C.byref(obj), C.byref(it), float(qp_tol))
         return st, res, obj.value, it.value
+
+    def solve_fixed_active(self, h, fixed: RawResults, qp_tol=1e-13):
+        """(rc, rows whose multiplier exceeds 1e-6 and the row's own slack at the oracle's solution - oracle.h says why both); qp_tol 1e-13 is QP_TOL_FINAL"""
+        fc = fixed.to_c()
+        n = C.c_int(-1)
+        st = self.L.orc_solve_fixed_active(h, C.byref(fc), float(qp_tol), C.byref(n))
+        return st, n.value

@@ -13,7 +13,8 @@ record has no field for them, fix_from_results leaves them at -1 (decode_row and
 row of that meaning.  They stay covered end to end only.
 
 Soft obstacles - fix records that ignore points of an obstacle, the byte L and its price - are held against the oracle in the same way in
-test_node_qp_soft_gpu.py.  Out of scope: the active-set kernels (solve_fixed runs the interior point chain only).
+test_node_qp_soft_gpu.py.  The active-set kernels (solve_fixed runs the interior point chain only) are held against the oracle on the same records
+in test_as_node_gpu.py.
 All tests here need a real MI355X: run with  python -m pytest tests/test_node_qp_gpu.py -m gpu."""
 import numpy as np
 import pytest
