@@ -256,6 +256,27 @@ class CplexWrapper {
     if (decisions.size() < D * (size_t)n) return -1;
     return miqp_solver_solve_decisions(h_, decisions.data(), n, results.data(), best);
   }
+  // canonicalDecisions: solveDecisions, and canon[k * D ..] the canonical labels of record k's own solution, written on the device
+  // (miqp_solver_canonical_decisions): records whose labels agree are one solution.  All -1 for an entry of status 1 or 2.
+  int canonicalDecisions(const std::vector<signed char>& decisions, int n, std::vector<miqp_fixed_result_c>& results, std::vector<signed char>& canon, int* best = nullptr) {
+    results.assign(n > 0 ? (size_t)n : 0, miqp_fixed_result_c{2, -1, 0, 0, std::nan(""), std::nan("")});
+    canon.clear();
+    int d[6];
+    if (!h_ || n <= 0 || miqp_solver_get_dims(h_, d) != 0) return -1;
+    const size_t D = (size_t)d[0] * d[1] * 6 + (size_t)d[0] * d[4] * d[1] * 5 + (size_t)(d[0] * (d[0] - 1) / 2) * d[1] * 4;
+    if (decisions.size() < D * (size_t)n) return -1;
+    canon.assign(D * (size_t)n, (signed char)-1);
+    return miqp_solver_canonical_decisions(h_, decisions.data(), n, results.data(), canon.data(), best);
+  }
+  // exploreSolutionPoolDistinct: exploreSolutionPool that admits a neighbour only when the canonical labels of its own solution have a new signature
+  // as well (miqp_solver_pool_explore_distinct): an entry's solution under other labels takes no place.
+  int exploreSolutionPoolDistinct(std::vector<miqp_pool_explore_c>& added, int max_passes = 4, double max_rel = -1.0) {
+    added.assign((size_t)miqp_gpu_pool_max(), miqp_pool_explore_c{-1, 0, 0, 0, 0, 0, 0, 0, std::nan("")});
+    if (!h_) { added.clear(); return -1; }
+    const int rc = miqp_solver_pool_explore_distinct(h_, max_passes, max_rel, added.data(), (int)added.size());
+    added.resize(rc > 0 ? (size_t)rc : 0);
+    return rc;
+  }
   SolutionProperties getSolutionProperties() const { return solutionProperties_; }
   void setDebugOutputPrint(bool v) { print_debug_outputs_ = v; }
   void setDebugOutputFilePath(std::string in) { debugOutputFilePath_ = in; }

@@ -452,6 +452,39 @@ int miqp_gpu_pool_explore_size(void);
  * iterations, out[5] 1 when the last allowed pass still admitted something (with places still free miqp_solver_last_error says so), else 0. */
 int miqp_solver_pool_explore(miqp_solver_t* s, int max_passes, double max_rel, miqp_pool_explore_c* out, int cap);
 
+/* ---- canonical labels on the device, and the explore that admits a manoeuvre only when its own labels are new.  Opt-in and new: the
+ * calls above stay what they are. ----
+ * The CANONICAL record of a solved node: per disjunction of the steps 1 .. N - 1 the first alternative that holds at the node's own solution - what
+ * miqp_solver_fixed_batch_record hands out, read back as a fix record: byte for byte the D decision bytes of
+ * miqp_solver_pool_signature(record, 31).  An undecided byte of the node's record counts as alternative 0 there, as in every record the library
+ * hands out.  Step 0 is -1.  Two records with the same canonical record are one solution under two names.
+ * miqp_solver_canonical_decisions is miqp_solver_solve_decisions - contract, return codes, miqp_solver_last_timing, out and best are that call's, bit
+ * for bit: the same chain, the same chunks, the same state for miqp_solver_fixed_batch_record - with pool_label_kernel behind every chunk of the
+ * chain: canon[k * D ..] receives the D canonical bytes of entry k, all -1 for an entry of status 1 or 2 and for a record with an undecided region
+ * byte at a step >= 1 (its points have no region to be taken in).  A caller enumerating manoeuvres learns which of its records are one solution
+ * without building n RawResults records.  Additional refusal: -3 with a text in miqp_solver_last_error (cleared at the start of the call) when two
+ * fix records and a trajectory row exceed the LDS of a workgroup (160 KB).  No reference counterpart; the reference's collectRawResults is the host
+ * analogue. */
+int miqp_solver_canonical_decisions(miqp_solver_t* s, const signed char* decisions, int n, miqp_fixed_result_c* out, signed char* canon /* [n * D] */, int* best);
+/* the same labels for trajectories the caller holds, on the host: trajectories[k] is the row of N * 8 * NrCars doubles of record k in the
+ * library's column order per step (per car position, velocity, acceleration in x then y, then the inputs of all cars).  via 0: the restatement the
+ * kernel compiles (every operation rounded on its own, in the host's order), via 1: the two host functions behind miqp_solver_fixed_batch_record -
+ * the two agree byte for byte, which is what pins the kernel's arithmetic without a device.  canon[k * D ..] is all -1 for a record out of range or
+ * with an undecided region byte at a step >= 1.  Returns the number of records labelled; -1 NULL arguments, no instance or n <= 0; -2 via not 0 or 1,
+ * or a refused shape.  Pure host code: no device. */
+int miqp_solver_canonical_labels(const miqp_solver_t* s, const signed char* decisions, const double* trajectories, int n, int via, signed char* canon /* [n * D] */);
+/* miqp_solver_pool_explore with DISTINCT admission: arguments, return codes, refusals, timing slots, "the pool is untouched on every failure" and the
+ * stored bytes - an added entry is its parent's bytes behind its jump - are that call's.  Differences:
+ * pass 0, as in the climb: the kept entries' own records are solved at the tight tolerance and labelled; per place the call keeps, beside the
+ * signature, the CANONICAL signature - the signature under the handle's filter of the entry's canonical record; of its as-found bytes for a kept
+ * entry that is not feasible there.  Every pass labels its neighbours chunk by chunk, and a neighbour is admitted when its signature AND the
+ * canonical signature of its own solution are not in the pool yet - the entries admitted earlier in the pass included; both are appended with it.
+ * A neighbour that is an entry's solution under other labels is dropped and takes no place, so the places go to the manoeuvres behind it in the
+ * visiting order.  Stopping rules, cap and order are unchanged.  Additional refusal (-3, with a text): 4 x record bytes + 64 KB, or 2 x record bytes
+ * and a trajectory row, exceed 160 KB.
+ * miqp_solver_last_timing: out[3] and out[4] include pass 0's nodes (one per kept entry) and their iterations; out[2] does not count pass 0. */
+int miqp_solver_pool_explore_distinct(miqp_solver_t* s, int max_passes, double max_rel, miqp_pool_explore_c* out, int cap);
+
 /* 1 when instances of this shape (NrCars, N) have the dual active-set launches - one or two cars, a horizon of up to 20 steps - else 0 (their node
  * relaxations are interior point solves).  Pure host code: no device is needed or touched.  A call switches the launches off with MIQP_AS=0 */
 int miqp_gpu_has_active_set(int num_cars, int num_steps);

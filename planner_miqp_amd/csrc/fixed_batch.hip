@@ -27,14 +27,14 @@ bool fixed_record_ok(const miqp_raw_results_c& r) {
 
 // Behind the fix records of a call: they run, and every handle receives its answers.  Node c is entry where[c] of the caller's arrays and belongs to
 // handle inst[c]; the nodes of handle h are nfirst[h] .. nfirst[h + 1] - 1, its entries first[h] .. first[h + 1] - 1.  out and best (may be NULL)
-// are the caller's.  0 or -3
+// are the caller's; after (may be NULL) is enqueued behind every chunk (fixed_run).  0 or -3
 int fixed_answer(FixedCall& call, const std::vector<signed char>& fix, const std::vector<int>& inst, const std::vector<int>& where, const std::vector<int>& nfirst, const int* first,
-                 miqp_fixed_result_c* out, int* best, double t_call) {
+                 miqp_fixed_result_c* out, int* best, double t_call, const FixedAfterChunk* after = nullptr) {
   const Layout& Y = call.Y; const size_t fl = (size_t)Y.fixlen, row = (size_t)Y.N * Y.nz;
   const int m = (int)where.size();
   const double setup_s = wall_s() - t_call;
   std::vector<miqp_fixed_result_c> tmp; std::vector<double> Z; std::vector<int> hbest; float dev_ms = 0.0f; int groups = 0;
-  if (call.run(fix, inst, m, tmp, Z, hbest, dev_ms, groups) != 0) return -3;
+  if (call.run(fix, inst, m, tmp, Z, hbest, dev_ms, groups, after) != 0) return -3;
   for (int c = 0; c < m; ++c) out[where[c]] = tmp[c];
   const double call_s = wall_s() - t_call;
   for (int h = 0; h < call.n; ++h) {

@@ -215,10 +215,14 @@ bool fixed_chunk(DevCtx& X, const DevBuf& Bp, const Layout& Y, const FixedDev& F
   return true;
 }
 
+// what a caller enqueues behind a chunk's fixed_chunk while the chunk's records still lie in pool_fix: (first node of the chunk, its nodes) -> false on a HIP error
+using FixedAfterChunk = std::function<bool(int, int)>;
+
 // The chunks of `fix` (m records; inst[k]: the handle of record k, ascending) through the chain.  tmp[m] and Zout receive the results, best[h] the
-// index WITHIN handle h's records of this run of its feasible minimum (-1: none), groups the number of chunks.  false: HIP error
+// index WITHIN handle h's records of this run of its feasible minimum (-1: none), groups the number of chunks.  after (may be NULL) runs behind
+// every chunk.  false: HIP error
 bool fixed_run(DevCtx& X, FixedDev& G, const Layout& Y, int n_inst, const std::vector<signed char>& fix, const std::vector<int>& inst, int m,
-               std::vector<miqp_fixed_result_c>& tmp, std::vector<double>& Zout, std::vector<int>& best, float& dev_ms, int& groups) {
+               std::vector<miqp_fixed_result_c>& tmp, std::vector<double>& Zout, std::vector<int>& best, float& dev_ms, int& groups, const FixedAfterChunk* after = nullptr) {
   DevBuf& B = X.B; hipStream_t st = X.stream;
   const size_t fl = (size_t)Y.fixlen, row = (size_t)Y.N * Y.nz;
   const int nch = (m + FB_CHUNK - 1) / FB_CHUNK;
@@ -262,6 +266,7 @@ bool fixed_run(DevCtx& X, FixedDev& G, const Layout& Y, int n_inst, const std::v
     HIP_OK(hipEventRecord(G.ev_taken[p], st));
     FixedChunk C{bc, c0, G.d_res + c0, G.d_Z + (size_t)c0 * row, ns, G.d_sobj + sfirst[j], G.d_sidx + sfirst[j]};
     if (!fixed_chunk(X, Bp, Y, G, n_inst, C)) return false;
+    if (after && !(*after)(c0, bc)) return false;
   }
   HIP_OK(hipEventRecord(X.ev1, st));
   std::vector<double> sobj(nsegs); std::vector<int> sidx(nsegs);
@@ -324,9 +329,10 @@ struct FixedCall {
     HIP_OK(hipStreamSynchronize(st));   // (ident is a local)
     return true;
   }
-  int run(const std::vector<signed char>& fix, const std::vector<int>& inst, int m, std::vector<miqp_fixed_result_c>& tmp, std::vector<double>& Z, std::vector<int>& best, float& dev_ms, int& groups) {
+  int run(const std::vector<signed char>& fix, const std::vector<int>& inst, int m, std::vector<miqp_fixed_result_c>& tmp, std::vector<double>& Z, std::vector<int>& best, float& dev_ms, int& groups,
+          const FixedAfterChunk* after = nullptr) {
     FixedDev& F = dev();
-    if (!fixed_run(*X, F, Y, n, fix, inst, m, tmp, Z, best, dev_ms, groups)) { (void)hipStreamSynchronize(X->stream); if (F.s_up) (void)hipStreamSynchronize(F.s_up); return -3; }
+    if (!fixed_run(*X, F, Y, n, fix, inst, m, tmp, Z, best, dev_ms, groups, after)) { (void)hipStreamSynchronize(X->stream); if (F.s_up) (void)hipStreamSynchronize(F.s_up); return -3; }
     return 0;
   }
 };

@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <atomic>
@@ -1694,6 +1695,7 @@ bool solve_batch_impl(miqp_solver_t* const* S, int n, int* statuses, const Split
 #include "as_fixed.hip"
 #include "solution_pool.hip"
 #include "pool_improve.hip"
+#include "pool_label.hip"
 #include "pool_explore.hip"
 
 // ================================================================================================

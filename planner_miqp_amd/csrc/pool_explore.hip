@@ -30,6 +30,11 @@
 //                          existing entry is changed or moved.
 // Owner computes: no atomics, no lock, no wavefront waits on another, no scratch; records move as 16-byte loads and stores.  The host waits once per
 // pass and reads the number admitted, their `out` records and the jump counts of the next pass.
+//
+// DISTINCT admission (miqp_solver_pool_explore_distinct; opt-in, the call above is unchanged): most neighbours of a new signature are
+// an entry's own solution under other labels.  The distinct call solves the kept entries' own records first (pass 0), has pool_label_kernel
+// (pool_label.hip) write the canonical record of every solved node behind its chunk, keeps per place the signature of that record beside the plain
+// one (pool_canon0_kernel) and admits a neighbour only when BOTH signatures are new (pool_admit_distinct_kernel: the same body, one more test).
 #pragma once
 
 namespace {
@@ -111,6 +116,10 @@ struct PoolExploreArgs {
   int* state;                     // [0] entries in the pool, [1] admitted by the last pass, [2] iterations of the last pass's neighbours
   miqp_pool_explore_c* out;       // [places] the records of the last pass's admitted entries
   double obj0, max_rel; int pass;
+  // the distinct call only (miqp_solver_pool_explore_distinct, below): the signatures of the entries' CANONICAL records under the handle's filter, and
+  // the labelled record of every neighbour of the pass (pool_label_kernel, chunk by chunk)
+  signed char* csig;              // [places]
+  const signed char* lab;         // [NB_MAX]
 };
 
 __global__ __launch_bounds__(64) void pool_jumps_kernel(const PoolExploreArgs E) {
@@ -157,12 +166,16 @@ __device__ inline void pool_admit_signature(const PoolExploreArgs& E, uint4* rec
 
 constexpr double POOL_ADMIT_NONE = 1e308;   // in the staged objectives: not feasible, beyond the cap, or visited
 
-__global__ __launch_bounds__(64) void pool_admit_kernel(const PoolExploreArgs E, int nb_max) {
-  extern __shared__ uint4 pa_lds[];   // the candidate's record, its signature; behind them one objective per neighbour of the pass
+// The admission of a pass.  DISTINCT (miqp_solver_pool_explore_distinct): a candidate of a new signature is admitted only when the signature of its
+// CANONICAL record - the labels of its own solution, E.lab - is new as well, among the canonical signatures of everything in the pool (E.csig: the
+// kept entries' from pass 0, the admitted ones' appended here); a candidate dropped for that takes no place.  Without DISTINCT none of that is compiled
+template <bool DISTINCT>
+__device__ inline void pool_admit_body(const PoolExploreArgs& E, int nb_max, uint4* pa_lds) {
   const PoolImproveArgs& A = E.A;
   const int lane = threadIdx.x, chunks = A.fixlen >> 4, K = A.m;
   uint4* const cand = pa_lds; uint4* const csig = cand + chunks;
-  double* const key = (double*)(csig + chunks);
+  uint4* const ccan = csig + chunks; uint4* const ccsg = ccan + chunks;   // DISTINCT: the candidate's labelled record and its signature
+  double* const key = (double*)(csig + (DISTINCT ? 3 : 1) * chunks);
   const int fam = A.ent_fam[0];
   const int n0 = min(max(E.state[0], 0), K), total = min(max(A.off[K], 0), nb_max);
   uint4* const pool = (uint4*)A.cur; uint4* const sig = (uint4*)E.sig;
@@ -211,6 +224,14 @@ __global__ __launch_bounds__(64) void pool_admit_kernel(const PoolExploreArgs E,
     bool known = false;
     for (int j = 0; j < n && !known; ++j) known = pool_cmp(csig, sig + (size_t)j * chunks, chunks, lane) == 0;
     if (known) continue;
+    if (DISTINCT) {
+      const uint4* const lab = (const uint4*)E.lab + (size_t)bg * chunks; uint4* const can = (uint4*)E.csig;
+      for (int c = lane; c < chunks; c += 64) { ccan[c] = lab[c]; ccsg[c] = make_uint4(~0u, ~0u, ~0u, ~0u); }
+      pool_admit_signature(E, ccan, ccsg, fam, lane);
+      for (int j = 0; j < n && !known; ++j) known = pool_cmp(ccsg, can + (size_t)j * chunks, chunks, lane) == 0;
+      if (known) continue;   // (an alias of an entry: the same solution under labels of another signature)
+      for (int c = lane; c < chunks; c += 64) can[(size_t)n * chunks + c] = ccsg[c];
+    }
     for (int c = lane; c < chunks; c += 64) { pool[(size_t)n * chunks + c] = cand[c]; sig[(size_t)n * chunks + c] = csig[c]; }
     if (lane == 0) {
       A.cur_obj[n] = bo;
@@ -223,6 +244,37 @@ __global__ __launch_bounds__(64) void pool_admit_kernel(const PoolExploreArgs E,
   }
   for (int j = lane; j < K; j += 64) A.act[j] = j >= n0 && j < n ? 1 : 0;   // the next pass expands what this one added
   if (lane == 0) { E.state[0] = n; E.state[1] = added; E.state[2] = it; }
+}
+
+__global__ __launch_bounds__(64) void pool_admit_kernel(const PoolExploreArgs E, int nb_max) {
+  extern __shared__ uint4 pa_lds[];   // the candidate's record, its signature; behind them one objective per neighbour of the pass
+  pool_admit_body<false>(E, nb_max, pa_lds);
+}
+
+__global__ __launch_bounds__(64) void pool_admit_distinct_kernel(const PoolExploreArgs E, int nb_max) {
+  extern __shared__ uint4 pa_lds[];   // the candidate's record, its signature, its labelled record, that one's signature; behind them the objectives
+  pool_admit_body<true>(E, nb_max, pa_lds);
+}
+
+// Pass 0 of the distinct call, behind the chain and pool_label_kernel over the kept entries' own records: ONE wavefront writes, per kept entry, the
+// signature of its canonical record - of its as-found bytes when its own QP is not feasible at the tight tolerance - and the iterations of the pass
+__global__ __launch_bounds__(64) void pool_canon0_kernel(const PoolExploreArgs E) {
+  extern __shared__ uint4 pc_lds[];   // a record, its signature
+  const PoolImproveArgs& A = E.A;
+  const int lane = threadIdx.x, chunks = A.fixlen >> 4, K = A.m;
+  uint4* const rec = pc_lds; uint4* const sg = rec + chunks;
+  const int fam = A.ent_fam[0], n0 = min(max(E.state[0], 0), K);
+  int it = 0;
+  for (int j = 0; j < n0; ++j) {
+    const miqp_fixed_result_c r = A.res[j];
+    it += r.iterations;
+    const uint4* const src = (r.status == 0 ? (const uint4*)E.lab : (const uint4*)A.cur) + (size_t)j * chunks;
+    __syncthreads();
+    for (int c = lane; c < chunks; c += 64) { rec[c] = src[c]; sg[c] = make_uint4(~0u, ~0u, ~0u, ~0u); }
+    pool_admit_signature(E, rec, sg, fam, lane);
+    for (int c = lane; c < chunks; c += 64) ((uint4*)E.csig)[(size_t)j * chunks + c] = sg[c];
+  }
+  if (lane == 0) E.state[2] = it;
 }
 
 // buffers of the call beside the climb's (PoolImproveDev, PoolEntryDev), cached per device (grown, not shrunk)
@@ -239,6 +291,17 @@ struct PoolExploreDev {
     }
     return true;
   }
+  // the distinct call's: the canonical signatures of the places and the labelled records of a pass's neighbours
+  signed char* csig = nullptr; signed char* lab = nullptr; size_t lab_cap = 0;
+  bool ensure_distinct(size_t fl) {
+    if ((size_t)PoolImproveDev::NB_MAX * fl > lab_cap) {
+      if (csig) (void)hipFree(csig); if (lab) (void)hipFree(lab);
+      csig = nullptr; lab = nullptr; lab_cap = 0;
+      HIP_OK(hipMalloc((void**)&csig, MIQP_POOL_MAX * fl)); HIP_OK(hipMalloc((void**)&lab, (size_t)PoolImproveDev::NB_MAX * fl));
+      lab_cap = (size_t)PoolImproveDev::NB_MAX * fl;
+    }
+    return true;
+  }
 };
 std::map<int, PoolExploreDev> g_pool_explore_dev;   // by device ordinal; used under the device lock
 
@@ -249,20 +312,28 @@ struct PoolExploreOut {
   std::string err;
 };
 
-// false: HIP error (nothing of the handle has been touched).  n: entries in the pool, K: its places
-bool pool_explore_run(const FixedCall& call, int fam, int L, const signed char* fix, int n, int K, double obj0, double max_rel, int max_passes, PoolExploreOut& O) {
+// false: HIP error (nothing of the handle has been touched).  n: entries in the pool, K: its places; name: the entry point, for its messages;
+// distinct: pass 0 in front, the labels of every chunk, the admission by both signatures (miqp_solver_pool_explore_distinct)
+bool pool_explore_run(const FixedCall& call, const char* name, bool distinct, int fam, int L, const signed char* fix, int n, int K, double obj0, double max_rel, int max_passes, PoolExploreOut& O) {
   DevCtx& X = *call.X; DevBuf& B = X.B; hipStream_t st = X.stream; const Layout& Y = call.Y;
   const size_t fl = (size_t)Y.fixlen;
   PoolImproveDev& R = g_pool_improve_dev[X.device]; PoolEntryDev& G = g_pool_entry_dev[X.device]; PoolExploreDev& Q = g_pool_explore_dev[X.device];
-  if (!R.ensure((size_t)Y.N * Y.nz) || !G.ensure(MIQP_POOL_MAX, fl) || !Q.ensure(fl)) return false;
+  if (!R.ensure((size_t)Y.N * Y.nz) || !G.ensure(MIQP_POOL_MAX, fl) || !Q.ensure(fl) || (distinct && !Q.ensure_distinct(fl))) return false;
   const PoolDims dims = pool_dims(Y);
-  const size_t jump_lds = fl + (size_t)pool_jump_units(dims) * sizeof(int), admit_lds = 2 * fl + (size_t)PoolImproveDev::NB_MAX * sizeof(double);
+  const size_t jump_lds = fl + (size_t)pool_jump_units(dims) * sizeof(int), admit_lds = (distinct ? 4 : 2) * fl + (size_t)PoolImproveDev::NB_MAX * sizeof(double);
   if (std::max(jump_lds, admit_lds) > POOL_EXPLORE_LDS_MAX) {
-    O.err = "miqp_solver_pool_explore: the fix record of this shape does not fit the LDS of pool_admit_kernel twice beside the objectives of a pass";
+    O.err = std::string(name) + (distinct ? ": the fix record of this shape does not fit the LDS of pool_admit_distinct_kernel four times beside the objectives of a pass"
+                                          : ": the fix record of this shape does not fit the LDS of pool_admit_kernel twice beside the objectives of a pass");
     std::fprintf(stderr, "[miqp_gpu] %s (%zu bytes)\n", O.err.c_str(), std::max(jump_lds, admit_lds)); return false;
   }
+  if (distinct && !pool_label_fits(Y, name, O.err)) return false;
   HIP_OK(hipFuncSetAttribute((const void*)pool_jumps_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)jump_lds));
-  HIP_OK(hipFuncSetAttribute((const void*)pool_admit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)admit_lds));
+  if (distinct) {
+    HIP_OK(hipFuncSetAttribute((const void*)pool_admit_distinct_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)admit_lds));
+    HIP_OK(hipFuncSetAttribute((const void*)pool_canon0_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * fl)));
+    if (!pool_label_set_lds(Y)) return false;
+  } else
+    HIP_OK(hipFuncSetAttribute((const void*)pool_admit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)admit_lds));
   std::vector<int> act(MIQP_POOL_MAX, 0); for (int k = 0; k < n; ++k) act[k] = 1;
   const int state0[4] = {n, 0, 0, 0};
   HIP_OK(hipMemsetAsync(B.batch_inst, 0, (size_t)FB_CHUNK * 4, st));
@@ -280,6 +351,7 @@ bool pool_explore_run(const FixedCall& call, int fam, int L, const signed char* 
   A.ent_inst = G.ent_inst; A.ent_fam = G.ent_fam; A.off = G.off; A.batch_inst = B.batch_inst;
   A.dims = dims; A.fixlen = (int)fl; A.m = K;   // (every place of the pool is an entry of the kernels: a free one is not expanded and has no jumps)
   E.L = L; E.sig = Q.sig; E.state = Q.state; E.out = Q.out; E.obj0 = obj0; E.max_rel = max_rel; E.pass = 0;
+  E.csig = distinct ? Q.csig : nullptr; E.lab = distinct ? Q.lab : nullptr;
   // `total` neighbours of a pass through the chain, a chunk at a time, as the climb sends them (no segments, the trajectories written over)
   auto solve_nodes = [&](int total) -> bool {
     for (int c0 = 0; c0 < total; c0 += FB_CHUNK) {
@@ -287,13 +359,15 @@ bool pool_explore_run(const FixedCall& call, int fam, int L, const signed char* 
       hipLaunchKernelGGL(pool_neighbour_kernel, dim3((bc + 3) / 4), dim3(256), 0, st, A, c0, bc, 0);
       HIP_OK(hipGetLastError());
       if (!fixed_chunk(X, Bp, Y, call.dev(), 1, FixedChunk{bc, c0, R.res + c0, R.Z})) return false;
+      if (distinct && !pool_label_chunk(X, Y, 1, bc, R.res + c0, R.Z, Q.lab + (size_t)c0 * fl)) return false;   // (per chunk: the next one writes over R.Z)
     }
     return true;
   };
   // behind a pass (admit: not in front of the first one): the jumps of the next one, and what the host needs of both
   std::vector<int> cnt(MIQP_POOL_MAX); int state[4] = {n, 0, 0, 0}; std::vector<miqp_pool_explore_c> rec(MIQP_POOL_MAX);
   auto finish_pass = [&](bool admit) -> bool {
-    if (admit) hipLaunchKernelGGL(pool_admit_kernel, dim3(1), dim3(64), admit_lds, st, E, (int)PoolImproveDev::NB_MAX);
+    if (admit && distinct) hipLaunchKernelGGL(pool_admit_distinct_kernel, dim3(1), dim3(64), admit_lds, st, E, (int)PoolImproveDev::NB_MAX);
+    else if (admit) hipLaunchKernelGGL(pool_admit_kernel, dim3(1), dim3(64), admit_lds, st, E, (int)PoolImproveDev::NB_MAX);
     hipLaunchKernelGGL(pool_jumps_kernel, dim3(K), dim3(64), jump_lds, st, E);
     hipLaunchKernelGGL(pool_offsets_kernel, dim3(1), dim3(256), 0, st, A);
     HIP_OK(hipGetLastError());
@@ -306,16 +380,24 @@ bool pool_explore_run(const FixedCall& call, int fam, int L, const signed char* 
     return true;
   };
   HIP_OK(hipEventRecord(X.ev0, st));
+  if (distinct) {   // pass 0, as in the climb: the kept entries' own records through the chain, their labels, the signatures of those
+    hipLaunchKernelGGL(pool_neighbour_kernel, dim3((n + 3) / 4), dim3(256), 0, st, A, 0, n, 1);
+    HIP_OK(hipGetLastError());
+    if (!fixed_chunk(X, Bp, Y, call.dev(), 1, FixedChunk{n, 0, R.res, R.Z}) || !pool_label_chunk(X, Y, 1, n, R.res, R.Z, Q.lab)) return false;
+    hipLaunchKernelGGL(pool_canon0_kernel, dim3(1), dim3(64), 2 * fl, st, E);
+    HIP_OK(hipGetLastError());
+  }
   if (!finish_pass(false)) return false;
+  if (distinct) { O.neighbours += n; O.iterations += state[2]; }
   int have = n;
   for (;;) {
     long total = 0;
-    for (int k = 0; k < K; ++k) { if (cnt[k] < 0 || cnt[k] > POOL_MOVES_MAX) { std::fprintf(stderr, "[miqp_gpu] miqp_solver_pool_explore: jump count %d of entry %d\n", cnt[k], k); return false; } total += cnt[k]; }
+    for (int k = 0; k < K; ++k) { if (cnt[k] < 0 || cnt[k] > POOL_MOVES_MAX) { std::fprintf(stderr, "[miqp_gpu] %s: jump count %d of entry %d\n", name, cnt[k], k); return false; } total += cnt[k]; }
     if (total == 0 || total > PoolImproveDev::NB_MAX || O.passes == max_passes || have >= K) break;
     E.pass = O.passes + 1;
     HIP_OK(hipEventRecord(X.ev0, st));
     if (!solve_nodes((int)total) || !finish_pass(true)) return false;
-    if (state[0] != have + state[1] || state[1] < 0 || state[0] > K) { std::fprintf(stderr, "[miqp_gpu] miqp_solver_pool_explore: %d entries behind %d, %d admitted\n", state[0], have, state[1]); return false; }
+    if (state[0] != have + state[1] || state[1] < 0 || state[0] > K) { std::fprintf(stderr, "[miqp_gpu] %s: %d entries behind %d, %d admitted\n", name, state[0], have, state[1]); return false; }
     O.passes++; O.neighbours += total; O.iterations += state[2];
     for (int k = 0; k < state[1]; ++k) O.added.push_back(rec[k]);
     have = state[0];
@@ -346,7 +428,12 @@ int miqp_gpu_pool_jumps(int cars, int steps, int obstacles, int max_lines, int f
   return (int)mv.size();
 }
 
-int miqp_solver_pool_explore(miqp_solver_t* s, int max_passes, double max_rel, miqp_pool_explore_c* out, int cap) {
+}  // extern "C"
+
+namespace {
+
+// the two explore entries: what they refuse, the run, what the handle keeps
+int pool_explore_entry(miqp_solver_t* s, const char* name, bool distinct, int max_passes, double max_rel, miqp_pool_explore_c* out, int cap) {
   if (s) s->err.clear();   // (miqp_solver_last_error speaks of this call from here on)
   if (!s || !s->has_inst || !out || cap < 0 || max_rel != max_rel) return -1;
   if (s->pool_fam < 1 || s->pool_fam >= POOL_FAM_TIMING || !(s->pool_fam & (POOL_FAM_OBSTACLE | POOL_FAM_CAR_CAR))) return -2;
@@ -363,7 +450,7 @@ int miqp_solver_pool_explore(miqp_solver_t* s, int max_passes, double max_rel, m
   FixedCall call;
   if (call.open(one, 1, Y) != 0) return -3;
   PoolExploreOut O;
-  if (!pool_explore_run(call, s->pool_fam, s->inst.L, s->pool_fix.data(), n, K, s->pool_obj[0], max_rel, max_passes, O)) {
+  if (!pool_explore_run(call, name, distinct, s->pool_fam, s->inst.L, s->pool_fix.data(), n, K, s->pool_obj[0], max_rel, max_passes, O)) {
     (void)hipStreamSynchronize(call.X->stream); if (!O.err.empty()) s->err = O.err; return -3;
   }
   const int added = (int)O.added.size();
@@ -377,10 +464,22 @@ int miqp_solver_pool_explore(miqp_solver_t* s, int max_passes, double max_rel, m
   s->pr_n = 0; std::vector<char>().swap(s->pr_ok); std::vector<signed char>().swap(s->pr_fix); std::vector<double>().swap(s->pr_Z);
   s->timing[0] = wall_s() - t_call; s->timing[1] = O.dev_ms * 1e-3; s->timing[2] = O.passes; s->timing[3] = (double)O.neighbours; s->timing[4] = (double)O.iterations; s->timing[5] = O.still_adding ? 1 : 0;
   if (O.still_adding && n + added < K) {
-    char msg[200]; std::snprintf(msg, sizeof msg, "miqp_solver_pool_explore: the last of %d passes still added an entry and places are free; more passes may fill them", max_passes);
+    char msg[200]; std::snprintf(msg, sizeof msg, "%s: the last of %d passes still added an entry and places are free; more passes may fill them", name, max_passes);
     s->err = msg;
   }
   return added;
+}
+
+}  // namespace
+
+extern "C" {
+
+int miqp_solver_pool_explore(miqp_solver_t* s, int max_passes, double max_rel, miqp_pool_explore_c* out, int cap) {
+  return pool_explore_entry(s, "miqp_solver_pool_explore", false, max_passes, max_rel, out, cap);
+}
+
+int miqp_solver_pool_explore_distinct(miqp_solver_t* s, int max_passes, double max_rel, miqp_pool_explore_c* out, int cap) {
+  return pool_explore_entry(s, "miqp_solver_pool_explore_distinct", true, max_passes, max_rel, out, cap);
 }
 
 }  // extern "C"

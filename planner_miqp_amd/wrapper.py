@@ -129,6 +129,11 @@ def load_library():
     L.miqp_gpu_pool_jumps.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_byte), C.POINTER(C.c_int), C.c_int]
     L.miqp_gpu_pool_explore_size.restype = C.c_int; L.miqp_gpu_pool_explore_size.argtypes = []
     L.miqp_solver_pool_explore.restype = C.c_int; L.miqp_solver_pool_explore.argtypes = [vp, C.c_int, C.c_double, C.POINTER(PoolExploreC), C.c_int]
+    L.miqp_solver_pool_explore_distinct.restype = C.c_int; L.miqp_solver_pool_explore_distinct.argtypes = [vp, C.c_int, C.c_double, C.POINTER(PoolExploreC), C.c_int]
+    L.miqp_solver_canonical_decisions.restype = C.c_int
+    L.miqp_solver_canonical_decisions.argtypes = [vp, C.POINTER(C.c_byte), C.c_int, C.POINTER(FixedResultC), C.POINTER(C.c_byte), C.POINTER(C.c_int)]
+    L.miqp_solver_canonical_labels.restype = C.c_int
+    L.miqp_solver_canonical_labels.argtypes = [vp, C.POINTER(C.c_byte), c_double_p, C.c_int, C.c_int, C.POINTER(C.c_byte)]
     L.miqp_solver_solve_fixed_multi.restype = C.c_int
     L.miqp_solver_solve_fixed_multi.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(C.POINTER(RawResultsC)), C.POINTER(C.c_int), C.POINTER(FixedResultC), C.POINTER(C.c_int)]
     L.miqp_solver_pool_solve_multi.restype = C.c_int
@@ -171,7 +176,8 @@ EXPORTED_SYMBOLS = ["miqp_solver_create", "miqp_solver_destroy", "miqp_solver_se
                     "miqp_solver_set_pool_filter", "miqp_gpu_pool_signature", "miqp_solver_pool_signature", "miqp_solver_pool_found_decisions",
                     "miqp_gpu_pool_moves", "miqp_gpu_pool_moves_max", "miqp_gpu_pool_improve_size", "miqp_solver_solve_decisions", "miqp_solver_pool_improve",
                     "miqp_solver_pool_improve_multi", "miqp_gpu_pool_improve_plan",
-                    "miqp_gpu_pool_jumps", "miqp_gpu_pool_explore_size", "miqp_solver_pool_explore"]
+                    "miqp_gpu_pool_jumps", "miqp_gpu_pool_explore_size", "miqp_solver_pool_explore",
+                    "miqp_solver_canonical_decisions", "miqp_solver_canonical_labels", "miqp_solver_pool_explore_distinct"]
 
 
 # a row of CplexWrapper.launchPlan (NodeLaunch in csrc/miqp_gpu.hip)
@@ -678,7 +684,7 @@ class CplexWrapper:
         a = np.frombuffer(out, dtype=np.dtype([("before", "<f8"), ("after", "<f8"), ("moves", "<i4"), ("status", "<i4")]), count=m)
         return rc, a["before"].copy(), a["after"].copy(), a["moves"].copy(), a["status"].copy()
 
-    def exploreSolutionPool(self, max_passes=4, max_rel=-1.0):
+    def exploreSolutionPool(self, max_passes=4, max_rel=-1.0, distinct=False):
         """the free places of a FILTERED pool filled with neighbouring manoeuvre classes in one device-resident loop (miqp_solver_pool_explore;
         IloCplex::populate for a CPLEX user): pass 1 solves every jump of pool_jumps of every kept entry at the tight tolerance, pass p > 1 those of
         the entries pass p - 1 added; the best feasible neighbour of every class the pool does not hold yet is appended while a place is free.
@@ -686,10 +692,13 @@ class CplexWrapper:
         entries added - or the library's code < 0: -2 the filter is not in 1 .. 15 or has neither POOL_BY_OBSTACLE nor POOL_BY_CAR_CAR, or
         max_passes not in 1 .. 64; -3 no device; the pool is untouched then - and one dict per added entry, in pool order behind the old entries
         (parent, pass, first, stride, count, value, iterations, objective; empty for rc <= 0).  Old entries keep their bytes and places.  A
-        refined pool is dropped: call solveSolutionPool afterwards."""
+        refined pool is dropped: call solveSolutionPool afterwards.
+        ``distinct`` (miqp_solver_pool_explore_distinct): a neighbour is admitted only when the canonical labels of its own solution have a new
+        signature as well, so an entry's solution under other labels takes no place; the timing then counts pass 0, the kept entries' own solves."""
         n = pool_max()
         out = (PoolExploreC * n)()
-        rc = int(self._L.miqp_solver_pool_explore(self._h, int(max_passes), float(max_rel), out, n))
+        call = self._L.miqp_solver_pool_explore_distinct if distinct else self._L.miqp_solver_pool_explore
+        rc = int(call(self._h, int(max_passes), float(max_rel), out, n))
         return rc, [dict(parent=o.parent, **{"pass": o.pass_}, first=o.first, stride=o.stride, count=o.count, value=o.value, iterations=o.iterations,
                          objective=float(o.objective)) for o in out[:max(rc, 0)]]
 
@@ -711,6 +720,43 @@ class CplexWrapper:
         rc = int(self._L.miqp_solver_solve_decisions(self._h, d.ctypes.data_as(C.POINTER(C.c_byte)), n, out, C.byref(best)))
         a = np.frombuffer(out, dtype=_FIXED_RESULT_DTYPE, count=n)
         return (rc, a["status"].copy(), a["objective"].copy(), a["violation"].copy(), a["iterations"].copy(), a["route"].copy(), best.value)
+
+    def _decision_array(self, decisions):
+        d = np.ascontiguousarray(decisions, dtype=np.int8)
+        dims = (C.c_int * 6)()
+        if self._L.miqp_solver_get_dims(self._h, dims) != 0 and (self._push_inputs() != 0 or self._L.miqp_solver_get_dims(self._h, dims) != 0):   # (a loaded instance is kept: loading drops its pool)
+            raise RuntimeError("invalid parameters")
+        D = _decision_len(dims[0], dims[1], dims[4])
+        if d.ndim != 2 or d.shape[1] != D:
+            raise ValueError("decision records of %d bytes expected, got an array of shape %s" % (D, d.shape))
+        return d, dims
+
+    def canonicalDecisions(self, decisions):
+        """solveDecisions with the canonical labels of every solved record, written on the device (miqp_solver_canonical_decisions): returns the
+        tuple of solveDecisions and an int8 array [n, D] - row k the first alternative of every disjunction that holds at record k's own solution,
+        byte for byte poolSignature(fixedBatchRecord(k), 31); all -1 for an entry of status 1 or 2.  Rows that agree are one solution."""
+        d, _ = self._decision_array(decisions)
+        n = d.shape[0]
+        out = (FixedResultC * max(n, 1))()
+        canon = np.full((max(n, 1), d.shape[1]), -1, dtype=np.int8)
+        best = C.c_int(-1)
+        bp = C.POINTER(C.c_byte)
+        rc = int(self._L.miqp_solver_canonical_decisions(self._h, d.ctypes.data_as(bp), n, out, canon.ctypes.data_as(bp), C.byref(best)))
+        a = np.frombuffer(out, dtype=_FIXED_RESULT_DTYPE, count=n)
+        return (rc, a["status"].copy(), a["objective"].copy(), a["violation"].copy(), a["iterations"].copy(), a["route"].copy(), best.value, canon[:n])
+
+    def canonicalLabels(self, decisions, trajectories, via=0):
+        """the canonical labels of decision records [n, D] at given trajectories [n, NumSteps * 8 * NumCars], on the host
+        (miqp_solver_canonical_labels): via 0 the restatement the device kernel compiles, via 1 the host functions behind fixedBatchRecord.
+        Returns (labelled, int8 array [n, D]).  Needs no device."""
+        d, dims = self._decision_array(decisions)
+        z = np.ascontiguousarray(trajectories, dtype=np.float64)
+        if z.shape != (d.shape[0], dims[1] * 8 * dims[0]):
+            raise ValueError("trajectories of shape %s expected, got %s" % ((d.shape[0], dims[1] * 8 * dims[0]), z.shape))
+        canon = np.full(d.shape, -1, dtype=np.int8)
+        bp = C.POINTER(C.c_byte)
+        rc = int(self._L.miqp_solver_canonical_labels(self._h, d.ctypes.data_as(bp), z.ctypes.data_as(c_double_p), d.shape[0], int(via), canon.ctypes.data_as(bp)))
+        return rc, canon
 
     def solutionPoolRecord(self, k):
         """(rc, RawResults) of entry ``k`` of the last solveSolutionPool: rc 0 and the record; rc 1 (the entry did not come out feasible at the

@@ -2,7 +2,7 @@
 """The step of a filtered solution pool across manoeuvre classes (miqp_solver_pool_explore): what it adds, and what it costs against its host replay.
 
   python tools/pool_explore_ab.py [--cfg cfg4] [--seeds 16] [--gap 1e-4] [--capacity 16] [--filter 12] [--passes 4] [--max-rel -1] [--climb 8]
-                                  [--cost-seed 7] [--runs 7]
+                                  [--cost-seed 7] [--runs 7] [--distinct]
 
 Quality: per seed one solve with the filtered pool and one exploreSolutionPool(passes, max_rel) - the entries before and after, the passes and the
 neighbours solved, the device time, the objectives of the added entries relative to the incumbent (objective / entry 0's found objective - 1) - and
@@ -13,7 +13,11 @@ the same answers, which the tool checks (objective bytes and decision bytes of t
 found, which a fresh solve of the same wrapper restores; that solve's own device time (lastTiming solve_s) is the yardstick printed beside.  One
 warm-up of each side, then --runs runs, ALTERNATING A and B; median (min .. max) of the host wall clock around the call(s) and of the library's own
 figures (miqp_solver_last_timing out[0] the whole call less what miqp_solver_last_setup reports for the device context, out[1] of which on the
-device; B: summed over its calls).  Needs an MI355X."""
+device; B: summed over its calls).
+--distinct adds, per seed, the explore with distinct admission (miqp_solver_pool_explore_distinct) beside the plain one, each from the
+pool as found: entries after the call, how many of them are real - left by solveSolutionPool - and how many that call merged away; and the device time
+(miqp_solver_last_timing out[1]) of the two calls, median of --runs ALTERNATING runs behind one warm-up of each - in place of the cost comparison with
+the host replay.  Needs an MI355X."""
 import argparse
 import ctypes as C
 import os
@@ -37,6 +41,7 @@ def main():
     ap.add_argument("--climb", type=int, default=8)
     ap.add_argument("--cost-seed", type=int, default=7)
     ap.add_argument("--runs", type=int, default=7)
+    ap.add_argument("--distinct", action="store_true")
     a = ap.parse_args()
     import numpy as np
     import planner_miqp_amd as P
@@ -77,6 +82,34 @@ def main():
         rel2 = [after[n0 + k] / after[0] - 1.0 for k in range(rc)]
         print("seed %2d: %2d -> %2d entries, %d passes%s, %5d neighbours, device %8.3f ms | incumbent %.1f | added, relative to it: %s | behind the climb (%d moved, incumbent %.1f): %s"
               % (seed, n0, n0 + rc, t[2], " (still adding)" if t[5] else "", t[3], 1e3 * t[1], inc, fmt(rel), crc, after[0], fmt(rel2)))
+
+    if a.distinct:
+        print("distinct admission against the plain call, per seed: entries found -> after the call -> real (left by solveSolutionPool), merged away; device ms, median of %d alternating runs" % a.runs)
+        tot = {False: [0, 0], True: [0, 0]}
+        for seed in range(a.seeds):
+            w = solved(seed)
+            n0 = w.solutionPoolCount()
+            row, dev = {}, {False: [], True: []}
+            for run in range(a.runs + 1):
+                for mode in (False, True):
+                    if run or mode:   # (every call starts from the pool as found: a fresh solve of the same wrapper restores it)
+                        assert w.callCplex() == P.OptimizationStatus.SUCCESS
+                    rc, added = w.exploreSolutionPool(a.passes, a.max_rel, distinct=mode)
+                    assert rc >= 0, (seed, mode, rc)
+                    if run > 0 and n0 < a.capacity:   # (run 0: the warm-up of both calls; a full pool: no device work)
+                        dev[mode].append(timing(w)[1])
+                    if run == a.runs:
+                        n1 = w.solutionPoolCount()
+                        w.solveSolutionPool()
+                        row[mode] = (n1, w.solutionPoolCount())
+            for mode in (False, True):
+                tot[mode][0] += row[mode][0] - n0; tot[mode][1] += row[mode][0] - row[mode][1]
+            med = {m: 1e3 * statistics.median(v) if v else 0.0 for m, v in dev.items()}
+            print("seed %2d: %2d found | plain -> %2d -> %2d real, %2d merged, %8.3f ms | distinct -> %2d -> %2d real, %2d merged, %8.3f ms | distinct / plain %s"
+                  % (seed, n0, row[False][0], row[False][1], row[False][0] - row[False][1], med[False], row[True][0], row[True][1], row[True][0] - row[True][1], med[True],
+                     "%.2fx" % (med[True] / med[False]) if med[False] > 0 else "-"))
+        print("in all: plain added %d, of which %d merged away; distinct added %d, of which %d merged away" % (tot[False][0], tot[False][1], tot[True][0], tot[True][1]))
+        return
 
     w = solved(a.cost_seed)
     Cn, N, O, L = dims(w)
