@@ -277,6 +277,29 @@ class CplexWrapper {
     added.resize(rc > 0 ? (size_t)rc : 0);
     return rc;
   }
+  // settleDecisions: n decision records solved and re-labelled on the device until their labels stay (miqp_solver_settle_decisions), at most
+  // miqp_gpu_pool_settle_passes() solves each: results[k] the LAST solve of record k, settled[k * D ..] the labels it ran with (all -1 for an entry
+  // of status 1 or 2), solves[k] the number of its solves (0: refused, negative: still moving at the end).  No trajectories are kept: send the
+  // settled rows through solveDecisions for them.
+  int settleDecisions(const std::vector<signed char>& decisions, int n, std::vector<miqp_fixed_result_c>& results, std::vector<signed char>& settled, std::vector<int>& solves, int* best = nullptr) {
+    results.assign(n > 0 ? (size_t)n : 0, miqp_fixed_result_c{2, -1, 0, 0, std::nan(""), std::nan("")});
+    settled.clear(); solves.assign(n > 0 ? (size_t)n : 0, 0);
+    int d[6];
+    if (!h_ || n <= 0 || miqp_solver_get_dims(h_, d) != 0) return -1;
+    const size_t D = (size_t)d[0] * d[1] * 6 + (size_t)d[0] * d[4] * d[1] * 5 + (size_t)(d[0] * (d[0] - 1) / 2) * d[1] * 4;
+    if (decisions.size() < D * (size_t)n) return -1;
+    settled.assign(D * (size_t)n, (signed char)-1);
+    return miqp_solver_settle_decisions(h_, decisions.data(), n, results.data(), settled.data(), solves.data(), best);
+  }
+  // exploreSolutionPoolSettled: exploreSolutionPool that admits a neighbour by the signature of its SETTLED labels (miqp_solver_pool_explore_settled):
+  // solveSolutionPool behind it merges away nothing the call added.  added[k].reserved is the number of solves the entry's settling took.
+  int exploreSolutionPoolSettled(std::vector<miqp_pool_explore_c>& added, int max_passes = 4, double max_rel = -1.0) {
+    added.assign((size_t)miqp_gpu_pool_max(), miqp_pool_explore_c{-1, 0, 0, 0, 0, 0, 0, 0, std::nan("")});
+    if (!h_) { added.clear(); return -1; }
+    const int rc = miqp_solver_pool_explore_settled(h_, max_passes, max_rel, added.data(), (int)added.size());
+    added.resize(rc > 0 ? (size_t)rc : 0);
+    return rc;
+  }
   SolutionProperties getSolutionProperties() const { return solutionProperties_; }
   void setDebugOutputPrint(bool v) { print_debug_outputs_ = v; }
   void setDebugOutputFilePath(std::string in) { debugOutputFilePath_ = in; }

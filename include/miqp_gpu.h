@@ -485,6 +485,40 @@ int miqp_solver_canonical_labels(const miqp_solver_t* s, const signed char* deci
  * miqp_solver_last_timing: out[3] and out[4] include pass 0's nodes (one per kept entry) and their iterations; out[2] does not count pass 0. */
 int miqp_solver_pool_explore_distinct(miqp_solver_t* s, int max_passes, double max_rel, miqp_pool_explore_c* out, int cap);
 
+/* ---- settled labels on the device, and the explore that admits only manoeuvres the refinement will keep.  Opt-in and new: the calls
+ * above stay what they are. ----
+ * One labelling is not where miqp_solver_pool_solve ends: it labels and solves again, up to miqp_gpu_pool_settle_passes() times, until the labels
+ * stay, and a record solved under the labels of its own solution can slide to another solution.  SETTLING a record is that iteration for one
+ * record.  r0: its D decision bytes, completed to a fix record as miqp_solver_solve_decisions completes them.  For p = 1 .. passes: r(p - 1) is
+ * solved through the fixed-batch chain at the tight tolerance; an answer of status != 0 ends it - the record has no settled labels; its solution is
+ * labelled as miqp_solver_canonical_decisions labels it, to c(p); when c(p) is r(p - 1) byte for byte over the whole record, step 0 included, it is
+ * SETTLED; else r(p) = c(p).  A record still moving behind the last solve keeps the labels that solve ran with (never seen on any instance).
+ * miqp_solver_settle_decisions settles n records on the device, every round over the records that still move: contract, the refusals decided before
+ * a device is touched and the return codes are those of miqp_solver_canonical_decisions.  out[k] is the LAST solve of record k; settled[k * D ..]
+ * the D bytes of the labels that solve ran with - all -1 for an entry of status 1 or 2, and for a record with an undecided region byte at a step
+ * >= 1, whose labels are all -1 after the first solve and stay so; solves[k] is 0 for a refused record, else the number of its solves, 1 ..
+ * passes, and -passes for a record still moving at the end (miqp_solver_last_error then says so; it is cleared at the start of the call).  best as
+ * in miqp_solver_solve_decisions, over the last results.  The call keeps NO state for miqp_solver_fixed_batch_record and drops what the handle held:
+ * a caller who wants the trajectories sends `settled` through miqp_solver_solve_decisions and receives `out` again bit for bit.
+ * miqp_solver_last_timing: out[0] the whole call, out[1] of which on the device, out[2] launch groups, out[3] solves in all, out[4] their
+ * iterations, out[5] 1 when a record still moved at the end.  No reference counterpart. */
+int miqp_solver_settle_decisions(miqp_solver_t* s, const signed char* decisions, int n, miqp_fixed_result_c* out, signed char* settled /* [n * D] */, int* solves /* [n] */, int* best);
+/* the number of solves after which settling and the refinement of miqp_solver_pool_solve stop (6).  Pure host code: no device */
+int miqp_gpu_pool_settle_passes(void);
+/* miqp_solver_pool_explore with SETTLED admission: arguments, return codes, refusals (those of the distinct call included), stopping rules, cap,
+ * visiting order, "the pool is untouched on every failure" and what is stored - an added entry is its parent's bytes behind its jump, objective and
+ * iterations are its first solve's - are that call's.  Differences:
+ * pass 0 settles the kept entries' own records; per place the call keeps, beside the signature, the SETTLED signature - the signature under the
+ * handle's filter of the entry's settled labels; a kept entry without settled labels has none and matches nothing.  In every pass the neighbours
+ * that are feasible, within the cost cap and of a signature that is new against the pool at the start of the pass are settled - those whose first
+ * labels are their own record with that one solve - and a neighbour is admitted while a place is free when its signature is not in the pool, it has
+ * a settled signature and that one is not among the settled signatures of the pool; the entries admitted earlier in the pass are included in both.
+ * The canonical signature of the distinct call takes no part.  miqp_solver_pool_solve behind the call merges away nothing the call added.
+ * out[k].reserved is the number of solves the entry's settling took (1 .. miqp_gpu_pool_settle_passes()); in the other two calls it stays 0.
+ * miqp_solver_last_timing: out[3] and out[4] count every solve of the call - pass 0, the neighbours, the settle rounds - and their iterations;
+ * out[2] does not count pass 0. */
+int miqp_solver_pool_explore_settled(miqp_solver_t* s, int max_passes, double max_rel, miqp_pool_explore_c* out, int cap);
+
 /* 1 when instances of this shape (NrCars, N) have the dual active-set launches - one or two cars, a horizon of up to 20 steps - else 0 (their node
  * relaxations are interior point solves).  Pure host code: no device is needed or touched.  A call switches the launches off with MIQP_AS=0 */
 int miqp_gpu_has_active_set(int num_cars, int num_steps);

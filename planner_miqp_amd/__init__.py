@@ -9,5 +9,5 @@ from .ctypes_types import ModelParameters, RawResults, Certificate, CertificateC
 from .wrapper import (CplexWrapper, OptimizationStatus, SolutionProperties, WarmstartType, ParameterSource,  # noqa: F401
                       solve_batch, prepare_batch, materialize_results, certify_batch, certify_last_timing, load_library, library_path, build_library,
                       has_active_set, fixed_batch_chunk, pool_max, solve_fixed_multi, solve_solution_pools, pool_signature, pool_moves, pool_moves_max,
-                      improve_solution_pools, pool_improve_plan, pool_jumps,
+                      improve_solution_pools, pool_improve_plan, pool_jumps, pool_settle_passes,
                       POOL_BY_REGION, POOL_BY_ENVIRONMENT, POOL_BY_OBSTACLE, POOL_BY_CAR_CAR, POOL_EXACT_TIMING)

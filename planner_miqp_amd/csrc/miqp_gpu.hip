@@ -1696,6 +1696,7 @@ bool solve_batch_impl(miqp_solver_t* const* S, int n, int* statuses, const Split
 #include "solution_pool.hip"
 #include "pool_improve.hip"
 #include "pool_label.hip"
+#include "pool_settle.hip"
 #include "pool_explore.hip"
 
 // ================================================================================================

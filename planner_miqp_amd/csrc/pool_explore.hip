@@ -35,6 +35,20 @@
 // an entry's own solution under other labels.  The distinct call solves the kept entries' own records first (pass 0), has pool_label_kernel
 // (pool_label.hip) write the canonical record of every solved node behind its chunk, keeps per place the signature of that record beside the plain
 // one (pool_canon0_kernel) and admits a neighbour only when BOTH signatures are new (pool_admit_distinct_kernel: the same body, one more test).
+//
+// SETTLED admission (miqp_solver_pool_explore_settled; opt-in, both calls above are unchanged): first labels are an intermediate of
+// the iteration the refinement runs, and it merges by the final ones.  The settled call carries every candidate of a pass to ITS fixed point
+// (pool_settle.hip) and admits by the signature of the settled labels, so that miqp_solver_pool_solve behind it merges away nothing it added:
+//   pass 0                     the kept entries' own records through the settle rounds; pool_settled0_kernel writes, per kept entry, the plain
+//                              signature and the signature of its settled labels (none when its own QP is not feasible: it never matches)
+//   pool_settle_pick_kernel    behind a pass's chain and labels, one wavefront per neighbour: a CANDIDATE is feasible, within the cost cap, and its
+//                              plain signature - of the parent's bytes behind the jump, rebuilt in LDS as the admission does - is new against
+//                              the pool at the START of the pass.  The pool only grows within a pass, so every neighbour the serial admission can
+//                              admit is a candidate.  A candidate whose first labels are its record is settled with one solve; the others enter
+//                              the settle rounds (round 2 on) under their first labels
+//   pool_admit_settled_kernel  the admission body with the settled test in place of the canonical one: a candidate is admitted when its plain
+//                              signature is new and the signature of its settled labels is new among the settled signatures of the pool, the
+//                              entries admitted earlier in the pass included; `reserved` of its record carries the solves its settling took
 #pragma once
 
 namespace {
@@ -120,6 +134,11 @@ struct PoolExploreArgs {
   // the labelled record of every neighbour of the pass (pool_label_kernel, chunk by chunk)
   signed char* csig;              // [places]
   const signed char* lab;         // [NB_MAX]
+  // the settled call only (miqp_solver_pool_explore_settled): csig holds the signatures of the SETTLED labels, lab the settled labels of every
+  // neighbour of the pass (PoolSettleArgs::cur); a place has a settled signature when has_sig says so; fin and solves: the last answer of every
+  // neighbour's settling and the number of its solves (0: no candidate)
+  int* has_sig;                   // [places]
+  const miqp_fixed_result_c* fin; const int* solves;   // [NB_MAX]
 };
 
 __global__ __launch_bounds__(64) void pool_jumps_kernel(const PoolExploreArgs E) {
@@ -168,10 +187,14 @@ constexpr double POOL_ADMIT_NONE = 1e308;   // in the staged objectives: not fea
 
 // The admission of a pass.  DISTINCT (miqp_solver_pool_explore_distinct): a candidate of a new signature is admitted only when the signature of its
 // CANONICAL record - the labels of its own solution, E.lab - is new as well, among the canonical signatures of everything in the pool (E.csig: the
-// kept entries' from pass 0, the admitted ones' appended here); a candidate dropped for that takes no place.  Without DISTINCT none of that is compiled
-template <bool DISTINCT>
+// kept entries' from pass 0, the admitted ones' appended here); a candidate dropped for that takes no place.  Without DISTINCT none of that is compiled.
+// SETTLED (miqp_solver_pool_explore_settled; MODE 2, which includes the code of DISTINCT): E.lab are the settled labels, E.csig the signatures of
+// those, and a neighbour without settled labels - no candidate of the pick kernel, or not feasible at its last solve - is passed over
+constexpr int POOL_ADMIT_PLAIN = 0, POOL_ADMIT_DISTINCT = 1, POOL_ADMIT_SETTLED = 2;
+template <int MODE>
 __device__ inline void pool_admit_body(const PoolExploreArgs& E, int nb_max, uint4* pa_lds) {
   const PoolImproveArgs& A = E.A;
+  constexpr bool DISTINCT = MODE != POOL_ADMIT_PLAIN, SETTLED = MODE == POOL_ADMIT_SETTLED;
   const int lane = threadIdx.x, chunks = A.fixlen >> 4, K = A.m;
   uint4* const cand = pa_lds; uint4* const csig = cand + chunks;
   uint4* const ccan = csig + chunks; uint4* const ccsg = ccan + chunks;   // DISTINCT: the candidate's labelled record and its signature
@@ -224,19 +247,25 @@ __device__ inline void pool_admit_body(const PoolExploreArgs& E, int nb_max, uin
     bool known = false;
     for (int j = 0; j < n && !known; ++j) known = pool_cmp(csig, sig + (size_t)j * chunks, chunks, lane) == 0;
     if (known) continue;
+    int solves = 0;
+    if (SETTLED) {
+      solves = E.solves[bg];
+      if (solves == 0 || E.fin[bg].status != 0) continue;   // (uniform: no settled labels)
+    }
     if (DISTINCT) {
       const uint4* const lab = (const uint4*)E.lab + (size_t)bg * chunks; uint4* const can = (uint4*)E.csig;
       for (int c = lane; c < chunks; c += 64) { ccan[c] = lab[c]; ccsg[c] = make_uint4(~0u, ~0u, ~0u, ~0u); }
       pool_admit_signature(E, ccan, ccsg, fam, lane);
-      for (int j = 0; j < n && !known; ++j) known = pool_cmp(ccsg, can + (size_t)j * chunks, chunks, lane) == 0;
+      for (int j = 0; j < n && !known; ++j) known = (!SETTLED || E.has_sig[j]) && pool_cmp(ccsg, can + (size_t)j * chunks, chunks, lane) == 0;
       if (known) continue;   // (an alias of an entry: the same solution under labels of another signature)
       for (int c = lane; c < chunks; c += 64) can[(size_t)n * chunks + c] = ccsg[c];
+      if (SETTLED && lane == 0) E.has_sig[n] = 1;
     }
     for (int c = lane; c < chunks; c += 64) { pool[(size_t)n * chunks + c] = cand[c]; sig[(size_t)n * chunks + c] = csig[c]; }
     if (lane == 0) {
       A.cur_obj[n] = bo;
       miqp_pool_explore_c o;
-      o.parent = e; o.pass = E.pass; o.first = mv.x; o.stride = mv.y; o.count = mv.z; o.value = mv.w; o.iterations = A.res[bg].iterations; o.reserved = 0; o.objective = bo;
+      o.parent = e; o.pass = E.pass; o.first = mv.x; o.stride = mv.y; o.count = mv.z; o.value = mv.w; o.iterations = A.res[bg].iterations; o.reserved = SETTLED ? abs(solves) : 0; o.objective = bo;
       E.out[added] = o;
     }
     n++; added++;
@@ -248,12 +277,76 @@ __device__ inline void pool_admit_body(const PoolExploreArgs& E, int nb_max, uin
 
 __global__ __launch_bounds__(64) void pool_admit_kernel(const PoolExploreArgs E, int nb_max) {
   extern __shared__ uint4 pa_lds[];   // the candidate's record, its signature; behind them one objective per neighbour of the pass
-  pool_admit_body<false>(E, nb_max, pa_lds);
+  pool_admit_body<POOL_ADMIT_PLAIN>(E, nb_max, pa_lds);
 }
 
 __global__ __launch_bounds__(64) void pool_admit_distinct_kernel(const PoolExploreArgs E, int nb_max) {
   extern __shared__ uint4 pa_lds[];   // the candidate's record, its signature, its labelled record, that one's signature; behind them the objectives
-  pool_admit_body<true>(E, nb_max, pa_lds);
+  pool_admit_body<POOL_ADMIT_DISTINCT>(E, nb_max, pa_lds);
+}
+
+__global__ __launch_bounds__(64) void pool_admit_settled_kernel(const PoolExploreArgs E, int nb_max) {
+  extern __shared__ uint4 pa_lds[];   // the candidate's record, its signature, its settled labels, their signature; behind them the objectives
+  pool_admit_body<POOL_ADMIT_SETTLED>(E, nb_max, pa_lds);
+}
+
+// Behind the chain and the labels of a pass of the settled call, one wavefront per neighbour: is it a candidate (see the head of the file), and did
+// its labels move.  Writes the neighbour's words of the settle rounds (PoolSettleArgs, by neighbour number): its first labels as the record of
+// round 2, its first answer, 1 solve (0: no candidate), the moved flag.  first_lab: the labelled records of the pass's neighbours
+__global__ __launch_bounds__(64) void pool_settle_pick_kernel(const PoolExploreArgs E, const PoolSettleArgs S, const signed char* first_lab, int nb_max) {
+  extern __shared__ uint4 pk_lds[];   // the neighbour's record, its signature
+  const PoolImproveArgs& A = E.A;
+  const int g = blockIdx.x, lane = threadIdx.x, chunks = A.fixlen >> 4, K = A.m;
+  const int n0 = min(max(E.state[0], 0), K), total = min(max(A.off[K], 0), nb_max);
+  if (g >= total || g >= S.n) return;
+  uint4* const rec = pk_lds; uint4* const sg = rec + chunks;
+  const int status = A.res[g].status; const double objective = A.res[g].objective;
+  int e = 0;   // off[e] <= g < off[e + 1]: at most 16 places
+  for (int j = 1; j < K; ++j) if (A.off[j] <= g) e = j;
+  const int jm = g - A.off[e];
+  bool cand = status == 0 && objective < POOL_ADMIT_NONE && pool_within_cap(E.obj0, objective, E.max_rel) && jm >= 0 && jm < POOL_MOVES_MAX && e < n0;
+  bool moved = false;   // (cand and moved are uniform over the wavefront)
+  if (cand) {
+    const int fam = A.ent_fam[0];
+    const int4 mv = A.moves[(size_t)e * POOL_MOVES_MAX + jm];
+    const uint4* const pool = (const uint4*)A.cur; const uint4* const sig = (const uint4*)E.sig;
+    for (int c = lane; c < chunks; c += 64) {
+      uint4 v = pool[(size_t)e * chunks + c];
+      for (int k = 0; k < mv.z; ++k) { const int p = mv.x + k * mv.y - c * 16; if ((unsigned)p < 16u) pool_patch_byte(v, p, mv.w); }
+      rec[c] = v; sg[c] = make_uint4(~0u, ~0u, ~0u, ~0u);
+    }
+    pool_admit_signature(E, rec, sg, fam, lane);
+    bool known = false;
+    for (int j = 0; j < n0 && !known; ++j) known = pool_cmp(sg, sig + (size_t)j * chunks, chunks, lane) == 0;
+    cand = !known;
+  }
+  if (cand) {
+    const uint4* const lab = (const uint4*)first_lab + (size_t)g * chunks; uint4* const dst = (uint4*)S.cur + (size_t)g * chunks;
+    bool diff = false;
+    for (int c = lane; c < chunks; c += 64) { const uint4 x = lab[c], y = rec[c]; diff = diff || x.x != y.x || x.y != y.y || x.z != y.z || x.w != y.w; dst[c] = x; }
+    moved = __ballot(diff) != 0ull;
+  }
+  if (lane == 0) { pool_settle_copy_result(S.last + g, A.res + g); S.solves[g] = cand ? 1 : 0; S.moved[g] = moved ? 1 : 0; S.round_it[g] = 0; }
+}
+
+// Pass 0 of the settled call, behind the settle rounds over the kept entries' own records: ONE wavefront writes, per kept entry, its plain signature
+// (the pick kernel of pass 1 compares with it) and the signature of its settled labels, with the word that says whether it has one
+__global__ __launch_bounds__(64) void pool_settled0_kernel(const PoolExploreArgs E) {
+  extern __shared__ uint4 pc_lds[];   // a record, its signature
+  const PoolImproveArgs& A = E.A;
+  const int lane = threadIdx.x, chunks = A.fixlen >> 4, K = A.m;
+  uint4* const rec = pc_lds; uint4* const sg = rec + chunks;
+  const int fam = A.ent_fam[0], n0 = min(max(E.state[0], 0), K);
+  for (int j = 0; j < n0; ++j)
+    for (int settled = 0; settled < 2; ++settled) {
+      const uint4* const src = (settled ? (const uint4*)E.lab : (const uint4*)A.cur) + (size_t)j * chunks;
+      uint4* const dst = (settled ? (uint4*)E.csig : (uint4*)E.sig) + (size_t)j * chunks;
+      __syncthreads();
+      for (int c = lane; c < chunks; c += 64) { rec[c] = src[c]; sg[c] = make_uint4(~0u, ~0u, ~0u, ~0u); }
+      pool_admit_signature(E, rec, sg, fam, lane);
+      for (int c = lane; c < chunks; c += 64) dst[c] = sg[c];
+    }
+  for (int j = lane; j < K; j += 64) E.has_sig[j] = j < n0 && E.fin[j].status == 0 ? 1 : 0;
 }
 
 // Pass 0 of the distinct call, behind the chain and pool_label_kernel over the kept entries' own records: ONE wavefront writes, per kept entry, the
@@ -280,8 +373,10 @@ __global__ __launch_bounds__(64) void pool_canon0_kernel(const PoolExploreArgs E
 // buffers of the call beside the climb's (PoolImproveDev, PoolEntryDev), cached per device (grown, not shrunk)
 struct PoolExploreDev {
   signed char* sig = nullptr; size_t sig_cap = 0; int* state = nullptr; miqp_pool_explore_c* out = nullptr;
+  int* has_sig = nullptr;   // (the settled call's: a place has a settled signature)
   bool ensure(size_t fl) {
     if (!state) HIP_OK(hipMalloc((void**)&state, 4 * sizeof(int)));
+    if (!has_sig) HIP_OK(hipMalloc((void**)&has_sig, MIQP_POOL_MAX * sizeof(int)));
     if (!out) HIP_OK(hipMalloc((void**)&out, MIQP_POOL_MAX * sizeof(miqp_pool_explore_c)));
     if (MIQP_POOL_MAX * fl > sig_cap) {
       if (sig) (void)hipFree(sig);
@@ -313,22 +408,32 @@ struct PoolExploreOut {
 };
 
 // false: HIP error (nothing of the handle has been touched).  n: entries in the pool, K: its places; name: the entry point, for its messages;
-// distinct: pass 0 in front, the labels of every chunk, the admission by both signatures (miqp_solver_pool_explore_distinct)
-bool pool_explore_run(const FixedCall& call, const char* name, bool distinct, int fam, int L, const signed char* fix, int n, int K, double obj0, double max_rel, int max_passes, PoolExploreOut& O) {
+// mode POOL_ADMIT_DISTINCT: pass 0 in front, the labels of every chunk, the admission by both signatures (miqp_solver_pool_explore_distinct);
+// POOL_ADMIT_SETTLED: pass 0 and every pass's candidates through the settle rounds, the admission by the settled signature (.._explore_settled)
+bool pool_explore_run(const FixedCall& call, const char* name, int mode, int fam, int L, const signed char* fix, int n, int K, double obj0, double max_rel, int max_passes, PoolExploreOut& O) {
   DevCtx& X = *call.X; DevBuf& B = X.B; hipStream_t st = X.stream; const Layout& Y = call.Y;
   const size_t fl = (size_t)Y.fixlen;
+  const bool distinct = mode != POOL_ADMIT_PLAIN, settled = mode == POOL_ADMIT_SETTLED;   // (distinct: what both opt-in calls need - labels, pass 0, the second signature)
   PoolImproveDev& R = g_pool_improve_dev[X.device]; PoolEntryDev& G = g_pool_entry_dev[X.device]; PoolExploreDev& Q = g_pool_explore_dev[X.device];
+  PoolSettleDev& W = g_pool_settle_dev[X.device];
   if (!R.ensure((size_t)Y.N * Y.nz) || !G.ensure(MIQP_POOL_MAX, fl) || !Q.ensure(fl) || (distinct && !Q.ensure_distinct(fl))) return false;
+  if (settled && !W.ensure((size_t)PoolImproveDev::NB_MAX, fl)) return false;
   const PoolDims dims = pool_dims(Y);
   const size_t jump_lds = fl + (size_t)pool_jump_units(dims) * sizeof(int), admit_lds = (distinct ? 4 : 2) * fl + (size_t)PoolImproveDev::NB_MAX * sizeof(double);
   if (std::max(jump_lds, admit_lds) > POOL_EXPLORE_LDS_MAX) {
-    O.err = std::string(name) + (distinct ? ": the fix record of this shape does not fit the LDS of pool_admit_distinct_kernel four times beside the objectives of a pass"
+    O.err = std::string(name) + (settled ? ": the fix record of this shape does not fit the LDS of pool_admit_settled_kernel four times beside the objectives of a pass"
+                                 : distinct ? ": the fix record of this shape does not fit the LDS of pool_admit_distinct_kernel four times beside the objectives of a pass"
                                           : ": the fix record of this shape does not fit the LDS of pool_admit_kernel twice beside the objectives of a pass");
     std::fprintf(stderr, "[miqp_gpu] %s (%zu bytes)\n", O.err.c_str(), std::max(jump_lds, admit_lds)); return false;
   }
   if (distinct && !pool_label_fits(Y, name, O.err)) return false;
   HIP_OK(hipFuncSetAttribute((const void*)pool_jumps_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)jump_lds));
-  if (distinct) {
+  if (settled) {
+    HIP_OK(hipFuncSetAttribute((const void*)pool_admit_settled_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)admit_lds));
+    HIP_OK(hipFuncSetAttribute((const void*)pool_settle_pick_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * fl)));
+    HIP_OK(hipFuncSetAttribute((const void*)pool_settled0_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * fl)));
+    if (!pool_label_set_lds(Y)) return false;
+  } else if (distinct) {
     HIP_OK(hipFuncSetAttribute((const void*)pool_admit_distinct_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)admit_lds));
     HIP_OK(hipFuncSetAttribute((const void*)pool_canon0_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * fl)));
     if (!pool_label_set_lds(Y)) return false;
@@ -351,7 +456,9 @@ bool pool_explore_run(const FixedCall& call, const char* name, bool distinct, in
   A.ent_inst = G.ent_inst; A.ent_fam = G.ent_fam; A.off = G.off; A.batch_inst = B.batch_inst;
   A.dims = dims; A.fixlen = (int)fl; A.m = K;   // (every place of the pool is an entry of the kernels: a free one is not expanded and has no jumps)
   E.L = L; E.sig = Q.sig; E.state = Q.state; E.out = Q.out; E.obj0 = obj0; E.max_rel = max_rel; E.pass = 0;
-  E.csig = distinct ? Q.csig : nullptr; E.lab = distinct ? Q.lab : nullptr;
+  E.csig = distinct ? Q.csig : nullptr; E.lab = settled ? W.cur : distinct ? Q.lab : nullptr;
+  E.has_sig = Q.has_sig; E.fin = settled ? W.last : nullptr; E.solves = settled ? W.solves : nullptr;
+  PoolSettleTally tally;   // (the settled call's: the solves of its settle rounds and their iterations)
   // `total` neighbours of a pass through the chain, a chunk at a time, as the climb sends them (no segments, the trajectories written over)
   auto solve_nodes = [&](int total) -> bool {
     for (int c0 = 0; c0 < total; c0 += FB_CHUNK) {
@@ -366,7 +473,8 @@ bool pool_explore_run(const FixedCall& call, const char* name, bool distinct, in
   // behind a pass (admit: not in front of the first one): the jumps of the next one, and what the host needs of both
   std::vector<int> cnt(MIQP_POOL_MAX); int state[4] = {n, 0, 0, 0}; std::vector<miqp_pool_explore_c> rec(MIQP_POOL_MAX);
   auto finish_pass = [&](bool admit) -> bool {
-    if (admit && distinct) hipLaunchKernelGGL(pool_admit_distinct_kernel, dim3(1), dim3(64), admit_lds, st, E, (int)PoolImproveDev::NB_MAX);
+    if (admit && settled) hipLaunchKernelGGL(pool_admit_settled_kernel, dim3(1), dim3(64), admit_lds, st, E, (int)PoolImproveDev::NB_MAX);
+    else if (admit && distinct) hipLaunchKernelGGL(pool_admit_distinct_kernel, dim3(1), dim3(64), admit_lds, st, E, (int)PoolImproveDev::NB_MAX);
     else if (admit) hipLaunchKernelGGL(pool_admit_kernel, dim3(1), dim3(64), admit_lds, st, E, (int)PoolImproveDev::NB_MAX);
     hipLaunchKernelGGL(pool_jumps_kernel, dim3(K), dim3(64), jump_lds, st, E);
     hipLaunchKernelGGL(pool_offsets_kernel, dim3(1), dim3(256), 0, st, A);
@@ -379,8 +487,20 @@ bool pool_explore_run(const FixedCall& call, const char* name, bool distinct, in
     float ms = 0.0f; (void)hipEventElapsedTime(&ms, X.ev0, X.ev1); O.dev_ms += ms;
     return true;
   };
+  // the settled call, behind a pass's chain and labels: the candidates, the live list of those whose labels moved, their rounds from the second on
+  auto settle_pass = [&](int total) -> bool {
+    const PoolSettleArgs S = pool_settle_args(W, B, Y, total);
+    hipLaunchKernelGGL(pool_settle_pick_kernel, dim3(total), dim3(64), 2 * fl, st, E, S, (const signed char*)Q.lab, (int)PoolImproveDev::NB_MAX);
+    HIP_OK(hipGetLastError());
+    int live = 0;
+    return pool_settle_compact(X, S, live, tally) && pool_settle_rounds(call, Bp, S, R.Z, 2, live, tally);
+  };
   HIP_OK(hipEventRecord(X.ev0, st));
-  if (distinct) {   // pass 0, as in the climb: the kept entries' own records through the chain, their labels, the signatures of those
+  if (settled) {   // pass 0: the kept entries' own records to their fixed points, the signatures of both kinds
+    if (!pool_settle_records(call, Bp, pool_settle_args(W, B, Y, n), R.Z, G.cur, true, tally)) return false;
+    hipLaunchKernelGGL(pool_settled0_kernel, dim3(1), dim3(64), 2 * fl, st, E);
+    HIP_OK(hipGetLastError());
+  } else if (distinct) {   // pass 0, as in the climb: the kept entries' own records through the chain, their labels, the signatures of those
     hipLaunchKernelGGL(pool_neighbour_kernel, dim3((n + 3) / 4), dim3(256), 0, st, A, 0, n, 1);
     HIP_OK(hipGetLastError());
     if (!fixed_chunk(X, Bp, Y, call.dev(), 1, FixedChunk{n, 0, R.res, R.Z}) || !pool_label_chunk(X, Y, 1, n, R.res, R.Z, Q.lab)) return false;
@@ -388,7 +508,7 @@ bool pool_explore_run(const FixedCall& call, const char* name, bool distinct, in
     HIP_OK(hipGetLastError());
   }
   if (!finish_pass(false)) return false;
-  if (distinct) { O.neighbours += n; O.iterations += state[2]; }
+  if (distinct && !settled) { O.neighbours += n; O.iterations += state[2]; }
   int have = n;
   for (;;) {
     long total = 0;
@@ -396,7 +516,7 @@ bool pool_explore_run(const FixedCall& call, const char* name, bool distinct, in
     if (total == 0 || total > PoolImproveDev::NB_MAX || O.passes == max_passes || have >= K) break;
     E.pass = O.passes + 1;
     HIP_OK(hipEventRecord(X.ev0, st));
-    if (!solve_nodes((int)total) || !finish_pass(true)) return false;
+    if (!solve_nodes((int)total) || (settled && !settle_pass((int)total)) || !finish_pass(true)) return false;
     if (state[0] != have + state[1] || state[1] < 0 || state[0] > K) { std::fprintf(stderr, "[miqp_gpu] %s: %d entries behind %d, %d admitted\n", name, state[0], have, state[1]); return false; }
     O.passes++; O.neighbours += total; O.iterations += state[2];
     for (int k = 0; k < state[1]; ++k) O.added.push_back(rec[k]);
@@ -404,6 +524,7 @@ bool pool_explore_run(const FixedCall& call, const char* name, bool distinct, in
     O.still_adding = state[1] > 0 && O.passes == max_passes;
     if (state[1] == 0) break;
   }
+  O.neighbours += tally.solves; O.iterations += tally.iterations;
   O.fix.resize((size_t)have * fl); O.obj.resize(have);
   HIP_OK(hipMemcpy(O.fix.data(), G.cur, (size_t)have * fl, hipMemcpyDeviceToHost));
   HIP_OK(hipMemcpy(O.obj.data(), G.cur_obj, (size_t)have * sizeof(double), hipMemcpyDeviceToHost));
@@ -432,8 +553,8 @@ int miqp_gpu_pool_jumps(int cars, int steps, int obstacles, int max_lines, int f
 
 namespace {
 
-// the two explore entries: what they refuse, the run, what the handle keeps
-int pool_explore_entry(miqp_solver_t* s, const char* name, bool distinct, int max_passes, double max_rel, miqp_pool_explore_c* out, int cap) {
+// the three explore entries: what they refuse, the run, what the handle keeps
+int pool_explore_entry(miqp_solver_t* s, const char* name, int mode, int max_passes, double max_rel, miqp_pool_explore_c* out, int cap) {
   if (s) s->err.clear();   // (miqp_solver_last_error speaks of this call from here on)
   if (!s || !s->has_inst || !out || cap < 0 || max_rel != max_rel) return -1;
   if (s->pool_fam < 1 || s->pool_fam >= POOL_FAM_TIMING || !(s->pool_fam & (POOL_FAM_OBSTACLE | POOL_FAM_CAR_CAR))) return -2;
@@ -450,7 +571,7 @@ int pool_explore_entry(miqp_solver_t* s, const char* name, bool distinct, int ma
   FixedCall call;
   if (call.open(one, 1, Y) != 0) return -3;
   PoolExploreOut O;
-  if (!pool_explore_run(call, name, distinct, s->pool_fam, s->inst.L, s->pool_fix.data(), n, K, s->pool_obj[0], max_rel, max_passes, O)) {
+  if (!pool_explore_run(call, name, mode, s->pool_fam, s->inst.L, s->pool_fix.data(), n, K, s->pool_obj[0], max_rel, max_passes, O)) {
     (void)hipStreamSynchronize(call.X->stream); if (!O.err.empty()) s->err = O.err; return -3;
   }
   const int added = (int)O.added.size();
@@ -475,11 +596,15 @@ int pool_explore_entry(miqp_solver_t* s, const char* name, bool distinct, int ma
 extern "C" {
 
 int miqp_solver_pool_explore(miqp_solver_t* s, int max_passes, double max_rel, miqp_pool_explore_c* out, int cap) {
-  return pool_explore_entry(s, "miqp_solver_pool_explore", false, max_passes, max_rel, out, cap);
+  return pool_explore_entry(s, "miqp_solver_pool_explore", POOL_ADMIT_PLAIN, max_passes, max_rel, out, cap);
 }
 
 int miqp_solver_pool_explore_distinct(miqp_solver_t* s, int max_passes, double max_rel, miqp_pool_explore_c* out, int cap) {
-  return pool_explore_entry(s, "miqp_solver_pool_explore_distinct", true, max_passes, max_rel, out, cap);
+  return pool_explore_entry(s, "miqp_solver_pool_explore_distinct", POOL_ADMIT_DISTINCT, max_passes, max_rel, out, cap);
+}
+
+int miqp_solver_pool_explore_settled(miqp_solver_t* s, int max_passes, double max_rel, miqp_pool_explore_c* out, int cap) {
+  return pool_explore_entry(s, "miqp_solver_pool_explore_settled", POOL_ADMIT_SETTLED, max_passes, max_rel, out, cap);
 }
 
 }  // extern "C"

@@ -132,6 +132,10 @@ def load_library():
     L.miqp_solver_pool_explore_distinct.restype = C.c_int; L.miqp_solver_pool_explore_distinct.argtypes = [vp, C.c_int, C.c_double, C.POINTER(PoolExploreC), C.c_int]
     L.miqp_solver_canonical_decisions.restype = C.c_int
     L.miqp_solver_canonical_decisions.argtypes = [vp, C.POINTER(C.c_byte), C.c_int, C.POINTER(FixedResultC), C.POINTER(C.c_byte), C.POINTER(C.c_int)]
+    L.miqp_solver_settle_decisions.restype = C.c_int
+    L.miqp_solver_settle_decisions.argtypes = [vp, C.POINTER(C.c_byte), C.c_int, C.POINTER(FixedResultC), C.POINTER(C.c_byte), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.miqp_solver_pool_explore_settled.restype = C.c_int; L.miqp_solver_pool_explore_settled.argtypes = [vp, C.c_int, C.c_double, C.POINTER(PoolExploreC), C.c_int]
+    L.miqp_gpu_pool_settle_passes.restype = C.c_int; L.miqp_gpu_pool_settle_passes.argtypes = []
     L.miqp_solver_canonical_labels.restype = C.c_int
     L.miqp_solver_canonical_labels.argtypes = [vp, C.POINTER(C.c_byte), c_double_p, C.c_int, C.c_int, C.POINTER(C.c_byte)]
     L.miqp_solver_solve_fixed_multi.restype = C.c_int
@@ -177,7 +181,8 @@ EXPORTED_SYMBOLS = ["miqp_solver_create", "miqp_solver_destroy", "miqp_solver_se
                     "miqp_gpu_pool_moves", "miqp_gpu_pool_moves_max", "miqp_gpu_pool_improve_size", "miqp_solver_solve_decisions", "miqp_solver_pool_improve",
                     "miqp_solver_pool_improve_multi", "miqp_gpu_pool_improve_plan",
                     "miqp_gpu_pool_jumps", "miqp_gpu_pool_explore_size", "miqp_solver_pool_explore",
-                    "miqp_solver_canonical_decisions", "miqp_solver_canonical_labels", "miqp_solver_pool_explore_distinct"]
+                    "miqp_solver_canonical_decisions", "miqp_solver_canonical_labels", "miqp_solver_pool_explore_distinct",
+                    "miqp_solver_settle_decisions", "miqp_solver_pool_explore_settled", "miqp_gpu_pool_settle_passes"]
 
 
 # a row of CplexWrapper.launchPlan (NodeLaunch in csrc/miqp_gpu.hip)
@@ -259,6 +264,11 @@ def pool_jumps(cars, steps, obstacles, max_lines, families, decisions):
 def pool_max():
     """largest capacity CplexWrapper.setSolutionPool accepts (a constant of the built library; needs no device)"""
     return int(load_library().miqp_gpu_pool_max())
+
+
+def pool_settle_passes():
+    """the number of solves after which settleDecisions and the refinement of solveSolutionPool stop (miqp_gpu_pool_settle_passes)"""
+    return int(load_library().miqp_gpu_pool_settle_passes())
 
 
 def fixed_batch_chunk():
@@ -684,7 +694,7 @@ class CplexWrapper:
         a = np.frombuffer(out, dtype=np.dtype([("before", "<f8"), ("after", "<f8"), ("moves", "<i4"), ("status", "<i4")]), count=m)
         return rc, a["before"].copy(), a["after"].copy(), a["moves"].copy(), a["status"].copy()
 
-    def exploreSolutionPool(self, max_passes=4, max_rel=-1.0, distinct=False):
+    def exploreSolutionPool(self, max_passes=4, max_rel=-1.0, distinct=False, settled=False):
         """the free places of a FILTERED pool filled with neighbouring manoeuvre classes in one device-resident loop (miqp_solver_pool_explore;
         IloCplex::populate for a CPLEX user): pass 1 solves every jump of pool_jumps of every kept entry at the tight tolerance, pass p > 1 those of
         the entries pass p - 1 added; the best feasible neighbour of every class the pool does not hold yet is appended while a place is free.
@@ -694,13 +704,18 @@ class CplexWrapper:
         (parent, pass, first, stride, count, value, iterations, objective; empty for rc <= 0).  Old entries keep their bytes and places.  A
         refined pool is dropped: call solveSolutionPool afterwards.
         ``distinct`` (miqp_solver_pool_explore_distinct): a neighbour is admitted only when the canonical labels of its own solution have a new
-        signature as well, so an entry's solution under other labels takes no place; the timing then counts pass 0, the kept entries' own solves."""
+        signature as well, so an entry's solution under other labels takes no place; the timing then counts pass 0, the kept entries' own solves.
+        ``settled`` (miqp_solver_pool_explore_settled): every candidate is solved and re-labelled until its labels stay, as solveSolutionPool
+        does, and admitted by the signature of those settled labels, so solveSolutionPool behind the call merges away nothing it added; the
+        dicts then carry ``solves``, the solves the entry's settling took, and the timing counts every solve.  Not together with ``distinct``."""
+        if distinct and settled:
+            raise ValueError("distinct and settled are two admissions: choose one")
         n = pool_max()
         out = (PoolExploreC * n)()
-        call = self._L.miqp_solver_pool_explore_distinct if distinct else self._L.miqp_solver_pool_explore
+        call = self._L.miqp_solver_pool_explore_settled if settled else self._L.miqp_solver_pool_explore_distinct if distinct else self._L.miqp_solver_pool_explore
         rc = int(call(self._h, int(max_passes), float(max_rel), out, n))
         return rc, [dict(parent=o.parent, **{"pass": o.pass_}, first=o.first, stride=o.stride, count=o.count, value=o.value, iterations=o.iterations,
-                         objective=float(o.objective)) for o in out[:max(rc, 0)]]
+                         objective=float(o.objective), **({"solves": o.reserved} if settled else {})) for o in out[:max(rc, 0)]]
 
     def solveDecisions(self, decisions):
         """the continuous QPs of many DECISION records of this wrapper's instance in one device call (miqp_solver_solve_decisions): ``decisions`` is
@@ -744,6 +759,22 @@ class CplexWrapper:
         rc = int(self._L.miqp_solver_canonical_decisions(self._h, d.ctypes.data_as(bp), n, out, canon.ctypes.data_as(bp), C.byref(best)))
         a = np.frombuffer(out, dtype=_FIXED_RESULT_DTYPE, count=n)
         return (rc, a["status"].copy(), a["objective"].copy(), a["violation"].copy(), a["iterations"].copy(), a["route"].copy(), best.value, canon[:n])
+
+    def settleDecisions(self, decisions):
+        """decision records solved and re-labelled on the device until their labels stay (miqp_solver_settle_decisions), at most
+        pool_settle_passes() solves each: returns the tuple of solveDecisions - of every record's LAST solve - an int8 array [n, D] - row k the
+        labels that solve ran with; all -1 for an entry of status 1 or 2 - and an int32 array [n], the solves of every record (0: refused,
+        negative: still moving at the end).  fixedBatchRecord does not work behind it: send the settled rows through solveDecisions."""
+        d, _ = self._decision_array(decisions)
+        n = d.shape[0]
+        out = (FixedResultC * max(n, 1))()
+        settled = np.full((max(n, 1), d.shape[1]), -1, dtype=np.int8)
+        solves = np.zeros(max(n, 1), dtype=np.int32)
+        best = C.c_int(-1)
+        bp = C.POINTER(C.c_byte)
+        rc = int(self._L.miqp_solver_settle_decisions(self._h, d.ctypes.data_as(bp), n, out, settled.ctypes.data_as(bp), solves.ctypes.data_as(C.POINTER(C.c_int)), C.byref(best)))
+        a = np.frombuffer(out, dtype=_FIXED_RESULT_DTYPE, count=n)
+        return (rc, a["status"].copy(), a["objective"].copy(), a["violation"].copy(), a["iterations"].copy(), a["route"].copy(), best.value, settled[:n], solves[:n])
 
     def canonicalLabels(self, decisions, trajectories, via=0):
         """the canonical labels of decision records [n, D] at given trajectories [n, NumSteps * 8 * NumCars], on the host

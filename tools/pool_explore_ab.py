@@ -2,7 +2,7 @@
 """The step of a filtered solution pool across manoeuvre classes (miqp_solver_pool_explore): what it adds, and what it costs against its host replay.
 
   python tools/pool_explore_ab.py [--cfg cfg4] [--seeds 16] [--gap 1e-4] [--capacity 16] [--filter 12] [--passes 4] [--max-rel -1] [--climb 8]
-                                  [--cost-seed 7] [--runs 7] [--distinct]
+                                  [--cost-seed 7] [--runs 7] [--distinct] [--settled] [--as-found]
 
 Quality: per seed one solve with the filtered pool and one exploreSolutionPool(passes, max_rel) - the entries before and after, the passes and the
 neighbours solved, the device time, the objectives of the added entries relative to the incumbent (objective / entry 0's found objective - 1) - and
@@ -17,7 +17,10 @@ device; B: summed over its calls).
 --distinct adds, per seed, the explore with distinct admission (miqp_solver_pool_explore_distinct) beside the plain one, each from the
 pool as found: entries after the call, how many of them are real - left by solveSolutionPool - and how many that call merged away; and the device time
 (miqp_solver_last_timing out[1]) of the two calls, median of --runs ALTERNATING runs behind one warm-up of each - in place of the cost comparison with
-the host replay.  Needs an MI355X."""
+the host replay.  The passes run and the solves (miqp_solver_last_timing out[2], out[3]) of every call are printed beside.
+--settled is --distinct with a third set of columns: the explore with settled admission (miqp_solver_pool_explore_settled).
+--as-found prints, per seed, only what solveSolutionPool leaves of the pool AS FOUND, without any explore: "real" of a call less this number is what
+the call added for good, and "merged away" less (found - this number) is what it added in vain.  Needs an MI355X."""
 import argparse
 import ctypes as C
 import os
@@ -42,6 +45,8 @@ def main():
     ap.add_argument("--cost-seed", type=int, default=7)
     ap.add_argument("--runs", type=int, default=7)
     ap.add_argument("--distinct", action="store_true")
+    ap.add_argument("--settled", action="store_true")
+    ap.add_argument("--as-found", action="store_true")
     a = ap.parse_args()
     import numpy as np
     import planner_miqp_amd as P
@@ -67,6 +72,18 @@ def main():
     def fmt(v):
         return " ".join("%+.3f" % x for x in v) if len(v) else "-"
 
+    if a.as_found:
+        print("the pool as found through solveSolutionPool, no explore: %s seeds 0 .. %d, gap %g, capacity %d, filter %d" % (a.cfg, a.seeds - 1, a.gap, a.capacity, a.filter))
+        tot = [0, 0]
+        for seed in range(a.seeds):
+            w = solved(seed)
+            n0 = w.solutionPoolCount()
+            w.solveSolutionPool()
+            tot[0] += n0; tot[1] += w.solutionPoolCount()
+            print("seed %2d: %2d found -> %2d real, %2d merged" % (seed, n0, w.solutionPoolCount(), n0 - w.solutionPoolCount()))
+        print("in all: %d found, %d real, %d merged" % (tot[0], tot[1], tot[0] - tot[1]))
+        return
+
     print("quality: %s seeds 0 .. %d, gap %g, capacity %d, filter %d, max_passes %d, max_rel %g; behind it a climb of %d passes"
           % (a.cfg, a.seeds - 1, a.gap, a.capacity, a.filter, a.passes, a.max_rel, a.climb))
     for seed in range(a.seeds):
@@ -83,32 +100,35 @@ def main():
         print("seed %2d: %2d -> %2d entries, %d passes%s, %5d neighbours, device %8.3f ms | incumbent %.1f | added, relative to it: %s | behind the climb (%d moved, incumbent %.1f): %s"
               % (seed, n0, n0 + rc, t[2], " (still adding)" if t[5] else "", t[3], 1e3 * t[1], inc, fmt(rel), crc, after[0], fmt(rel2)))
 
-    if a.distinct:
-        print("distinct admission against the plain call, per seed: entries found -> after the call -> real (left by solveSolutionPool), merged away; device ms, median of %d alternating runs" % a.runs)
-        tot = {False: [0, 0], True: [0, 0]}
+    if a.distinct or a.settled:
+        modes = ["plain", "distinct"] + (["settled"] if a.settled else [])
+        print("%s admission against the plain call, per seed and call: entries after the call, passes run, solves, real (left by solveSolutionPool), merged away; device ms, median of %d alternating runs"
+              % (" and ".join(modes[1:]), a.runs))
+        tot = {m: [0, 0] for m in modes}
         for seed in range(a.seeds):
             w = solved(seed)
             n0 = w.solutionPoolCount()
-            row, dev = {}, {False: [], True: []}
+            row, dev = {}, {m: [] for m in modes}
             for run in range(a.runs + 1):
-                for mode in (False, True):
-                    if run or mode:   # (every call starts from the pool as found: a fresh solve of the same wrapper restores it)
+                for mode in modes:
+                    if run or mode != modes[0]:   # (every call starts from the pool as found: a fresh solve of the same wrapper restores it)
                         assert w.callCplex() == P.OptimizationStatus.SUCCESS
-                    rc, added = w.exploreSolutionPool(a.passes, a.max_rel, distinct=mode)
+                    rc, added = w.exploreSolutionPool(a.passes, a.max_rel, distinct=mode == "distinct", settled=mode == "settled")
                     assert rc >= 0, (seed, mode, rc)
-                    if run > 0 and n0 < a.capacity:   # (run 0: the warm-up of both calls; a full pool: no device work)
-                        dev[mode].append(timing(w)[1])
+                    t = timing(w) if n0 < a.capacity else [0.0] * 6   # (a full pool: no device work, the timing is still the solve's)
+                    if run > 0 and n0 < a.capacity:   # (run 0: the warm-up of every call)
+                        dev[mode].append(t[1])
                     if run == a.runs:
                         n1 = w.solutionPoolCount()
                         w.solveSolutionPool()
-                        row[mode] = (n1, w.solutionPoolCount())
-            for mode in (False, True):
+                        row[mode] = (n1, w.solutionPoolCount(), int(t[2]), int(t[3]))
+            for mode in modes:
                 tot[mode][0] += row[mode][0] - n0; tot[mode][1] += row[mode][0] - row[mode][1]
             med = {m: 1e3 * statistics.median(v) if v else 0.0 for m, v in dev.items()}
-            print("seed %2d: %2d found | plain -> %2d -> %2d real, %2d merged, %8.3f ms | distinct -> %2d -> %2d real, %2d merged, %8.3f ms | distinct / plain %s"
-                  % (seed, n0, row[False][0], row[False][1], row[False][0] - row[False][1], med[False], row[True][0], row[True][1], row[True][0] - row[True][1], med[True],
-                     "%.2fx" % (med[True] / med[False]) if med[False] > 0 else "-"))
-        print("in all: plain added %d, of which %d merged away; distinct added %d, of which %d merged away" % (tot[False][0], tot[False][1], tot[True][0], tot[True][1]))
+            print("seed %2d: %2d found | " % (seed, n0) + " | ".join(
+                "%s -> %2d, %d passes, %5d solves -> %2d real, %2d merged, %8.3f ms" % (m, row[m][0], row[m][2], row[m][3], row[m][1], row[m][0] - row[m][1], med[m]) for m in modes)
+                + " | " + ", ".join("%s / plain %s" % (m, "%.2fx" % (med[m] / med["plain"]) if med["plain"] > 0 else "-") for m in modes[1:]))
+        print("in all: " + "; ".join("%s added %d, of which %d merged away" % (m, tot[m][0], tot[m][1]) for m in modes))
         return
 
     w = solved(a.cost_seed)
