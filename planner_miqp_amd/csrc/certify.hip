@@ -92,8 +92,8 @@ __global__ __launch_bounds__(CERT_NT) void certify_kernel(const char* __restrict
 struct CertDev {
   hipStream_t s_up = nullptr, s_k = nullptr;
   hipEvent_t ev_up[2] = {}, ev_done[2] = {}, t_up0[2] = {}, t_up1[2] = {}, t_k0[2] = {}, t_k1[2] = {};
-  char* h_stage[2] = {nullptr, nullptr}; char* d_blob[2] = {nullptr, nullptr}; size_t cap = 0;
-  miqp_certificate_c* d_out = nullptr; size_t out_cap = 0;
+  DevArr<char, true> h_stage[2]; DevArr<char> d_blob[2];
+  DevArr<miqp_certificate_c> d_out;
   bool streams = false;
   bool ensure(size_t bytes, size_t n_out) {
     if (!streams) {
@@ -104,28 +104,10 @@ struct CertDev {
       }
       streams = true;
     }
-    if (bytes > cap) {
-      size_t want = (size_t)1 << 20; while (want < bytes) want <<= 1;
-      for (int b = 0; b < 2; ++b) {
-        if (h_stage[b]) (void)hipHostFree(h_stage[b]);
-        if (d_blob[b]) (void)hipFree(d_blob[b]);
-        h_stage[b] = nullptr; d_blob[b] = nullptr;
-      }
-      cap = 0;
-      for (int b = 0; b < 2; ++b) { HIP_OK(hipHostMalloc((void**)&h_stage[b], want, hipHostMallocDefault)); HIP_OK(hipMalloc((void**)&d_blob[b], want)); }
-      cap = want;
-    }
-    if (n_out > out_cap) {
-      if (d_out) (void)hipFree(d_out);
-      d_out = nullptr; out_cap = 0;
-      size_t want = 256; while (want < n_out) want <<= 1;
-      HIP_OK(hipMalloc((void**)&d_out, want * sizeof(miqp_certificate_c)));
-      out_cap = want;
-    }
-    return true;
+    for (int b = 0; b < 2; ++b) if (!h_stage[b].need(bytes, (size_t)1 << 20) || !d_blob[b].need(bytes, (size_t)1 << 20)) return false;
+    return d_out.need(n_out, 256);
   }
 };
-std::map<int, CertDev> g_cert_dev;   // by device ordinal; used under the device lock (DevCtx::mu of lane 0)
 double g_cert_timing[4] = {0, 0, 0, 0};   // of the last certify call of the process: host packing, upload, kernel, whole call (seconds)
 
 struct CertJob { const HostInst* I; const miqp_raw_results_c* r; size_t bytes; };
@@ -162,7 +144,7 @@ bool certify_jobs(int device, const std::vector<CertJob>& jobs, miqp_certificate
     start.push_back(n);
   }
   const int nchunks = (int)need.size();
-  CertDev& G = g_cert_dev[X->device];
+  CertDev& G = call_dev<CertDev>(X->device);
   if (!G.ensure(*std::max_element(need.begin(), need.end()), (size_t)n)) { err = "device or pinned memory for the certificate could not be allocated"; return false; }
   double pack_s = 0.0; float up_ms = 0.0f, k_ms = 0.0f; bool used_buf[2] = {false, false};
   auto harvest = [&](int b) {

@@ -106,74 +106,34 @@ __global__ __launch_bounds__(FB_NT) void fixed_collect_kernel(const FixedCollect
       const int ok = A.batch_ok[k]; const double viol = A.batch_viol[k], obj = R[k].objective;
       if (ok && !(viol > FEAS_TOL) && obj < bo) { bo = obj; bi = k; }
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-      const double oo = __shfl_xor(bo, d, 64); const int oi = __shfl_xor(bi, d, 64);
-      if (oo < bo || (oo == bo && oi < bi)) { bo = oo; bi = oi; }
-    }
+    pool_wave_argmin(bo, bi);
     if (lane == 0) { A.seg_obj[s] = bo; A.seg_idx[s] = (bi == 0x7FFFFFFF || !known) ? -1 : A.base + bi - A.hfirst[inst]; }
   }
 }
 
 // ---------------------------------------------------------------------------------------------------------------- device cache
-// staging, result and per-handle buffers of the fixed calls, cached per device and never taken from the solver's pools (grown, not shrunk).  Each
-// group's capacity is set when all of the group is there: an allocation that failed half-way is taken up from the group's start, nothing is held twice
+// staging, result and per-handle buffers of the fixed calls, cached per device and never taken from the solver's pools (DevArr: grown, not shrunk;
+// the staging and the trajectories exactly as large as the largest call so far).  Used under the device lock (DevCtx::mu of lane 0)
 struct FixedDev {
   hipStream_t s_up = nullptr; hipEvent_t ev_up[2] = {}, ev_taken[2] = {};
-  signed char* h_stage[2] = {nullptr, nullptr}; signed char* d_stage[2] = {nullptr, nullptr}; size_t stage_cap = 0;
-  miqp_fixed_result_c* d_res = nullptr; size_t res_cap = 0;
-  double* d_Z = nullptr; size_t z_cap = 0;
-  int* d_seg = nullptr;   // [FB_CHUNK + 1] the segment table of the chunk in flight (its batch_inst slice is copied into DevBuf::batch_inst)
-  double* d_cobj = nullptr; int* d_hfirst = nullptr; size_t inst_cap = 0;
-  double* d_sobj = nullptr; int* d_sidx = nullptr; size_t seg_cap = 0;
+  DevArr<signed char, true> h_stage[2]; DevArr<signed char> d_stage[2];
+  DevArr<miqp_fixed_result_c> d_res;
+  DevArr<double> d_Z;
+  DevArr<int> d_seg;   // [FB_CHUNK + 1] the segment table of the chunk in flight (its batch_inst slice is copied into DevBuf::batch_inst)
+  DevArr<double> d_cobj; DevArr<int> d_hfirst;
+  DevArr<double> d_sobj; DevArr<int> d_sidx;
   // what open() needs: the per-handle words
-  bool ensure_handles(size_t n_inst) {
-    if (n_inst > inst_cap) {
-      if (d_cobj) (void)hipFree(d_cobj); if (d_hfirst) (void)hipFree(d_hfirst);
-      d_cobj = nullptr; d_hfirst = nullptr; inst_cap = 0;
-      size_t want = 64; while (want < n_inst) want <<= 1;
-      HIP_OK(hipMalloc((void**)&d_cobj, want * sizeof(double))); HIP_OK(hipMalloc((void**)&d_hfirst, want * sizeof(int)));
-      inst_cap = want;
-    }
-    return true;
-  }
+  bool ensure_handles(size_t n_inst) { return d_cobj.need(n_inst, 64) && d_hfirst.need(n_inst, 64); }
   // what fixed_run needs: staging of a chunk, results and trajectories of n nodes, the minima of nsegs segments
   bool ensure_run(size_t stage_bytes, size_t n, size_t z_doubles, size_t nsegs) {
     if (!s_up) {
       HIP_OK(hipStreamCreateWithFlags(&s_up, hipStreamNonBlocking));
       for (int b = 0; b < 2; ++b) { HIP_OK(hipEventCreateWithFlags(&ev_up[b], hipEventDisableTiming)); HIP_OK(hipEventCreateWithFlags(&ev_taken[b], hipEventDisableTiming)); }
     }
-    if (!d_seg) HIP_OK(hipMalloc((void**)&d_seg, (size_t)(FB_CHUNK + 1) * sizeof(int)));
-    if (stage_bytes > stage_cap) {
-      for (int b = 0; b < 2; ++b) { if (h_stage[b]) (void)hipHostFree(h_stage[b]); if (d_stage[b]) (void)hipFree(d_stage[b]); h_stage[b] = nullptr; d_stage[b] = nullptr; }
-      stage_cap = 0;
-      for (int b = 0; b < 2; ++b) { HIP_OK(hipHostMalloc((void**)&h_stage[b], stage_bytes, hipHostMallocDefault)); HIP_OK(hipMalloc((void**)&d_stage[b], stage_bytes)); }
-      stage_cap = stage_bytes;
-    }
-    if (n > res_cap) {
-      if (d_res) (void)hipFree(d_res);
-      d_res = nullptr; res_cap = 0;
-      size_t want = 1024; while (want < n) want <<= 1;
-      HIP_OK(hipMalloc((void**)&d_res, want * sizeof(miqp_fixed_result_c)));
-      res_cap = want;
-    }
-    if (z_doubles > z_cap) {
-      if (d_Z) (void)hipFree(d_Z);
-      d_Z = nullptr; z_cap = 0;
-      HIP_OK(hipMalloc((void**)&d_Z, z_doubles * sizeof(double)));
-      z_cap = z_doubles;
-    }
-    if (nsegs > seg_cap) {
-      if (d_sobj) (void)hipFree(d_sobj); if (d_sidx) (void)hipFree(d_sidx);
-      d_sobj = nullptr; d_sidx = nullptr; seg_cap = 0;
-      size_t want = 128; while (want < nsegs) want <<= 1;
-      HIP_OK(hipMalloc((void**)&d_sobj, want * sizeof(double))); HIP_OK(hipMalloc((void**)&d_sidx, want * sizeof(int)));
-      seg_cap = want;
-    }
-    return true;
+    for (int b = 0; b < 2; ++b) if (!h_stage[b].need(stage_bytes) || !d_stage[b].need(stage_bytes)) return false;
+    return d_seg.need(FB_CHUNK + 1) && d_res.need(n, 1024) && d_Z.need(z_doubles) && d_sobj.need(nsegs, 128) && d_sidx.need(nsegs, 128);
   }
 };
-std::map<int, FixedDev> g_fixed_dev;   // by device ordinal; used under the device lock (DevCtx::mu of lane 0)
 
 // work(k) for k < n on at most 16 host threads (one per `per` items)
 template <class F> void fixed_threads(int n, int per, F work) {
@@ -314,7 +274,7 @@ struct FixedCall {
     });
     return upload() ? 0 : -3;
   }
-  FixedDev& dev() const { return g_fixed_dev[X->device]; }
+  FixedDev& dev() const { return call_dev<FixedDev>(X->device); }
   const double* tabD(int h) const { return D.data() + (size_t)h * Y.dstride; }
   const int* tabT(int h) const { return T.data() + (size_t)h * Y.istride; }
   bool upload() {

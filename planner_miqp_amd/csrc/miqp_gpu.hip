@@ -39,6 +39,28 @@ using namespace miqp;
 
 #define HIP_OK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { std::fprintf(stderr, "[miqp_gpu] %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); return false; } } while (0)
 
+// A device array that grows and never shrinks: what the per-device caches of the calls (certify.hip, fixed_chain.hip, the pool files) are made of.
+// need(n, floor): room for n elements - the capacity becomes floor doubled until it holds n, or exactly n without a floor; `tail` elements more are
+// allocated behind the capacity (the end word of a scan).  The old contents go.  A failure leaves the array empty, and the next call takes it up
+// again.  PINNED: the same in pinned host memory
+template <class T, bool PINNED = false> struct DevArr {
+  T* p = nullptr; size_t cap = 0;
+  operator T*() const { return p; }
+  bool need(size_t n, size_t floor = 0, size_t tail = 0) {
+    if (n <= cap) return true;
+    if (p) (void)(PINNED ? hipHostFree(p) : hipFree(p));
+    p = nullptr; cap = 0;
+    size_t want = floor ? floor : n;
+    while (want < n) want <<= 1;
+    if (PINNED) HIP_OK(hipHostMalloc((void**)&p, (want + tail) * sizeof(T), hipHostMallocDefault));
+    else HIP_OK(hipMalloc((void**)&p, (want + tail) * sizeof(T)));
+    cap = want;
+    return true;
+  }
+};
+// the cache of type D of a device (CertDev, FixedDev, Pool..Dev); the one table that holds them stands behind the includes of their files
+template <class D> D& call_dev(int device);
+
 // caller-independent RawResults record (deep copy target; MIP starts are kept in this form until the solve compiles them)
 struct OwnedResults {
   miqp_raw_results_c r{}; std::vector<std::vector<double>> d; std::vector<std::vector<int>> i;
@@ -374,6 +396,11 @@ struct DevCtx {
     void* q = nullptr;
     if (hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(Tp)) != hipSuccess) { std::fprintf(stderr, "[miqp_gpu] hipMalloc of %zu bytes failed\n", n * sizeof(Tp)); return false; }
     allocs.push_back(q); *p = (Tp*)q; return true;
+  }
+  template <class Tp> void drop(Tp** p) {   // one allocation given back ahead of release()
+    if (!*p) return;
+    for (auto it = allocs.begin(); it != allocs.end(); ++it) if (*it == (void*)*p) { allocs.erase(it); break; }
+    (void)hipFree(*p); *p = nullptr;
   }
   void release() {
     for (void* q : allocs) (void)hipFree(q);
@@ -1690,6 +1717,7 @@ bool solve_batch_impl(miqp_solver_t* const* S, int n, int* statuses, const Split
 }  // namespace
 
 #include "certify.hip"
+#include "pool_blocks.hip"
 #include "fixed_chain.hip"
 #include "fixed_batch.hip"
 #include "as_fixed.hip"
@@ -1698,6 +1726,10 @@ bool solve_batch_impl(miqp_solver_t* const* S, int n, int* statuses, const Split
 #include "pool_label.hip"
 #include "pool_settle.hip"
 #include "pool_explore.hip"
+
+// the caches of the calls above, by device ordinal; used under the device lock (DevCtx::mu of lane 0)
+std::map<int, std::tuple<CertDev, FixedDev, PoolImproveDev, PoolEntryDev, PoolLabelDev, PoolSettleDev, PoolExploreDev>> g_call_devs;
+template <class D> D& call_dev(int device) { return std::get<D>(g_call_devs[device]); }
 
 // ================================================================================================
 //  C ABI

@@ -18,8 +18,8 @@
 // pool_unit_jumps below is that definition, once, for the host (miqp_gpu_pool_jumps) and the device (pool_jumps_kernel).
 //
 // The call, per pass, all on the solver stream (pass 1 expands every kept entry, pass p > 1 the entries pass p - 1 added):
-//   pool_jumps_kernel      one wavefront per place of the pool: the record staged in LDS, one lane per unit (in a loop when there are more units
-//                          than lanes) counts its jumps, a wave scan over the per-unit counts numbers them, the lanes write them to the move table
+//   pool_jumps_kernel      one wavefront per place of the pool: the record staged in LDS, its jumps counted, numbered and written to the move
+//                          table (pool_count_scan_emit of pool_blocks.hip, one lane per unit)
 //   pool_offsets_kernel, pool_neighbour_kernel, fixed_chunk
 //                          the climb's, unchanged, chunk by chunk: at most 16 entries of 512 jumps are the 8192 results the climb holds - no slices
 //   pool_admit_kernel      ONE wavefront: the objectives of the pass's feasible neighbours within the cost cap staged in LDS; then, as long as a
@@ -34,12 +34,12 @@
 // DISTINCT admission (miqp_solver_pool_explore_distinct; opt-in, the call above is unchanged): most neighbours of a new signature are
 // an entry's own solution under other labels.  The distinct call solves the kept entries' own records first (pass 0), has pool_label_kernel
 // (pool_label.hip) write the canonical record of every solved node behind its chunk, keeps per place the signature of that record beside the plain
-// one (pool_canon0_kernel) and admits a neighbour only when BOTH signatures are new (pool_admit_distinct_kernel: the same body, one more test).
+// one (pool_pass0_kernel) and admits a neighbour only when BOTH signatures are new (pool_admit_distinct_kernel: the same body, one more test).
 //
 // SETTLED admission (miqp_solver_pool_explore_settled; opt-in, both calls above are unchanged): first labels are an intermediate of
 // the iteration the refinement runs, and it merges by the final ones.  The settled call carries every candidate of a pass to ITS fixed point
 // (pool_settle.hip) and admits by the signature of the settled labels, so that miqp_solver_pool_solve behind it merges away nothing it added:
-//   pass 0                     the kept entries' own records through the settle rounds; pool_settled0_kernel writes, per kept entry, the plain
+//   pass 0                     the kept entries' own records through the settle rounds; pool_pass0_kernel writes, per kept entry, the plain
 //                              signature and the signature of its settled labels (none when its own QP is not feasible: it never matches)
 //   pool_settle_pick_kernel    behind a pass's chain and labels, one wavefront per neighbour: a CANDIDATE is feasible, within the cost cap, and its
 //                              plain signature - of the parent's bytes behind the jump, rebuilt in LDS as the admission does - is new against
@@ -112,17 +112,6 @@ __host__ __device__ inline int pool_unit_jumps(const PoolJumpDims& J, int fam, i
   return n;
 }
 
-// "within the cost cap": objective - obj0 <= max_rel |obj0|, every operation rounded on its own on both sides so that host code can restate it
-__host__ __device__ inline bool pool_within_cap(double obj0, double obj, double max_rel) {
-  if (max_rel < 0.0) return true;
-#ifdef __HIP_DEVICE_COMPILE__
-  return __dsub_rn(obj, obj0) <= __dmul_rn(max_rel, fabs(obj0));
-#else
-  volatile double over = obj - obj0; volatile double room = max_rel * std::fabs(obj0);
-  return over <= room;
-#endif
-}
-
 struct PoolExploreArgs {
   PoolImproveArgs A;              // the climb's: cur = the places of the pool, act = expand it in this pass, cnt, moves, off, res, ent_fam; A.m = places
   int L;                          // edge count of an obstacle
@@ -146,44 +135,37 @@ __global__ __launch_bounds__(64) void pool_jumps_kernel(const PoolExploreArgs E)
   const PoolImproveArgs& A = E.A;
   const int e = blockIdx.x, lane = threadIdx.x, chunks = A.fixlen >> 4;
   const PoolJumpDims J{A.dims, E.L};
-  const int nunits = pool_jump_units(A.dims);
   if (e >= A.m) return;
   if (!A.act[e]) { if (lane == 0) A.cnt[e] = 0; return; }
   const signed char* const rec = (const signed char*)pj_lds;
-  int* const ucnt = (int*)(pj_lds + chunks);
-  const uint4* src = (const uint4*)(A.cur + (size_t)e * A.fixlen);
-  for (int c = lane; c < chunks; c += 64) pj_lds[c] = src[c];
+  pool_stage(pj_lds, (const uint4*)(A.cur + (size_t)e * A.fixlen), chunks, lane);
   __syncthreads();
   const int fam = A.ent_fam[e];
-  for (int u = lane; u < nunits; u += 64) ucnt[u] = pool_unit_jumps(J, fam, u, rec, [](int, const PoolMove&) {});
-  __syncthreads();
-  int total = 0;   // exclusive scan of the per-unit counts, 64 units at a time
-  for (int u0 = 0; u0 < nunits; u0 += 64) {
-    const int c = u0 + lane < nunits ? ucnt[u0 + lane] : 0;
-    int x = c;
-    for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(x, o, 64); if (lane >= o) x += y; }
-    if (u0 + lane < nunits) ucnt[u0 + lane] = total + x - c;
-    total += __shfl(x, 63, 64);
-  }
-  __syncthreads();
-  int4* const out = A.moves + (size_t)e * POOL_MOVES_MAX;
-  for (int u = lane; u < nunits; u += 64) {
-    const int off = ucnt[u];
-    if (off >= POOL_MOVES_MAX) continue;
-    (void)pool_unit_jumps(J, fam, u, rec, [&](int j, const PoolMove& mv) { if (off + j < POOL_MOVES_MAX) out[off + j] = make_int4(mv.first, mv.stride, mv.count, mv.value); });
-  }
-  if (lane == 0) A.cnt[e] = min(total, POOL_MOVES_MAX);
+  const int total = pool_count_scan_emit(pool_jump_units(A.dims), (int*)(pj_lds + chunks), A.moves + (size_t)e * POOL_MOVES_MAX, lane,
+                                         [&](int u, auto emit) { return pool_unit_jumps(J, fam, u, rec, emit); });
+  if (lane == 0) A.cnt[e] = total;
 }
 
-// record j of the pool into LDS and its signature behind it (the whole wavefront calls)
-__device__ inline void pool_admit_signature(const PoolExploreArgs& E, uint4* rec4, uint4* sg4, int fam, int lane) {
-  const int nsites = pool_sites(E.A.dims);
-  __syncthreads();
-  for (int s = lane; s < nsites; s += 64) pool_site_signature(E.A.dims, fam, s, (const signed char*)rec4, (signed char*)sg4);
-  __syncthreads();
+// The neighbour of place e behind the move mv, the whole wavefront: the parent's record with the move patched in into rec, its signature under the
+// handle's filter into sg (both in LDS).  True: the signature is one of the first n of the pool
+__device__ inline bool pool_candidate_known(const PoolExploreArgs& E, int e, const int4 mv, uint4* rec, uint4* sg, int n, int lane) {
+  const PoolImproveArgs& A = E.A; const int chunks = A.fixlen >> 4;
+  pool_stage(rec, (const uint4*)A.cur + (size_t)e * chunks, chunks, lane, sg, mv);
+  pool_sign(A.dims, A.ent_fam[0], rec, sg, lane);
+  return pool_known(sg, (const uint4*)E.sig, n, chunks, lane);
 }
 
-constexpr double POOL_ADMIT_NONE = 1e308;   // in the staged objectives: not feasible, beyond the cap, or visited
+// Pass 0, the whole wavefront: record j < n of the array src(j) names (the pool's places, or the labels of the pass) signed under the handle's
+// filter into place j of dst.  rec, sg: a record and a signature in LDS
+template <class Src>
+__device__ inline void pool_sign_places(const PoolExploreArgs& E, uint4* rec, uint4* sg, int n, Src src, uint4* dst, int lane) {
+  const PoolImproveArgs& A = E.A; const int chunks = A.fixlen >> 4, fam = A.ent_fam[0];
+  for (int j = 0; j < n; ++j) {
+    pool_stage(rec, src(j) + (size_t)j * chunks, chunks, lane, sg);
+    pool_sign(A.dims, fam, rec, sg, lane);
+    pool_stage(dst + (size_t)j * chunks, sg, chunks, lane);
+  }
+}
 
 // The admission of a pass.  DISTINCT (miqp_solver_pool_explore_distinct): a candidate of a new signature is admitted only when the signature of its
 // CANONICAL record - the labels of its own solution, E.lab - is new as well, among the canonical signatures of everything in the pool (E.csig: the
@@ -199,23 +181,19 @@ __device__ inline void pool_admit_body(const PoolExploreArgs& E, int nb_max, uin
   uint4* const cand = pa_lds; uint4* const csig = cand + chunks;
   uint4* const ccan = csig + chunks; uint4* const ccsg = ccan + chunks;   // DISTINCT: the candidate's labelled record and its signature
   double* const key = (double*)(csig + (DISTINCT ? 3 : 1) * chunks);
-  const int fam = A.ent_fam[0];
   const int n0 = min(max(E.state[0], 0), K), total = min(max(A.off[K], 0), nb_max);
   uint4* const pool = (uint4*)A.cur; uint4* const sig = (uint4*)E.sig;
   // the signatures of the entries that have none yet: all of them in pass 1, later the ones the pass before appended (their signature is written
   // with them) - so only pass 1 builds any
-  if (E.pass == 1)
-    for (int j = 0; j < n0; ++j) {
-      for (int c = lane; c < chunks; c += 64) { cand[c] = pool[(size_t)j * chunks + c]; csig[c] = make_uint4(~0u, ~0u, ~0u, ~0u); }
-      pool_admit_signature(E, cand, csig, fam, lane);
-      for (int c = lane; c < chunks; c += 64) sig[(size_t)j * chunks + c] = csig[c];
-    }
+  if (E.pass == 1) pool_sign_places(E, cand, csig, n0, [&](int) { return (const uint4*)pool; }, sig, lane);
+  // the objectives of the pass's candidates, place by place (off[0] = 0 and off ascends: every neighbour below `total` is visited once)
   int it = 0;
-  for (int g = lane; g < total; g += 64) {
-    const miqp_fixed_result_c r = A.res[g];
-    it += r.iterations;
-    key[g] = r.status == 0 && r.objective < POOL_ADMIT_NONE && pool_within_cap(E.obj0, r.objective, E.max_rel) ? r.objective : POOL_ADMIT_NONE;
-  }
+  for (int e = 0; e < K; ++e)
+    for (int g0 = A.off[e], g1 = min(A.off[e + 1], total), g = g0 + lane; g < g1; g += 64) {
+      const miqp_fixed_result_c r = A.res[g];
+      it += r.iterations;
+      key[g] = pool_is_candidate(r, E.obj0, E.max_rel, g - g0, e, n0) ? r.objective : POOL_ADMIT_NONE;
+    }
   for (int d = 32; d >= 1; d >>= 1) it += __shfl_xor(it, d, 64);
   __syncthreads();
   int n = n0, added = 0;
@@ -225,43 +203,27 @@ __device__ inline void pool_admit_body(const PoolExploreArgs& E, int nb_max, uin
       const double o = key[g];
       if (o < bo) { bo = o; bg = g; }
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-      const double oo = __shfl_xor(bo, d, 64); const int og = __shfl_xor(bg, d, 64);
-      if (oo < bo || (oo == bo && og < bg)) { bo = oo; bg = og; }
-    }
+    pool_wave_argmin(bo, bg);
     if (bg == 0x7FFFFFFF) break;
     __syncthreads();
     if (lane == 0) key[bg] = POOL_ADMIT_NONE;
-    int e = 0;   // off[e] <= bg < off[e + 1]: at most 16 places
-    for (int j = 1; j < K; ++j) if (A.off[j] <= bg) e = j;
-    const int jm = bg - A.off[e];
-    if (jm < 0 || jm >= POOL_MOVES_MAX || e >= n0) { __syncthreads(); continue; }
-    const int4 mv = A.moves[(size_t)e * POOL_MOVES_MAX + jm];
-    for (int c = lane; c < chunks; c += 64) {
-      uint4 v = pool[(size_t)e * chunks + c];
-      for (int k = 0; k < mv.z; ++k) { const int p = mv.x + k * mv.y - c * 16; if ((unsigned)p < 16u) pool_patch_byte(v, p, mv.w); }
-      cand[c] = v; csig[c] = make_uint4(~0u, ~0u, ~0u, ~0u);
-    }
-    pool_admit_signature(E, cand, csig, fam, lane);
-    bool known = false;
-    for (int j = 0; j < n && !known; ++j) known = pool_cmp(csig, sig + (size_t)j * chunks, chunks, lane) == 0;
-    if (known) continue;
+    const int e = pool_entry_of(A.off, K, bg);   // (a staged objective: a candidate, so its move is one of the table and e < n0)
+    const int4 mv = A.moves[(size_t)e * POOL_MOVES_MAX + bg - A.off[e]];
+    if (pool_candidate_known(E, e, mv, cand, csig, n, lane)) continue;
     int solves = 0;
     if (SETTLED) {
       solves = E.solves[bg];
       if (solves == 0 || E.fin[bg].status != 0) continue;   // (uniform: no settled labels)
     }
     if (DISTINCT) {
-      const uint4* const lab = (const uint4*)E.lab + (size_t)bg * chunks; uint4* const can = (uint4*)E.csig;
-      for (int c = lane; c < chunks; c += 64) { ccan[c] = lab[c]; ccsg[c] = make_uint4(~0u, ~0u, ~0u, ~0u); }
-      pool_admit_signature(E, ccan, ccsg, fam, lane);
-      for (int j = 0; j < n && !known; ++j) known = (!SETTLED || E.has_sig[j]) && pool_cmp(ccsg, can + (size_t)j * chunks, chunks, lane) == 0;
-      if (known) continue;   // (an alias of an entry: the same solution under labels of another signature)
-      for (int c = lane; c < chunks; c += 64) can[(size_t)n * chunks + c] = ccsg[c];
+      uint4* const can = (uint4*)E.csig;
+      pool_stage(ccan, (const uint4*)E.lab + (size_t)bg * chunks, chunks, lane, ccsg);
+      pool_sign(A.dims, A.ent_fam[0], ccan, ccsg, lane);
+      if (pool_known(ccsg, can, n, chunks, lane, SETTLED ? E.has_sig : nullptr)) continue;   // (an alias of an entry: the same solution under labels of another signature)
+      pool_stage(can + (size_t)n * chunks, ccsg, chunks, lane);
       if (SETTLED && lane == 0) E.has_sig[n] = 1;
     }
-    for (int c = lane; c < chunks; c += 64) { pool[(size_t)n * chunks + c] = cand[c]; sig[(size_t)n * chunks + c] = csig[c]; }
+    for (int c = lane; c < chunks; c += 64) { pool[(size_t)n * chunks + c] = cand[c]; sig[(size_t)n * chunks + c] = csig[c]; }   // (one loop for both: two cost the plain kernel four registers)
     if (lane == 0) {
       A.cur_obj[n] = bo;
       miqp_pool_explore_c o;
@@ -300,105 +262,50 @@ __global__ __launch_bounds__(64) void pool_settle_pick_kernel(const PoolExploreA
   const int n0 = min(max(E.state[0], 0), K), total = min(max(A.off[K], 0), nb_max);
   if (g >= total || g >= S.n) return;
   uint4* const rec = pk_lds; uint4* const sg = rec + chunks;
-  const int status = A.res[g].status; const double objective = A.res[g].objective;
-  int e = 0;   // off[e] <= g < off[e + 1]: at most 16 places
-  for (int j = 1; j < K; ++j) if (A.off[j] <= g) e = j;
-  const int jm = g - A.off[e];
-  bool cand = status == 0 && objective < POOL_ADMIT_NONE && pool_within_cap(E.obj0, objective, E.max_rel) && jm >= 0 && jm < POOL_MOVES_MAX && e < n0;
-  bool moved = false;   // (cand and moved are uniform over the wavefront)
+  const int e = pool_entry_of(A.off, K, g), jm = g - A.off[e];
+  // (cand and moved are uniform over the wavefront.)  The pool only grows within a pass: new against its first n0 signatures is what the admission can ask at most
+  bool cand = pool_is_candidate(A.res[g], E.obj0, E.max_rel, jm, e, n0);
+  if (cand) cand = !pool_candidate_known(E, e, A.moves[(size_t)e * POOL_MOVES_MAX + jm], rec, sg, n0, lane);
+  bool moved = false;
   if (cand) {
-    const int fam = A.ent_fam[0];
-    const int4 mv = A.moves[(size_t)e * POOL_MOVES_MAX + jm];
-    const uint4* const pool = (const uint4*)A.cur; const uint4* const sig = (const uint4*)E.sig;
-    for (int c = lane; c < chunks; c += 64) {
-      uint4 v = pool[(size_t)e * chunks + c];
-      for (int k = 0; k < mv.z; ++k) { const int p = mv.x + k * mv.y - c * 16; if ((unsigned)p < 16u) pool_patch_byte(v, p, mv.w); }
-      rec[c] = v; sg[c] = make_uint4(~0u, ~0u, ~0u, ~0u);
-    }
-    pool_admit_signature(E, rec, sg, fam, lane);
-    bool known = false;
-    for (int j = 0; j < n0 && !known; ++j) known = pool_cmp(sg, sig + (size_t)j * chunks, chunks, lane) == 0;
-    cand = !known;
-  }
-  if (cand) {
-    const uint4* const lab = (const uint4*)first_lab + (size_t)g * chunks; uint4* const dst = (uint4*)S.cur + (size_t)g * chunks;
-    bool diff = false;
-    for (int c = lane; c < chunks; c += 64) { const uint4 x = lab[c], y = rec[c]; diff = diff || x.x != y.x || x.y != y.y || x.z != y.z || x.w != y.w; dst[c] = x; }
-    moved = __ballot(diff) != 0ull;
+    const uint4* const lab = (const uint4*)first_lab + (size_t)g * chunks;
+    moved = pool_records_differ(lab, rec, chunks, lane);
+    pool_stage((uint4*)S.cur + (size_t)g * chunks, lab, chunks, lane);
   }
   if (lane == 0) { pool_settle_copy_result(S.last + g, A.res + g); S.solves[g] = cand ? 1 : 0; S.moved[g] = moved ? 1 : 0; S.round_it[g] = 0; }
 }
 
-// Pass 0 of the settled call, behind the settle rounds over the kept entries' own records: ONE wavefront writes, per kept entry, its plain signature
-// (the pick kernel of pass 1 compares with it) and the signature of its settled labels, with the word that says whether it has one
-__global__ __launch_bounds__(64) void pool_settled0_kernel(const PoolExploreArgs E) {
-  extern __shared__ uint4 pc_lds[];   // a record, its signature
+// Pass 0 of the distinct and the settled call, ONE wavefront, behind the kept entries' own solves.  Distinct (behind the chain and pool_label_kernel):
+// per kept entry the signature of its canonical record - of its as-found bytes when its own QP is not feasible at the tight tolerance - and the
+// iterations of the pass.  Settled (behind the settle rounds): per kept entry its plain signature (the pick kernel of pass 1 compares with it) and
+// the signature of its settled labels, with the word that says whether it has one
+__global__ __launch_bounds__(64) void pool_pass0_kernel(const PoolExploreArgs E, int settled) {
+  extern __shared__ uint4 p0_lds[];   // a record, its signature
   const PoolImproveArgs& A = E.A;
   const int lane = threadIdx.x, chunks = A.fixlen >> 4, K = A.m;
-  uint4* const rec = pc_lds; uint4* const sg = rec + chunks;
-  const int fam = A.ent_fam[0], n0 = min(max(E.state[0], 0), K);
-  for (int j = 0; j < n0; ++j)
-    for (int settled = 0; settled < 2; ++settled) {
-      const uint4* const src = (settled ? (const uint4*)E.lab : (const uint4*)A.cur) + (size_t)j * chunks;
-      uint4* const dst = (settled ? (uint4*)E.csig : (uint4*)E.sig) + (size_t)j * chunks;
-      __syncthreads();
-      for (int c = lane; c < chunks; c += 64) { rec[c] = src[c]; sg[c] = make_uint4(~0u, ~0u, ~0u, ~0u); }
-      pool_admit_signature(E, rec, sg, fam, lane);
-      for (int c = lane; c < chunks; c += 64) dst[c] = sg[c];
-    }
-  for (int j = lane; j < K; j += 64) E.has_sig[j] = j < n0 && E.fin[j].status == 0 ? 1 : 0;
-}
-
-// Pass 0 of the distinct call, behind the chain and pool_label_kernel over the kept entries' own records: ONE wavefront writes, per kept entry, the
-// signature of its canonical record - of its as-found bytes when its own QP is not feasible at the tight tolerance - and the iterations of the pass
-__global__ __launch_bounds__(64) void pool_canon0_kernel(const PoolExploreArgs E) {
-  extern __shared__ uint4 pc_lds[];   // a record, its signature
-  const PoolImproveArgs& A = E.A;
-  const int lane = threadIdx.x, chunks = A.fixlen >> 4, K = A.m;
-  uint4* const rec = pc_lds; uint4* const sg = rec + chunks;
-  const int fam = A.ent_fam[0], n0 = min(max(E.state[0], 0), K);
-  int it = 0;
-  for (int j = 0; j < n0; ++j) {
-    const miqp_fixed_result_c r = A.res[j];
-    it += r.iterations;
-    const uint4* const src = (r.status == 0 ? (const uint4*)E.lab : (const uint4*)A.cur) + (size_t)j * chunks;
-    __syncthreads();
-    for (int c = lane; c < chunks; c += 64) { rec[c] = src[c]; sg[c] = make_uint4(~0u, ~0u, ~0u, ~0u); }
-    pool_admit_signature(E, rec, sg, fam, lane);
-    for (int c = lane; c < chunks; c += 64) ((uint4*)E.csig)[(size_t)j * chunks + c] = sg[c];
+  uint4* const rec = p0_lds; uint4* const sg = rec + chunks;
+  const int n0 = min(max(E.state[0], 0), K);
+  const uint4* const cur = (const uint4*)A.cur; const uint4* const lab = (const uint4*)E.lab;
+  if (settled) {
+    pool_sign_places(E, rec, sg, n0, [&](int) { return cur; }, (uint4*)E.sig, lane);
+    pool_sign_places(E, rec, sg, n0, [&](int) { return lab; }, (uint4*)E.csig, lane);
+    for (int j = lane; j < K; j += 64) E.has_sig[j] = j < n0 && E.fin[j].status == 0 ? 1 : 0;
+  } else {
+    int it = 0;
+    for (int j = 0; j < n0; ++j) it += A.res[j].iterations;
+    pool_sign_places(E, rec, sg, n0, [&](int j) { return A.res[j].status == 0 ? lab : cur; }, (uint4*)E.csig, lane);
+    if (lane == 0) E.state[2] = it;
   }
-  if (lane == 0) E.state[2] = it;
 }
 
-// buffers of the call beside the climb's (PoolImproveDev, PoolEntryDev), cached per device (grown, not shrunk)
+// buffers of the call beside the climb's (PoolImproveDev, PoolEntryDev), cached per device (DevArr: grown, not shrunk).  has_sig is the settled
+// call's (a place has a settled signature); csig and lab the distinct and the settled call's: the second signatures of the places and the labelled
+// records of a pass's neighbours
 struct PoolExploreDev {
-  signed char* sig = nullptr; size_t sig_cap = 0; int* state = nullptr; miqp_pool_explore_c* out = nullptr;
-  int* has_sig = nullptr;   // (the settled call's: a place has a settled signature)
-  bool ensure(size_t fl) {
-    if (!state) HIP_OK(hipMalloc((void**)&state, 4 * sizeof(int)));
-    if (!has_sig) HIP_OK(hipMalloc((void**)&has_sig, MIQP_POOL_MAX * sizeof(int)));
-    if (!out) HIP_OK(hipMalloc((void**)&out, MIQP_POOL_MAX * sizeof(miqp_pool_explore_c)));
-    if (MIQP_POOL_MAX * fl > sig_cap) {
-      if (sig) (void)hipFree(sig);
-      sig = nullptr; sig_cap = 0;
-      HIP_OK(hipMalloc((void**)&sig, MIQP_POOL_MAX * fl));
-      sig_cap = MIQP_POOL_MAX * fl;
-    }
-    return true;
-  }
-  // the distinct call's: the canonical signatures of the places and the labelled records of a pass's neighbours
-  signed char* csig = nullptr; signed char* lab = nullptr; size_t lab_cap = 0;
-  bool ensure_distinct(size_t fl) {
-    if ((size_t)PoolImproveDev::NB_MAX * fl > lab_cap) {
-      if (csig) (void)hipFree(csig); if (lab) (void)hipFree(lab);
-      csig = nullptr; lab = nullptr; lab_cap = 0;
-      HIP_OK(hipMalloc((void**)&csig, MIQP_POOL_MAX * fl)); HIP_OK(hipMalloc((void**)&lab, (size_t)PoolImproveDev::NB_MAX * fl));
-      lab_cap = (size_t)PoolImproveDev::NB_MAX * fl;
-    }
-    return true;
-  }
+  DevArr<signed char> sig, csig, lab; DevArr<int> state, has_sig; DevArr<miqp_pool_explore_c> out;
+  bool ensure(size_t fl) { return state.need(4) && has_sig.need(MIQP_POOL_MAX) && out.need(MIQP_POOL_MAX) && sig.need(MIQP_POOL_MAX * fl); }
+  bool ensure_distinct(size_t fl) { return csig.need(MIQP_POOL_MAX * fl) && lab.need((size_t)PoolImproveDev::NB_MAX * fl); }
 };
-std::map<int, PoolExploreDev> g_pool_explore_dev;   // by device ordinal; used under the device lock
 
 struct PoolExploreOut {
   std::vector<miqp_pool_explore_c> added;
@@ -414,31 +321,29 @@ bool pool_explore_run(const FixedCall& call, const char* name, int mode, int fam
   DevCtx& X = *call.X; DevBuf& B = X.B; hipStream_t st = X.stream; const Layout& Y = call.Y;
   const size_t fl = (size_t)Y.fixlen;
   const bool distinct = mode != POOL_ADMIT_PLAIN, settled = mode == POOL_ADMIT_SETTLED;   // (distinct: what both opt-in calls need - labels, pass 0, the second signature)
-  PoolImproveDev& R = g_pool_improve_dev[X.device]; PoolEntryDev& G = g_pool_entry_dev[X.device]; PoolExploreDev& Q = g_pool_explore_dev[X.device];
-  PoolSettleDev& W = g_pool_settle_dev[X.device];
+  PoolImproveDev& R = call_dev<PoolImproveDev>(X.device); PoolEntryDev& G = call_dev<PoolEntryDev>(X.device); PoolExploreDev& Q = call_dev<PoolExploreDev>(X.device);
+  PoolSettleDev& W = call_dev<PoolSettleDev>(X.device);
   if (!R.ensure((size_t)Y.N * Y.nz) || !G.ensure(MIQP_POOL_MAX, fl) || !Q.ensure(fl) || (distinct && !Q.ensure_distinct(fl))) return false;
   if (settled && !W.ensure((size_t)PoolImproveDev::NB_MAX, fl)) return false;
+  // per mode: the admission kernel, the records its LDS holds beside the objectives of a pass, and how the refusal names both
+  struct Mode { void (*admit)(PoolExploreArgs, int); int records; const char* kernel; const char* times; };
+  static const Mode modes[3] = {{pool_admit_kernel, 2, "pool_admit_kernel", "twice"}, {pool_admit_distinct_kernel, 4, "pool_admit_distinct_kernel", "four times"},
+                                {pool_admit_settled_kernel, 4, "pool_admit_settled_kernel", "four times"}};
+  const Mode& M = modes[mode];
   const PoolDims dims = pool_dims(Y);
-  const size_t jump_lds = fl + (size_t)pool_jump_units(dims) * sizeof(int), admit_lds = (distinct ? 4 : 2) * fl + (size_t)PoolImproveDev::NB_MAX * sizeof(double);
+  const size_t jump_lds = fl + (size_t)pool_jump_units(dims) * sizeof(int), admit_lds = M.records * fl + (size_t)PoolImproveDev::NB_MAX * sizeof(double);
   if (std::max(jump_lds, admit_lds) > POOL_EXPLORE_LDS_MAX) {
-    O.err = std::string(name) + (settled ? ": the fix record of this shape does not fit the LDS of pool_admit_settled_kernel four times beside the objectives of a pass"
-                                 : distinct ? ": the fix record of this shape does not fit the LDS of pool_admit_distinct_kernel four times beside the objectives of a pass"
-                                          : ": the fix record of this shape does not fit the LDS of pool_admit_kernel twice beside the objectives of a pass");
+    O.err = std::string(name) + ": the fix record of this shape does not fit the LDS of " + M.kernel + " " + M.times + " beside the objectives of a pass";
     std::fprintf(stderr, "[miqp_gpu] %s (%zu bytes)\n", O.err.c_str(), std::max(jump_lds, admit_lds)); return false;
   }
   if (distinct && !pool_label_fits(Y, name, O.err)) return false;
   HIP_OK(hipFuncSetAttribute((const void*)pool_jumps_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)jump_lds));
-  if (settled) {
-    HIP_OK(hipFuncSetAttribute((const void*)pool_admit_settled_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)admit_lds));
-    HIP_OK(hipFuncSetAttribute((const void*)pool_settle_pick_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * fl)));
-    HIP_OK(hipFuncSetAttribute((const void*)pool_settled0_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * fl)));
+  HIP_OK(hipFuncSetAttribute((const void*)M.admit, hipFuncAttributeMaxDynamicSharedMemorySize, (int)admit_lds));
+  if (distinct) {
+    HIP_OK(hipFuncSetAttribute((const void*)pool_pass0_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * fl)));
     if (!pool_label_set_lds(Y)) return false;
-  } else if (distinct) {
-    HIP_OK(hipFuncSetAttribute((const void*)pool_admit_distinct_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)admit_lds));
-    HIP_OK(hipFuncSetAttribute((const void*)pool_canon0_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * fl)));
-    if (!pool_label_set_lds(Y)) return false;
-  } else
-    HIP_OK(hipFuncSetAttribute((const void*)pool_admit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)admit_lds));
+  }
+  if (settled) HIP_OK(hipFuncSetAttribute((const void*)pool_settle_pick_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * fl)));
   std::vector<int> act(MIQP_POOL_MAX, 0); for (int k = 0; k < n; ++k) act[k] = 1;
   const int state0[4] = {n, 0, 0, 0};
   HIP_OK(hipMemsetAsync(B.batch_inst, 0, (size_t)FB_CHUNK * 4, st));
@@ -456,8 +361,8 @@ bool pool_explore_run(const FixedCall& call, const char* name, int mode, int fam
   A.ent_inst = G.ent_inst; A.ent_fam = G.ent_fam; A.off = G.off; A.batch_inst = B.batch_inst;
   A.dims = dims; A.fixlen = (int)fl; A.m = K;   // (every place of the pool is an entry of the kernels: a free one is not expanded and has no jumps)
   E.L = L; E.sig = Q.sig; E.state = Q.state; E.out = Q.out; E.obj0 = obj0; E.max_rel = max_rel; E.pass = 0;
-  E.csig = distinct ? Q.csig : nullptr; E.lab = settled ? W.cur : distinct ? Q.lab : nullptr;
-  E.has_sig = Q.has_sig; E.fin = settled ? W.last : nullptr; E.solves = settled ? W.solves : nullptr;
+  E.csig = distinct ? Q.csig.p : nullptr; E.lab = settled ? W.cur.p : distinct ? Q.lab.p : nullptr;
+  E.has_sig = Q.has_sig; E.fin = settled ? W.last.p : nullptr; E.solves = settled ? W.solves.p : nullptr;
   PoolSettleTally tally;   // (the settled call's: the solves of its settle rounds and their iterations)
   // `total` neighbours of a pass through the chain, a chunk at a time, as the climb sends them (no segments, the trajectories written over)
   auto solve_nodes = [&](int total) -> bool {
@@ -473,9 +378,7 @@ bool pool_explore_run(const FixedCall& call, const char* name, int mode, int fam
   // behind a pass (admit: not in front of the first one): the jumps of the next one, and what the host needs of both
   std::vector<int> cnt(MIQP_POOL_MAX); int state[4] = {n, 0, 0, 0}; std::vector<miqp_pool_explore_c> rec(MIQP_POOL_MAX);
   auto finish_pass = [&](bool admit) -> bool {
-    if (admit && settled) hipLaunchKernelGGL(pool_admit_settled_kernel, dim3(1), dim3(64), admit_lds, st, E, (int)PoolImproveDev::NB_MAX);
-    else if (admit && distinct) hipLaunchKernelGGL(pool_admit_distinct_kernel, dim3(1), dim3(64), admit_lds, st, E, (int)PoolImproveDev::NB_MAX);
-    else if (admit) hipLaunchKernelGGL(pool_admit_kernel, dim3(1), dim3(64), admit_lds, st, E, (int)PoolImproveDev::NB_MAX);
+    if (admit) hipLaunchKernelGGL(M.admit, dim3(1), dim3(64), admit_lds, st, E, (int)PoolImproveDev::NB_MAX);
     hipLaunchKernelGGL(pool_jumps_kernel, dim3(K), dim3(64), jump_lds, st, E);
     hipLaunchKernelGGL(pool_offsets_kernel, dim3(1), dim3(256), 0, st, A);
     HIP_OK(hipGetLastError());
@@ -498,15 +401,12 @@ bool pool_explore_run(const FixedCall& call, const char* name, int mode, int fam
   HIP_OK(hipEventRecord(X.ev0, st));
   if (settled) {   // pass 0: the kept entries' own records to their fixed points, the signatures of both kinds
     if (!pool_settle_records(call, Bp, pool_settle_args(W, B, Y, n), R.Z, G.cur, true, tally)) return false;
-    hipLaunchKernelGGL(pool_settled0_kernel, dim3(1), dim3(64), 2 * fl, st, E);
-    HIP_OK(hipGetLastError());
   } else if (distinct) {   // pass 0, as in the climb: the kept entries' own records through the chain, their labels, the signatures of those
     hipLaunchKernelGGL(pool_neighbour_kernel, dim3((n + 3) / 4), dim3(256), 0, st, A, 0, n, 1);
     HIP_OK(hipGetLastError());
     if (!fixed_chunk(X, Bp, Y, call.dev(), 1, FixedChunk{n, 0, R.res, R.Z}) || !pool_label_chunk(X, Y, 1, n, R.res, R.Z, Q.lab)) return false;
-    hipLaunchKernelGGL(pool_canon0_kernel, dim3(1), dim3(64), 2 * fl, st, E);
-    HIP_OK(hipGetLastError());
   }
+  if (distinct) { hipLaunchKernelGGL(pool_pass0_kernel, dim3(1), dim3(64), 2 * fl, st, E, settled ? 1 : 0); HIP_OK(hipGetLastError()); }
   if (!finish_pass(false)) return false;
   if (distinct && !settled) { O.neighbours += n; O.iterations += state[2]; }
   int have = n;

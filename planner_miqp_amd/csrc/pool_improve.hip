@@ -17,14 +17,12 @@
 //
 // pool_site_moves below is that definition, once, for the host (miqp_gpu_pool_moves) and the device (pool_moves_kernel).
 //
-// The climb, per pass, all on the solver stream:
-//   pool_moves_kernel      one wavefront per entry: the record staged in LDS, one lane per site (in a loop when there are more sites than lanes)
-//                          counts its kept moves under the ENTRY's filter, a wave scan over the per-site counts numbers them, the lanes write them
-//                          to the move table in HBM
+// The climb, per pass, all on the solver stream (the steps the kernels share with the explore's and the settle's are in pool_blocks.hip):
+//   pool_moves_kernel      one wavefront per entry: the record staged and signed in LDS, the kept moves of its sites under the ENTRY's filter
+//                          counted, numbered and written to the move table in HBM (pool_count_scan_emit, one lane per site)
 //   pool_offsets_kernel    one workgroup: the exclusive scan of the per-entry counts, off[0 .. m] - neighbour off[e] + j is move j of entry e
-//   pool_neighbour_kernel  one wavefront per node of the chunk being launched: neighbour number -> (entry, move) by binary search in the scan, the
-//                          entry's current record in 16-byte loads, the move patched in registers, 16-byte stores into slot k of pool_fix; the
-//                          entry's instance into slot k of batch_inst
+//   pool_neighbour_kernel  one wavefront per node of the chunk being launched: neighbour number -> (entry, move), the entry's current record with
+//                          the move patched in into slot k of pool_fix; the entry's instance into slot k of batch_inst
 //   fixed_chunk            the chain of the fixed calls with its resets and settings and fixed_collect_kernel behind it, without segments (fixed_chain.hip)
 //   pool_pick_kernel       one wavefront per entry over its contiguous range of results: the feasible neighbour of the lowest objective, ties to the
 //                          lower move number; accepted when it is below the entry's objective by more than 1e-9 (1 + |objective|) - then the move is
@@ -53,11 +51,8 @@
 
 namespace {
 
-constexpr int POOL_MOVES_MAX = 512;   // moves per record (miqp_gpu_pool_moves_max): LNS_MAX
 constexpr int POOL_IMPROVE_PASSES_MAX = 64;
 constexpr size_t POOL_MOVES_LDS_MAX = 160 * 1024;   // dynamic LDS of pool_moves_kernel (3 fixlen + 4 sites bytes): the LDS of a gfx950 workgroup; a larger shape is refused with a message
-
-struct PoolMove { int first, stride, count, value; };
 
 // the kept moves of site s in their order; emit(j, move) receives move j of the site, the number of moves is returned.  rec: the record (the site's
 // bytes are patched and restored on the way), sg0: its signature under fam at the site's bytes, sg1: -1 at the site's bytes, before and after
@@ -115,70 +110,35 @@ struct PoolImproveArgs {
 
 __global__ __launch_bounds__(64) void pool_moves_kernel(const PoolImproveArgs A) {
   extern __shared__ uint4 pm_lds[];   // the record, its signature, a second signature; behind them one int per site
-  const int e = blockIdx.x, lane = threadIdx.x, chunks = A.fixlen >> 4, nsites = pool_sites(A.dims);
+  const int e = blockIdx.x, lane = threadIdx.x, chunks = A.fixlen >> 4;
   if (!A.act[e]) { if (lane == 0) A.cnt[e] = 0; return; }
   uint4* const rec4 = pm_lds; uint4* const sg04 = rec4 + chunks; uint4* const sg14 = sg04 + chunks;
-  signed char* const rec = (signed char*)rec4; signed char* const sg0 = (signed char*)sg04; signed char* const sg1 = (signed char*)sg14;
-  int* const scnt = (int*)(sg14 + chunks);
-  const uint4* src = (const uint4*)(A.cur + (size_t)e * A.fixlen);
-  for (int c = lane; c < chunks; c += 64) { rec4[c] = src[c]; sg04[c] = make_uint4(~0u, ~0u, ~0u, ~0u); sg14[c] = make_uint4(~0u, ~0u, ~0u, ~0u); }
-  __syncthreads();
-  // (a site reads and writes its own bytes of the three blocks and no others: the lanes do not meet until the scan)
+  signed char* const rec = (signed char*)rec4; const signed char* const sg0 = (const signed char*)sg04; signed char* const sg1 = (signed char*)sg14;
   const int fam = A.ent_fam[e];
-  for (int s = lane; s < nsites; s += 64) {
-    pool_site_signature(A.dims, fam, s, rec, sg0);
-    scnt[s] = pool_site_moves(A.dims, fam, s, rec, sg0, sg1, [](int, const PoolMove&) {});
-  }
-  __syncthreads();
-  int total = 0;   // exclusive scan of the per-site counts, 64 sites at a time
-  for (int s0 = 0; s0 < nsites; s0 += 64) {
-    const int c = s0 + lane < nsites ? scnt[s0 + lane] : 0;
-    int x = c;
-    for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(x, o, 64); if (lane >= o) x += y; }
-    if (s0 + lane < nsites) scnt[s0 + lane] = total + x - c;
-    total += __shfl(x, 63, 64);
-  }
-  __syncthreads();
-  int4* const out = A.moves + (size_t)e * POOL_MOVES_MAX;
-  for (int s = lane; s < nsites; s += 64) {
-    const int off = scnt[s];
-    if (off >= POOL_MOVES_MAX) continue;
-    (void)pool_site_moves(A.dims, fam, s, rec, sg0, sg1, [&](int j, const PoolMove& mv) { if (off + j < POOL_MOVES_MAX) out[off + j] = make_int4(mv.first, mv.stride, mv.count, mv.value); });
-  }
-  if (lane == 0) A.cnt[e] = min(total, POOL_MOVES_MAX);
+  pool_stage(rec4, (const uint4*)(A.cur + (size_t)e * A.fixlen), chunks, lane, sg04);
+  for (int c = lane; c < chunks; c += 64) sg14[c] = make_uint4(~0u, ~0u, ~0u, ~0u);
+  pool_sign(A.dims, fam, rec4, sg04, lane);
+  // (a site reads and writes its own bytes of the record and of the second signature and no others: the lanes do not meet until the scan)
+  const int total = pool_count_scan_emit(pool_sites(A.dims), (int*)(sg14 + chunks), A.moves + (size_t)e * POOL_MOVES_MAX, lane,
+                                         [&](int s, auto emit) { return pool_site_moves(A.dims, fam, s, rec, sg0, sg1, emit); });
+  if (lane == 0) A.cnt[e] = total;
 }
 
-__device__ inline void pool_patch_byte(uint4& v, int p, int val) {   // byte p (0 .. 15) of v, without indexing the registers
-  const unsigned sh = (unsigned)(p & 3) * 8u, keep = ~(0xFFu << sh), bits = ((unsigned)val & 0xFFu) << sh;
-  const int w = p >> 2;
-  v.x = w == 0 ? (v.x & keep) | bits : v.x; v.y = w == 1 ? (v.y & keep) | bits : v.y;
-  v.z = w == 2 ? (v.z & keep) | bits : v.z; v.w = w == 3 ? (v.w & keep) | bits : v.w;
-}
-
-// off[0 .. m] behind pool_moves_kernel: ONE workgroup, tiles of 256 entries - a wave scan per wavefront, the four wavefront totals through LDS, the
-// running total of the tiles before in a register of every lane.  m <= 65536 entries of at most 512 moves: a pass total is at most 2^25
+// off[0 .. m] behind pool_moves_kernel: ONE workgroup, the exclusive scan of the clamped counts in tiles of 256 entries (pool_tile_scan).
+// m <= 65536 entries of at most 512 moves: a pass total is at most 2^25
 __global__ __launch_bounds__(256) void pool_offsets_kernel(const PoolImproveArgs A) {
   __shared__ int carry[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int base = 0;
-  for (int t0 = 0; t0 < A.m; t0 += 256) {   // (A.m is uniform: every lane meets every barrier)
-    const int e = t0 + tid;
-    const int c = e < A.m ? min(max(A.cnt[e], 0), POOL_MOVES_MAX) : 0;
-    int x = c;
-    for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(x, o, 64); if (lane >= o) x += y; }
-    if (lane == 63) carry[wave] = x;
-    __syncthreads();
-    int before = 0;
-    for (int w = 0; w < 4; ++w) before += w < wave ? carry[w] : 0;
-    if (e < A.m) A.off[e] = base + before + x - c;
-    base += carry[0] + carry[1] + carry[2] + carry[3];
-    __syncthreads();
+  for (int t0 = 0; t0 < A.m; t0 += 256) {   // (A.m is uniform: every thread meets every barrier)
+    const int e = t0 + threadIdx.x;
+    const int at = pool_tile_scan(e < A.m ? min(max(A.cnt[e], 0), POOL_MOVES_MAX) : 0, carry, base);
+    if (e < A.m) A.off[e] = at;
   }
-  if (tid == 0) A.off[A.m] = base;
+  if (threadIdx.x == 0) A.off[A.m] = base;
 }
 
 // nodes c0 .. c0 + bc - 1 of the pass into slots 0 .. bc - 1 of pool_fix and batch_inst; own: pass 0, node e is entry e's own record.  Else node g is
-// move g - off[e] of the entry e with off[e] <= g < off[e + 1]: a binary search of at most 17 probes, the same in every lane of the wavefront
+// move g - off[e] of the entry e with off[e] <= g < off[e + 1] (pool_entry_of), patched into the entry's record on its way (pool_stage)
 __global__ __launch_bounds__(256) void pool_neighbour_kernel(const PoolImproveArgs A, int c0, int bc, int own) {
   const int lane = threadIdx.x & 63, slot = blockIdx.x * 4 + (threadIdx.x >> 6), chunks = A.fixlen >> 4;
   if (slot >= bc) return;
@@ -186,20 +146,12 @@ __global__ __launch_bounds__(256) void pool_neighbour_kernel(const PoolImproveAr
   if (!own) {
     const int g = c0 + slot;
     if (g < 0 || g >= A.off[A.m]) return;
-    int lo = 0, hi = A.m;   // off[lo] <= g < off[hi]
-    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (A.off[mid] <= g) lo = mid; else hi = mid; }
-    e = lo; j = g - A.off[lo];
+    e = pool_entry_of(A.off, A.m, g); j = g - A.off[e];
     if (j >= POOL_MOVES_MAX) return;
   }
   if (e < 0 || e >= A.m) return;
   const int4 mv = j >= 0 ? A.moves[(size_t)e * POOL_MOVES_MAX + j] : make_int4(0, 1, 0, 0);
-  const uint4* src = (const uint4*)(A.cur + (size_t)e * A.fixlen);
-  uint4* dst = (uint4*)(A.pool_fix + (size_t)slot * A.fixlen);
-  for (int c = lane; c < chunks; c += 64) {
-    uint4 v = src[c];
-    for (int k = 0; k < mv.z; ++k) { const int p = mv.x + k * mv.y - c * 16; if ((unsigned)p < 16u) pool_patch_byte(v, p, mv.w); }
-    dst[c] = v;
-  }
+  pool_stage((uint4*)(A.pool_fix + (size_t)slot * A.fixlen), (const uint4*)(A.cur + (size_t)e * A.fixlen), chunks, lane, nullptr, mv);
   if (lane == 0) A.batch_inst[slot] = A.ent_inst[e];
 }
 
@@ -225,12 +177,8 @@ __global__ __launch_bounds__(64) void pool_pick_kernel(const PoolImproveArgs A, 
     it += r.iterations;
     if (r.status == 0 && r.objective < bo) { bo = r.objective; bj = j; }
   }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    const double oo = __shfl_xor(bo, d, 64); const int oj = __shfl_xor(bj, d, 64);
-    it += __shfl_xor(it, d, 64);
-    if (oo < bo || (oo == bo && oj < bj)) { bo = oo; bj = oj; }
-  }
+  pool_wave_argmin(bo, bj);
+  for (int d = 32; d >= 1; d >>= 1) it += __shfl_xor(it, d, 64);
   const bool acc = bj != 0x7FFFFFFF && pool_improves(cur, bo);
   if (acc) {
     const int4 mv = A.moves[(size_t)e * POOL_MOVES_MAX + bj];
@@ -244,54 +192,23 @@ __global__ __launch_bounds__(64) void pool_pick_kernel(const PoolImproveArgs A, 
 }
 
 // ---------------------------------------------------------------------------------------------------------------- device cache
-// buffers of the climb and the explore, cached per device like FixedDev and never taken from the solver's pools (grown, not shrunk).  The slice buffers:
+// buffers of the climb and the explore, cached per device like FixedDev and never taken from the solver's pools (DevArr: grown, not shrunk).  The slice
+// buffers - the collect kernel copies the chunk's trajectories: the climb has no use for them, one chunk's worth is written over:
 struct PoolImproveDev {
-  miqp_fixed_result_c* res = nullptr; double* Z = nullptr; size_t z_cap = 0;
   static constexpr int NB_MAX = MIQP_POOL_MAX * POOL_MOVES_MAX;   // results of a slice
-  bool ensure(size_t row) {
-    if (!res) HIP_OK(hipMalloc((void**)&res, (size_t)NB_MAX * sizeof(miqp_fixed_result_c)));
-    if ((size_t)FB_CHUNK * row > z_cap) {   // (the collect kernel copies the chunk's trajectories: the climb has no use for them, one chunk's worth is written over)
-      if (Z) (void)hipFree(Z);
-      Z = nullptr; z_cap = 0;
-      HIP_OK(hipMalloc((void**)&Z, (size_t)FB_CHUNK * row * sizeof(double)));
-      z_cap = (size_t)FB_CHUNK * row;
-    }
-    return true;
-  }
+  DevArr<miqp_fixed_result_c> res; DevArr<double> Z;
+  bool ensure(size_t row) { return res.need(NB_MAX) && Z.need((size_t)FB_CHUNK * row); }
 };
-std::map<int, PoolImproveDev> g_pool_improve_dev;   // by device ordinal; used under the device lock
 
 // ... and the per-entry buffers: never fewer than the MIQP_POOL_MAX places the explore fills
 struct PoolEntryDev {
-  signed char* cur = nullptr; size_t cur_cap = 0;
-  double* cur_obj = nullptr; int* act = nullptr; int* cnt = nullptr; int* off = nullptr; int* ent_inst = nullptr; int* ent_fam = nullptr;
-  int4* moves = nullptr; PoolWord* words = nullptr; size_t ent_cap = 0;
-  void drop_entries() {
-    if (cur_obj) (void)hipFree(cur_obj); if (act) (void)hipFree(act); if (cnt) (void)hipFree(cnt); if (off) (void)hipFree(off);
-    if (ent_inst) (void)hipFree(ent_inst); if (ent_fam) (void)hipFree(ent_fam); if (moves) (void)hipFree(moves); if (words) (void)hipFree(words);
-    cur_obj = nullptr; act = nullptr; cnt = nullptr; off = nullptr; ent_inst = nullptr; ent_fam = nullptr; moves = nullptr; words = nullptr; ent_cap = 0;
-  }
+  DevArr<signed char> cur; DevArr<double> cur_obj; DevArr<int> act, cnt, off, ent_inst, ent_fam; DevArr<int4> moves; DevArr<PoolWord> words;
   bool ensure(size_t m, size_t fl) {
     static_assert(MIQP_POOL_MAX <= 64, "the smallest allocation holds a pool");
-    if (m > ent_cap) {
-      drop_entries();
-      size_t want = 64; while (want < m) want <<= 1;
-      HIP_OK(hipMalloc((void**)&cur_obj, want * sizeof(double))); HIP_OK(hipMalloc((void**)&act, want * sizeof(int))); HIP_OK(hipMalloc((void**)&cnt, want * sizeof(int)));
-      HIP_OK(hipMalloc((void**)&off, (want + 1) * sizeof(int))); HIP_OK(hipMalloc((void**)&ent_inst, want * sizeof(int))); HIP_OK(hipMalloc((void**)&ent_fam, want * sizeof(int)));
-      HIP_OK(hipMalloc((void**)&words, want * sizeof(PoolWord))); HIP_OK(hipMalloc((void**)&moves, want * POOL_MOVES_MAX * sizeof(int4)));
-      ent_cap = want;   // (set when all eight are there: a failure half-way is taken up from the start)
-    }
-    if (m * fl > cur_cap) {
-      if (cur) (void)hipFree(cur);
-      cur = nullptr; cur_cap = 0;
-      size_t want = 64 * fl; while (want < m * fl) want <<= 1;
-      HIP_OK(hipMalloc((void**)&cur, want));
-      cur_cap = want;
-    }
-    return true;
+    return cur_obj.need(m, 64) && act.need(m, 64) && cnt.need(m, 64) && off.need(m, 64, 1) && ent_inst.need(m, 64) && ent_fam.need(m, 64) && words.need(m, 64) &&
+           moves.need(m * POOL_MOVES_MAX, 64 * POOL_MOVES_MAX) && cur.need(m * fl, 64 * fl);
   }
 };
-std::map<int, PoolEntryDev> g_pool_entry_dev;   // by device ordinal; used under the device lock
 
 // the slices of a pass, greedily in entry order: an entry opens a new slice when its (clamped) moves do not fit the results left of the current one
 int pool_improve_slices(const int* move_counts, int entries, int* slice_first, int cap) {
@@ -328,7 +245,7 @@ bool pool_improve_run(const FixedCall& call, const char* name, const signed char
   DevCtx& X = *call.X; const Layout& Y = call.Y; const int n_inst = call.n;
   DevBuf& B = X.B; hipStream_t st = X.stream;
   const size_t fl = (size_t)Y.fixlen, row = (size_t)Y.N * Y.nz;
-  PoolImproveDev& G = g_pool_improve_dev[X.device]; PoolEntryDev& M = g_pool_entry_dev[X.device];
+  PoolImproveDev& G = call_dev<PoolImproveDev>(X.device); PoolEntryDev& M = call_dev<PoolEntryDev>(X.device);
   if (!G.ensure(row) || !M.ensure((size_t)m, fl)) return false;
   const PoolDims dims = pool_dims(Y);
   const size_t gen_lds = 3 * fl + (size_t)pool_sites(dims) * sizeof(int);

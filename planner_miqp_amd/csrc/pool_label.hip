@@ -178,7 +178,7 @@ __global__ __launch_bounds__(64) void pool_label_kernel(const PoolLabelArgs A) {
   bool ok = A.res[k].status == 0 && (unsigned)inst < (unsigned)A.n_inst;   // (uniform over the wavefront)
   {
     const uint4* src = (const uint4*)(A.fix + (size_t)k * Y.fixlen);
-    for (int c = lane; c < chunks; c += 64) { rec4[c] = src[c]; out4[c] = make_uint4(~0u, ~0u, ~0u, ~0u); }
+    pool_stage(rec4, src, chunks, lane, out4);
     if (ok) { const uint4* zs = (const uint4*)(A.Z + (size_t)k * Y.N * Y.nz); for (int c = lane; c < zchunks; c += 64) z4[c] = zs[c]; }
   }
   __syncthreads();
@@ -194,25 +194,14 @@ __global__ __launch_bounds__(64) void pool_label_kernel(const PoolLabelArgs A) {
     for (int t = lane; t < nbytes; t += 64) { int at = 0; const int v = pool_label_byte(Y, D, T, rec, Z, t, at); out[at] = (signed char)v; }
   }
   __syncthreads();
-  uint4* dst = (uint4*)(A.out + (size_t)k * Y.fixlen);
-  for (int c = lane; c < chunks; c += 64) dst[c] = out4[c];
+  pool_stage((uint4*)(A.out + (size_t)k * Y.fixlen), out4, chunks, lane);
 }
 
-// the labelled records of a call, cached per device (grown, not shrunk)
+// the labelled records of a call, cached per device (DevArr: grown, not shrunk)
 struct PoolLabelDev {
-  signed char* canon = nullptr; size_t cap = 0;
-  bool ensure(size_t bytes) {
-    if (bytes > cap) {
-      if (canon) (void)hipFree(canon);
-      canon = nullptr; cap = 0;
-      size_t want = (size_t)1 << 20; while (want < bytes) want <<= 1;
-      HIP_OK(hipMalloc((void**)&canon, want));
-      cap = want;
-    }
-    return true;
-  }
+  DevArr<signed char> canon;
+  bool ensure(size_t bytes) { return canon.need(bytes, (size_t)1 << 20); }
 };
-std::map<int, PoolLabelDev> g_pool_label_dev;   // by device ordinal; used under the device lock
 
 inline size_t pool_label_lds(const Layout& Y) { return 2 * (size_t)Y.fixlen + (size_t)Y.N * Y.nz * sizeof(double); }
 
@@ -306,7 +295,7 @@ int miqp_solver_canonical_decisions(miqp_solver_t* s, const signed char* decisio
   if (!pool_label_fits(Y, "miqp_solver_canonical_decisions", s->err)) return -3;
   FixedCall call;
   if (call.open(one, 1, Y) != 0) return -3;
-  PoolLabelDev& Q = g_pool_label_dev[call.X->device];
+  PoolLabelDev& Q = call_dev<PoolLabelDev>(call.X->device);
   if (!Q.ensure((size_t)m * fl) || !pool_label_set_lds(Y)) return -3;
   std::vector<signed char> fix((size_t)m * fl, (signed char)-1);
   for (int c = 0; c < m; ++c) std::memcpy(fix.data() + (size_t)c * fl, decisions + (size_t)where[c] * D, D);

@@ -14,10 +14,9 @@
 //   pool_settle_step_kernel     one wavefront per slot: the labelled record against the record it was solved with (16-byte compares, one ballot);
 //                               the labels into the record's own place, the result, the solve count and the moved flag to the record's OWN index -
 //                               the live list is compacted, so this is a scatter by original index
-//   pool_settle_compact_kernel  behind the round's last chunk, ONE workgroup: the exclusive scan of the moved flags in record order, tiles of 256 - a
-//                               wave scan per wavefront, the wavefront totals through LDS, the running total in a register (pool_offsets_kernel's
-//                               pattern) - writes the live list of the next round, ascending by original index whatever the order of arrival, and
-//                               sums the round's iterations
+//   pool_settle_compact_kernel  behind the round's last chunk, ONE workgroup: the exclusive scan of the moved flags in record order, tiles of 256
+//                               (pool_tile_scan of pool_blocks.hip, as pool_offsets_kernel) - writes the live list of the next round, ascending
+//                               by original index whatever the order of arrival, and sums the round's iterations
 // The host waits once per round and reads two words: the live count that sizes the next round, and the iterations.  A round without a live record is
 // not launched.  Owner computes: no atomics, no wavefront waits on another, no scratch.
 // Device memory, cached per device, grown and not shrunk: n x (fixlen + 48) bytes for the n records of a call (labels, last result, solve count,
@@ -52,9 +51,7 @@ __global__ __launch_bounds__(256) void pool_settle_gather_kernel(const PoolSettl
   if (slot >= bc || c0 + slot >= S.n) return;
   const int k = S.live[c0 + slot];
   if ((unsigned)k >= (unsigned)S.n) return;
-  const uint4* src = (const uint4*)S.cur + (size_t)k * chunks;
-  uint4* dst = (uint4*)S.pool_fix + (size_t)slot * chunks;
-  for (int c = lane; c < chunks; c += 64) dst[c] = src[c];
+  pool_stage((uint4*)S.pool_fix + (size_t)slot * chunks, (const uint4*)S.cur + (size_t)k * chunks, chunks, lane);
   if (lane == 0) S.batch_inst[slot] = 0;
 }
 
@@ -64,12 +61,10 @@ __global__ __launch_bounds__(256) void pool_settle_step_kernel(const PoolSettleA
   const int k = S.live[c0 + slot];
   if ((unsigned)k >= (unsigned)S.n) return;
   const int status = S.res[slot].status;
-  const uint4* lab = (const uint4*)S.lab + (size_t)slot * chunks; const uint4* was = (const uint4*)S.pool_fix + (size_t)slot * chunks;
-  bool diff = false;
-  for (int c = lane; c < chunks; c += 64) { const uint4 x = lab[c], y = was[c]; diff = diff || x.x != y.x || x.y != y.y || x.z != y.z || x.w != y.w; }
-  const bool moving = status == 0 && __ballot(diff) != 0ull;   // (the slot is the wavefront's: every lane is here)
+  const uint4* lab = (const uint4*)S.lab + (size_t)slot * chunks;
+  const bool moving = status == 0 && pool_records_differ(lab, (const uint4*)S.pool_fix + (size_t)slot * chunks, chunks, lane);   // (the slot is the wavefront's: every lane is here)
   const bool go = moving && S.round < POOL_PASSES;
-  if (go) { uint4* dst = (uint4*)S.cur + (size_t)k * chunks; for (int c = lane; c < chunks; c += 64) dst[c] = lab[c]; }
+  if (go) pool_stage((uint4*)S.cur + (size_t)k * chunks, lab, chunks, lane);
   if (lane == 0) { pool_settle_copy_result(S.last + k, S.res + slot); S.solves[k] = moving && !go ? -S.round : S.round; S.moved[k] = go ? 1 : 0; S.round_it[k] = S.res[slot].iterations; }
 }
 
@@ -77,19 +72,12 @@ __global__ __launch_bounds__(256) void pool_settle_compact_kernel(const PoolSett
   __shared__ int carry[4], itw[4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int base = 0, it = 0;
-  for (int t0 = 0; t0 < S.n; t0 += 256) {   // (S.n is uniform: every lane meets every barrier)
+  for (int t0 = 0; t0 < S.n; t0 += 256) {   // (S.n is uniform: every thread meets every barrier)
     const int k = t0 + tid;
     const int f = k < S.n && S.moved[k] ? 1 : 0;
     if (k < S.n) { it += S.round_it[k]; S.round_it[k] = 0; }
-    int x = f;
-    for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(x, o, 64); if (lane >= o) x += y; }
-    if (lane == 63) carry[wave] = x;
-    __syncthreads();
-    int before = 0;
-    for (int w = 0; w < 4; ++w) before += w < wave ? carry[w] : 0;
-    if (f) S.live[base + before + x - 1] = k;   // (at most k flags in front of record k: the place is below S.n)
-    base += carry[0] + carry[1] + carry[2] + carry[3];
-    __syncthreads();
+    const int at = pool_tile_scan(f, carry, base);
+    if (f) S.live[at] = k;   // (at most k flags in front of record k: the place is below S.n)
   }
   for (int d = 32; d >= 1; d >>= 1) it += __shfl_xor(it, d, 64);
   if (lane == 0) itw[wave] = it;
@@ -97,38 +85,14 @@ __global__ __launch_bounds__(256) void pool_settle_compact_kernel(const PoolSett
   if (tid == 0) { S.state[0] = base; S.state[1] = itw[0] + itw[1] + itw[2] + itw[3]; }
 }
 
+// (DevArr: grown, not shrunk; the chunk's labels exactly FB_CHUNK records)
 struct PoolSettleDev {
-  signed char* cur = nullptr; size_t cur_cap = 0;
-  miqp_fixed_result_c* last = nullptr; int* solves = nullptr; int* moved = nullptr; int* round_it = nullptr; int* live = nullptr; size_t n_cap = 0;
-  signed char* lab = nullptr; size_t lab_cap = 0; miqp_fixed_result_c* res = nullptr; int* state = nullptr;
+  DevArr<signed char> cur, lab; DevArr<miqp_fixed_result_c> last, res; DevArr<int> solves, moved, round_it, live, state;
   bool ensure(size_t n, size_t fl) {
-    if (!state) HIP_OK(hipMalloc((void**)&state, 2 * sizeof(int)));
-    if (!res) HIP_OK(hipMalloc((void**)&res, (size_t)FB_CHUNK * sizeof(miqp_fixed_result_c)));
-    if (n > n_cap) {
-      if (last) (void)hipFree(last); if (solves) (void)hipFree(solves); if (moved) (void)hipFree(moved); if (round_it) (void)hipFree(round_it); if (live) (void)hipFree(live);
-      last = nullptr; solves = nullptr; moved = nullptr; round_it = nullptr; live = nullptr; n_cap = 0;
-      size_t want = 1024; while (want < n) want <<= 1;
-      HIP_OK(hipMalloc((void**)&last, want * sizeof(miqp_fixed_result_c))); HIP_OK(hipMalloc((void**)&solves, want * sizeof(int))); HIP_OK(hipMalloc((void**)&moved, want * sizeof(int)));
-      HIP_OK(hipMalloc((void**)&round_it, want * sizeof(int))); HIP_OK(hipMalloc((void**)&live, want * sizeof(int)));
-      n_cap = want;   // (set when all five are there: a failure half-way is taken up from the start)
-    }
-    if (n * fl > cur_cap) {
-      if (cur) (void)hipFree(cur);
-      cur = nullptr; cur_cap = 0;
-      size_t want = 1024 * fl; while (want < n * fl) want <<= 1;
-      HIP_OK(hipMalloc((void**)&cur, want));
-      cur_cap = want;
-    }
-    if ((size_t)FB_CHUNK * fl > lab_cap) {
-      if (lab) (void)hipFree(lab);
-      lab = nullptr; lab_cap = 0;
-      HIP_OK(hipMalloc((void**)&lab, (size_t)FB_CHUNK * fl));
-      lab_cap = (size_t)FB_CHUNK * fl;
-    }
-    return true;
+    return state.need(2) && res.need(FB_CHUNK) && last.need(n, 1024) && solves.need(n, 1024) && moved.need(n, 1024) && round_it.need(n, 1024) && live.need(n, 1024) &&
+           cur.need(n * fl, 1024 * fl) && lab.need((size_t)FB_CHUNK * fl);
   }
 };
-std::map<int, PoolSettleDev> g_pool_settle_dev;   // by device ordinal; used under the device lock
 
 // the kernel arguments of a call over n records (n <= the capacity `ensure` was asked for)
 PoolSettleArgs pool_settle_args(const PoolSettleDev& Q, const DevBuf& B, const Layout& Y, int n) {
@@ -216,7 +180,7 @@ int miqp_solver_settle_decisions(miqp_solver_t* s, const signed char* decisions,
   FixedCall call;
   if (call.open(one, 1, Y) != 0) return -3;
   DevCtx& X = *call.X;
-  PoolSettleDev& Q = g_pool_settle_dev[X.device]; PoolImproveDev& R = g_pool_improve_dev[X.device];
+  PoolSettleDev& Q = call_dev<PoolSettleDev>(X.device); PoolImproveDev& R = call_dev<PoolImproveDev>(X.device);
   std::vector<signed char> fix((size_t)m * fl, (signed char)-1);
   for (int c = 0; c < m; ++c) std::memcpy(fix.data() + (size_t)c * fl, decisions + (size_t)where[c] * D, D);
   std::vector<miqp_fixed_result_c> last(m); std::vector<int> cnt(m);

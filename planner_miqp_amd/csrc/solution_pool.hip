@@ -67,23 +67,6 @@ __global__ __launch_bounds__(256) void pool_compact_kernel(const PoolArgs A) {
   if (is) { const int p = base + __popcll(m & ((1ull << lane) - 1ull)); if (p < A.list_cap) A.list[p] = k; }
 }
 
-// bytes of two records of `chunks` 16-byte pieces, as unsigned: < 0, 0, > 0 (the whole wavefront calls; a in LDS or HBM, b in HBM)
-__device__ inline int pool_cmp(const uint4* a, const uint4* b, int chunks, int lane) {
-  for (int c0 = 0; c0 < chunks; c0 += 64) {
-    const int c = c0 + lane; int sign = 0;
-    if (c < chunks) {
-      const uint4 x = a[c], y = b[c];
-      if (x.x != y.x || x.y != y.y || x.z != y.z || x.w != y.w) {
-        const unsigned char* p = (const unsigned char*)&x; const unsigned char* q = (const unsigned char*)&y;
-        for (int t = 15; t >= 0; --t) if (p[t] != q[t]) sign = p[t] < q[t] ? -1 : 1;
-      }
-    }
-    const unsigned long long m = __ballot(sign != 0);
-    if (m) return __shfl(sign, __ffsll((long long)m) - 1, 64);
-  }
-  return 0;
-}
-
 __global__ __launch_bounds__(64) void pool_merge_kernel(const PoolArgs A) {
   extern __shared__ uint4 cand[];   // the candidate's record, mask bytes reset
   const int lane = threadIdx.x;
@@ -152,39 +135,7 @@ __global__ __launch_bounds__(64) void pool_merge_kernel(const PoolArgs A) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------- manoeuvre filter
-constexpr int POOL_FAM_REGION = 1, POOL_FAM_ENVIRONMENT = 2, POOL_FAM_OBSTACLE = 4, POOL_FAM_CAR_CAR = 8, POOL_FAM_TIMING = 16, POOL_FAM_ALL = 31;
-
-// the sites of a decision record - one disjunction followed along the horizon: the byte of step i of a site lies at first + i * step
-struct PoolDims { int C, N, O, NP; };
-struct PoolSite { int first, step, family; };
-__host__ __device__ inline int pool_declen(const PoolDims& d) { return d.C * d.N * 6 + d.C * d.O * d.N * 5 + d.NP * d.N * 4; }
-__host__ __device__ inline int pool_sites(const PoolDims& d) { return d.C * 6 + d.C * d.O * 5 + d.NP * 4; }
-__host__ __device__ inline PoolSite pool_site(const PoolDims& d, int s) {
-  const int f_env = d.C * d.N, f_obs = f_env + d.C * d.N * 5, f_c2c = f_obs + d.C * d.O * d.N * 5;
-  if (s < d.C) return PoolSite{s * d.N, 1, POOL_FAM_REGION};
-  s -= d.C;
-  if (s < d.C * 5) return PoolSite{f_env + (s / 5) * d.N * 5 + s % 5, 5, POOL_FAM_ENVIRONMENT};
-  s -= d.C * 5;
-  if (s < d.C * d.O * 5) return PoolSite{f_obs + (s / 5) * d.N * 5 + s % 5, 5, POOL_FAM_OBSTACLE};
-  s -= d.C * d.O * 5;
-  return PoolSite{f_c2c + (s >> 2) * d.N * 4 + (s & 3), 4, POOL_FAM_CAR_CAR};
-}
-// the signature bytes of ONE site (sg is -1 there before): with the timing bit its bytes as they are, step 0 included; without it the alternatives of
-// steps 1 .. N - 1 in their order, undecided bytes skipped, repeats collapsed, left-packed from step 1 - of a region byte the possible-region index
-// (byte >> 2: the low two bits are the half-plane or slow alternative)
-__host__ __device__ inline void pool_site_signature(const PoolDims& d, int fam, int s, const signed char* rec, signed char* sg) {
-  const PoolSite t = pool_site(d, s);
-  if (!(fam & t.family)) return;
-  if (fam & POOL_FAM_TIMING) { for (int i = 0; i < d.N; ++i) sg[t.first + i * t.step] = rec[t.first + i * t.step]; return; }
-  int last = -1, w = 0;
-  for (int i = 1; i < d.N; ++i) {
-    int v = rec[t.first + i * t.step];
-    if (v < 0) continue;
-    if (t.family == POOL_FAM_REGION) v >>= 2;
-    if (v != last) { w++; sg[t.first + w * t.step] = (signed char)v; last = v; }
-  }
-}
-
+// (the families, the sites of a record and the signature of a site: pool_blocks.hip)
 struct PoolFilterArgs { PoolArgs A; signed char* sig; const int* fam; PoolDims dims; };
 
 // pool_merge_kernel with the filter: the same launch (one wavefront per instance in flight, owner computes, ballot over 64 list entries), the same
@@ -201,7 +152,7 @@ __global__ __launch_bounds__(64) void pool_filter_kernel(const PoolFilterArgs F)
   const int K = min(A.cap[inst], A.stride);
   if (K <= 0) return;
   const int fam = F.fam[inst] & POOL_FAM_ALL;
-  const int m = min(A.count[A.par], min(A.bc, A.list_cap)), chunks = A.fixlen >> 4, nsites = pool_sites(F.dims);
+  const int m = min(A.count[A.par], min(A.bc, A.list_cap)), chunks = A.fixlen >> 4;
   uint4* const csig = fam ? cand + chunks : cand;
   uint4* const rec = (uint4*)(A.fix + (size_t)inst * A.stride * A.fixlen);
   uint4* const sig = fam ? (uint4*)(F.sig + (size_t)inst * A.stride * A.fixlen) : rec;
@@ -225,11 +176,7 @@ __global__ __launch_bounds__(64) void pool_filter_kernel(const PoolFilterArgs F)
         }
         for (int o = 32; o > 0; o >>= 1) h += __shfl_xor(h, o, 64);
       }
-      __syncthreads();
-      if (fam) {
-        for (int s = lane; s < nsites; s += 64) pool_site_signature(F.dims, fam, s, (const signed char*)cand, (signed char*)csig);
-        __syncthreads();
-      }
+      if (fam) pool_sign(F.dims, fam, cand, csig, lane); else __syncthreads();
       const unsigned int hs = (unsigned int)h; const double o = A.batch_obj[node]; const unsigned long long ok = d2key(o);
       // an entry of this signature already kept: the smaller of the two in the pool's order stays (and moves to its new place)
       int dup = -1;
@@ -294,10 +241,7 @@ inline bool pool_same_entry(const Layout& Y, int fam, const signed char* a, cons
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host: capture
-template <class Tp> bool pool_alloc(DevCtx& X, Tp** p, size_t n) {
-  if (*p) { for (auto it = X.allocs.begin(); it != X.allocs.end(); ++it) if (*it == (void*)*p) { X.allocs.erase(it); break; } (void)hipFree(*p); *p = nullptr; }
-  return X.alloc(p, n);
-}
+template <class Tp> bool pool_alloc(DevCtx& X, Tp** p, size_t n) { X.drop(p); return X.alloc(p, n); }
 
 bool pool_prepare(DevCtx& X, miqp_solver_t* const* S, int n) {
   int stride = 0; bool filt = false;   // (a filter counts only on a handle that has a pool)

@@ -4,10 +4,11 @@
   MIQP_GPU_LIB=<library> python tools/fixed_calls_dump.py OUT
 
 Two builds of the library compute the same thing exactly when their files are identical.  Per seed 0 .. 3 of cfg4 (gap 1e-4, pool capacity 8,
-filter 12), on fresh wrappers: the solve; solveDecisions of the found decisions; solveSolutionPool and every pool record; solveFixedBatch of
-those records repeated to fixed_batch_chunk() + 3 entries; the climb at 8 passes; the explore at 4 passes; the refinement again.  Then the three
-calls over many handles - refinement, climb, fix records - on twin wrappers of all seeds.  A line covers the returned arrays, best, decision
-bytes, record bytes and last_timing[2 .. 5] of the step.  Needs an MI355X and no oracle."""
+filter 12), on fresh wrappers: the solve; solveDecisions, canonicalDecisions and settleDecisions of the found decisions; solveSolutionPool and
+every pool record; solveFixedBatch of those records repeated to fixed_batch_chunk() + 3 entries; the climb at 8 passes; the explore at 4 passes;
+the refinement again; the distinct and the settled explore at 4 passes, each on a fresh solve.  Then the three calls over many handles -
+refinement, climb, fix records - on twin wrappers of all seeds.  A line covers the returned arrays, best, `added`, decision bytes, record bytes
+or pool bytes, and last_timing[2 .. 5] of the step.  Needs an MI355X and no oracle."""
 import ctypes as C
 import hashlib
 import os
@@ -71,6 +72,12 @@ def main():
         res = w.solveDecisions(dec)
         assert res[0] == 0
         emit("seed%d solve_decisions" % seed, *fixed_parts(w, res[1:]))
+        res = w.canonicalDecisions(dec)
+        assert res[0] == 0
+        emit("seed%d canonical_decisions" % seed, *res[1:6], np.array([res[6]]), res[7], pool_bytes(w), timing(w))
+        res = w.settleDecisions(dec)
+        assert res[0] == 0
+        emit("seed%d settle_decisions" % seed, *res[1:6], np.array([res[6]]), res[7], res[8], pool_bytes(w), timing(w))
         res, recs = refine(w)
         emit("seed%d pool_solve" % seed, *refine_parts(w, res, recs))
         records = [r for rc, r in recs if rc == 0]
@@ -86,6 +93,11 @@ def main():
         emit("seed%d pool_explore" % seed, np.array([rc]), repr([sorted(a.items()) for a in added]).encode(), pool_bytes(w), timing(w))
         res, recs = refine(w)
         emit("seed%d pool_solve again" % seed, *refine_parts(w, res, recs))
+        for mode in ("distinct", "settled"):
+            w = solved(seed)
+            rc, added = w.exploreSolutionPool(4, **{mode: True})
+            assert rc >= 0
+            emit("seed%d pool_explore %s" % (seed, mode), np.array([rc]), repr([sorted(a.items()) for a in added]).encode(), pool_bytes(w), timing(w))
 
     ws = [solved(seed) for seed in SEEDS]
     for h, res in enumerate(P.solve_solution_pools(ws)):
