@@ -519,6 +519,43 @@ int miqp_gpu_pool_settle_passes(void);
  * out[2] does not count pass 0. */
 int miqp_solver_pool_explore_settled(miqp_solver_t* s, int max_passes, double max_rel, miqp_pool_explore_c* out, int cap);
 
+/* ---- the free places of MANY handles filled in one device call.  Opt-in and new: the three calls above stay what they are. ----
+ * mode: the admission, one of the three the single calls have */
+#define MIQP_POOL_EXPLORE_PLAIN 0     /* miqp_solver_pool_explore */
+#define MIQP_POOL_EXPLORE_DISTINCT 1  /* miqp_solver_pool_explore_distinct */
+#define MIQP_POOL_EXPLORE_SETTLED 2   /* miqp_solver_pool_explore_settled */
+/* All handles start pass 1 together; one pass of the call is one pass of every handle that is still adding, and the neighbours of all of them
+ * fill common launch groups.  max_passes and max_rel are common; obj0, the capacity, the filter and the edge count are each handle's own.
+ * out[h * cap + k] is the k-th entry added to handle h, counts[h] their number.  PER HANDLE the call answers bit for bit what the single call of
+ * that mode answers for the handle alone: the added records (parent, pass, jump, iterations, objective, reserved), the pool afterwards (old
+ * entries untouched and in place), the dropped refined pool, miqp_solver_last_timing out[2 .. 5] (passes in which the handle had neighbours, its
+ * solves, their iterations, "still adding") and miqp_solver_last_error, the "last of N passes still added" text included.  out[0] and out[1] of
+ * miqp_solver_last_timing are the CALL's.
+ * A handle whose pool is empty or full takes no part WHATEVER ITS FILTER: counts[h] = 0, its pool and last timing stay, its last error is
+ * cleared.  This is the one difference to the single call, which checks the filter first and refuses such a handle with -2.
+ * Returns the number of entries added in all.  -1: NULL arrays, n <= 0, cap < 0, max_rel a NaN, mode outside 0 .. 2, a NULL handle, a handle
+ * without an instance, a handle named twice, or a kept pool whose record length is not the common Layout's.  -2: max_passes outside 1 .. 64;
+ * handles that do not share a shape or name different devices (as miqp_solver_solve_fixed_multi refuses them, with its text as the handles' last
+ * error); a handle that has entries and free places under a filter outside 1 .. 15 or with neither the obstacle nor the car/car family (its
+ * miqp_solver_last_error names it); cap below the largest number of free places among the handles that take part.  -5: more than 4096 handles
+ * (65536 / 16 places).  -3: no device / kernel image / HIP error, or the LDS refusals of the single call of that mode (the handles that take part
+ * then carry its text).  All but -3 are found before a device is touched; on EVERY failure out, counts and every pool are untouched.  A call in
+ * which no handle takes part returns 0 (counts all 0) without touching a device.  miqp_solver_last_error of every handle is cleared once nothing
+ * of the above but -3 refuses the call.
+ * Device memory: 16 places per handle x (3 records + miqp_gpu_pool_moves_max() x 16 bytes + a few words), and the records of pass 0 of the
+ * settled mode (the kept entries of all handles), beside the fixed slice buffers of 8192 neighbours; it does not grow with the neighbours of a pass.
+ * No reference counterpart. */
+int miqp_solver_pool_explore_multi(miqp_solver_t* const* solvers, int n, int mode, int max_passes, double max_rel, miqp_pool_explore_c* out, int cap, int* counts);
+/* the SLICES of a pass of that call: results, labels and settle words are kept a slice at a time, a slice being a run of WHOLE handles whose
+ * neighbours of the pass fit 8192.  handle_totals[h], h < n: the neighbours of handle h in the pass, 0 .. 8192.  Slices are formed greedily in handle
+ * order: a handle opens a new slice when its neighbours do not fit what is left of the current one; a handle without neighbours rides along.
+ * slice_first[s] receives the first handle of slice s, slice_first[nslices] = n.  Returns nslices (>= 1); -1 NULL pointers, n <= 0 or cap < 0; -2 a
+ * total outside 0 .. 8192; -3 cap < nslices + 1 (nothing is written).  Pure host code - no handle, no device - and the function the host loop of
+ * miqp_solver_pool_explore_multi itself calls. */
+int miqp_gpu_pool_explore_plan(const int* handle_totals, int n, int* slice_first, int cap);
+/* diagnostic: the passes and the slices the calling thread's last successful miqp_solver_pool_explore_multi ran on the device (either may be NULL) */
+void miqp_gpu_pool_explore_multi_last(int* passes, int* slices);
+
 /* 1 when instances of this shape (NrCars, N) have the dual active-set launches - one or two cars, a horizon of up to 20 steps - else 0 (their node
  * relaxations are interior point solves).  Pure host code: no device is needed or touched.  A call switches the launches off with MIQP_AS=0 */
 int miqp_gpu_has_active_set(int num_cars, int num_steps);

@@ -19,8 +19,8 @@
 //                               by original index whatever the order of arrival, and sums the round's iterations
 // The host waits once per round and reads two words: the live count that sizes the next round, and the iterations.  A round without a live record is
 // not launched.  Owner computes: no atomics, no wavefront waits on another, no scratch.
-// Device memory, cached per device, grown and not shrunk: n x (fixlen + 48) bytes for the n records of a call (labels, last result, solve count,
-// moved flag, iterations, live list) and FB_CHUNK x (fixlen + 32) for a chunk's labels and results; the chunk's trajectory rows are the climb's.
+// Device memory, cached per device, grown and not shrunk: n x (fixlen + 56) bytes for the n records of a call (labels, last result, solve count,
+// moved flag, iterations of the round and of all rounds, instance, live list) and FB_CHUNK x (fixlen + 32) for a chunk's labels and results; the chunk's trajectory rows are the climb's.
 #pragma once
 
 namespace {
@@ -31,6 +31,8 @@ struct PoolSettleArgs {
   int* solves;                      // [n] solves of record k so far; -POOL_PASSES: still moving behind the last one
   int* moved;                       // [n] record k is live in the next round
   int* round_it;                    // [n] iterations of record k's solve in this round (0 when it was not live)
+  int* acc_it;                      // [n] iterations of record k's solves of the rounds so far: the compaction sums a round over the whole call, the explore of many handles sums these per handle
+  int* inst;                        // [n] the instance of record k in the call: its handle's index
   int* live;                        // [n] the live list: original indices, ascending
   int* state;                       // [0] live records of the next round, [1] iterations of the round
   signed char* pool_fix; int* batch_inst;   // the chain's fix records and instances: slot k of the chunk
@@ -52,7 +54,7 @@ __global__ __launch_bounds__(256) void pool_settle_gather_kernel(const PoolSettl
   const int k = S.live[c0 + slot];
   if ((unsigned)k >= (unsigned)S.n) return;
   pool_stage((uint4*)S.pool_fix + (size_t)slot * chunks, (const uint4*)S.cur + (size_t)k * chunks, chunks, lane);
-  if (lane == 0) S.batch_inst[slot] = 0;
+  if (lane == 0) S.batch_inst[slot] = S.inst[k];
 }
 
 __global__ __launch_bounds__(256) void pool_settle_step_kernel(const PoolSettleArgs S, int c0, int bc) {
@@ -65,7 +67,7 @@ __global__ __launch_bounds__(256) void pool_settle_step_kernel(const PoolSettleA
   const bool moving = status == 0 && pool_records_differ(lab, (const uint4*)S.pool_fix + (size_t)slot * chunks, chunks, lane);   // (the slot is the wavefront's: every lane is here)
   const bool go = moving && S.round < POOL_PASSES;
   if (go) pool_stage((uint4*)S.cur + (size_t)k * chunks, lab, chunks, lane);
-  if (lane == 0) { pool_settle_copy_result(S.last + k, S.res + slot); S.solves[k] = moving && !go ? -S.round : S.round; S.moved[k] = go ? 1 : 0; S.round_it[k] = S.res[slot].iterations; }
+  if (lane == 0) { pool_settle_copy_result(S.last + k, S.res + slot); S.solves[k] = moving && !go ? -S.round : S.round; S.moved[k] = go ? 1 : 0; S.round_it[k] = S.res[slot].iterations; S.acc_it[k] += S.res[slot].iterations; }
 }
 
 __global__ __launch_bounds__(256) void pool_settle_compact_kernel(const PoolSettleArgs S) {
@@ -87,9 +89,9 @@ __global__ __launch_bounds__(256) void pool_settle_compact_kernel(const PoolSett
 
 // (DevArr: grown, not shrunk; the chunk's labels exactly FB_CHUNK records)
 struct PoolSettleDev {
-  DevArr<signed char> cur, lab; DevArr<miqp_fixed_result_c> last, res; DevArr<int> solves, moved, round_it, live, state;
+  DevArr<signed char> cur, lab; DevArr<miqp_fixed_result_c> last, res; DevArr<int> solves, moved, round_it, acc_it, inst, live, state;
   bool ensure(size_t n, size_t fl) {
-    return state.need(2) && res.need(FB_CHUNK) && last.need(n, 1024) && solves.need(n, 1024) && moved.need(n, 1024) && round_it.need(n, 1024) && live.need(n, 1024) &&
+    return state.need(2) && res.need(FB_CHUNK) && last.need(n, 1024) && solves.need(n, 1024) && moved.need(n, 1024) && round_it.need(n, 1024) && acc_it.need(n, 1024) && inst.need(n, 1024) && live.need(n, 1024) &&
            cur.need(n * fl, 1024 * fl) && lab.need((size_t)FB_CHUNK * fl);
   }
 };
@@ -97,7 +99,7 @@ struct PoolSettleDev {
 // the kernel arguments of a call over n records (n <= the capacity `ensure` was asked for)
 PoolSettleArgs pool_settle_args(const PoolSettleDev& Q, const DevBuf& B, const Layout& Y, int n) {
   PoolSettleArgs S;
-  S.cur = Q.cur; S.last = Q.last; S.solves = Q.solves; S.moved = Q.moved; S.round_it = Q.round_it; S.live = Q.live; S.state = Q.state;
+  S.cur = Q.cur; S.last = Q.last; S.solves = Q.solves; S.moved = Q.moved; S.round_it = Q.round_it; S.acc_it = Q.acc_it; S.inst = Q.inst; S.live = Q.live; S.state = Q.state;
   S.pool_fix = B.pool_fix; S.batch_inst = B.batch_inst; S.lab = Q.lab; S.res = Q.res; S.fixlen = Y.fixlen; S.n = n; S.round = 0;
   return S;
 }
@@ -116,7 +118,8 @@ bool pool_settle_compact(DevCtx& X, const PoolSettleArgs& S, int& live, PoolSett
   return true;
 }
 
-// Rounds `first` .. POOL_PASSES over the `live` records of the list in S.live.  Bp: fixed_chain_settings; Z: the rows of one chunk.  false: HIP error
+// Rounds `first` .. POOL_PASSES over the `live` records of the list in S.live, whose instances are among the call's.  Bp: fixed_chain_settings; Z: the
+// rows of one chunk.  false: HIP error
 bool pool_settle_rounds(const FixedCall& call, const DevBuf& Bp, PoolSettleArgs S, double* Z, int first, int live, PoolSettleTally& T) {
   DevCtx& X = *call.X; const Layout& Y = call.Y; hipStream_t st = X.stream;
   for (int p = first; p <= POOL_PASSES && live > 0; ++p) {
@@ -125,8 +128,8 @@ bool pool_settle_rounds(const FixedCall& call, const DevBuf& Bp, PoolSettleArgs 
       const int bc = std::min(FB_CHUNK, live - c0);
       hipLaunchKernelGGL(pool_settle_gather_kernel, dim3((bc + 3) / 4), dim3(256), 0, st, S, c0, bc);
       HIP_OK(hipGetLastError());
-      if (!fixed_chunk(X, Bp, Y, call.dev(), 1, FixedChunk{bc, c0, S.res, Z})) return false;
-      if (!pool_label_chunk(X, Y, 1, bc, S.res, Z, S.lab)) return false;
+      if (!fixed_chunk(X, Bp, Y, call.dev(), call.n, FixedChunk{bc, c0, S.res, Z})) return false;
+      if (!pool_label_chunk(X, Y, call.n, bc, S.res, Z, S.lab)) return false;
       hipLaunchKernelGGL(pool_settle_step_kernel, dim3((bc + 3) / 4), dim3(256), 0, st, S, c0, bc);
       HIP_OK(hipGetLastError());
       T.groups++;
@@ -137,14 +140,17 @@ bool pool_settle_rounds(const FixedCall& call, const DevBuf& Bp, PoolSettleArgs 
   return true;
 }
 
-// n records (fix bytes on the host) settled from round 1: uploads them, resets the per-record words, runs the rounds.  false: HIP error
-bool pool_settle_records(const FixedCall& call, const DevBuf& Bp, const PoolSettleArgs& S, double* Z, const signed char* fix, bool on_device, PoolSettleTally& T) {
+// n records (fix bytes on the host) settled from round 1: uploads them, resets the per-record words, runs the rounds.  inst (host; NULL: all of
+// instance 0): the instance of every record.  false: HIP error
+bool pool_settle_records(const FixedCall& call, const DevBuf& Bp, const PoolSettleArgs& S, double* Z, const signed char* fix, const int* inst, PoolSettleTally& T) {
   hipStream_t st = call.X->stream; const size_t fl = (size_t)call.Y.fixlen;
   std::vector<int> ident(S.n); for (int k = 0; k < S.n; ++k) ident[k] = k;
-  HIP_OK(hipMemcpyAsync(S.cur, fix, (size_t)S.n * fl, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(S.cur, fix, (size_t)S.n * fl, hipMemcpyHostToDevice, st));
+  if (inst) HIP_OK(hipMemcpyAsync(S.inst, inst, (size_t)S.n * sizeof(int), hipMemcpyHostToDevice, st));
+  else HIP_OK(hipMemsetAsync(S.inst, 0, (size_t)S.n * sizeof(int), st));
   HIP_OK(hipMemcpyAsync(S.live, ident.data(), (size_t)S.n * sizeof(int), hipMemcpyHostToDevice, st));
   HIP_OK(hipMemsetAsync(S.round_it, 0, (size_t)S.n * sizeof(int), st)); HIP_OK(hipMemsetAsync(S.moved, 0, (size_t)S.n * sizeof(int), st));
-  HIP_OK(hipMemsetAsync(S.solves, 0, (size_t)S.n * sizeof(int), st));
+  HIP_OK(hipMemsetAsync(S.solves, 0, (size_t)S.n * sizeof(int), st)); HIP_OK(hipMemsetAsync(S.acc_it, 0, (size_t)S.n * sizeof(int), st));
   HIP_OK(hipStreamSynchronize(st));   // (ident is a local)
   return pool_settle_rounds(call, Bp, S, Z, 1, S.n, T);
 }
@@ -190,7 +196,7 @@ int miqp_solver_settle_decisions(miqp_solver_t* s, const signed char* decisions,
     const DevBuf Bp = fixed_chain_settings(X.B);
     const PoolSettleArgs S = pool_settle_args(Q, X.B, Y, m);
     HIP_OK(hipEventRecord(X.ev0, X.stream));
-    if (!pool_settle_records(call, Bp, S, R.Z, fix.data(), false, tally)) return false;
+    if (!pool_settle_records(call, Bp, S, R.Z, fix.data(), nullptr, tally)) return false;
     HIP_OK(hipEventRecord(X.ev1, X.stream));
     HIP_OK(hipMemcpyAsync(last.data(), Q.last, (size_t)m * sizeof(miqp_fixed_result_c), hipMemcpyDeviceToHost, X.stream));
     HIP_OK(hipMemcpyAsync(cnt.data(), Q.solves, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, X.stream));

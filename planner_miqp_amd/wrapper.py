@@ -135,6 +135,11 @@ def load_library():
     L.miqp_solver_settle_decisions.restype = C.c_int
     L.miqp_solver_settle_decisions.argtypes = [vp, C.POINTER(C.c_byte), C.c_int, C.POINTER(FixedResultC), C.POINTER(C.c_byte), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.miqp_solver_pool_explore_settled.restype = C.c_int; L.miqp_solver_pool_explore_settled.argtypes = [vp, C.c_int, C.c_double, C.POINTER(PoolExploreC), C.c_int]
+    L.miqp_solver_pool_explore_multi.restype = C.c_int
+    L.miqp_solver_pool_explore_multi.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(PoolExploreC), C.c_int, C.POINTER(C.c_int)]
+    L.miqp_gpu_pool_explore_plan.restype = C.c_int
+    L.miqp_gpu_pool_explore_plan.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_int]
+    L.miqp_gpu_pool_explore_multi_last.restype = None; L.miqp_gpu_pool_explore_multi_last.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.miqp_gpu_pool_settle_passes.restype = C.c_int; L.miqp_gpu_pool_settle_passes.argtypes = []
     L.miqp_solver_canonical_labels.restype = C.c_int
     L.miqp_solver_canonical_labels.argtypes = [vp, C.POINTER(C.c_byte), c_double_p, C.c_int, C.c_int, C.POINTER(C.c_byte)]
@@ -182,7 +187,8 @@ EXPORTED_SYMBOLS = ["miqp_solver_create", "miqp_solver_destroy", "miqp_solver_se
                     "miqp_solver_pool_improve_multi", "miqp_gpu_pool_improve_plan",
                     "miqp_gpu_pool_jumps", "miqp_gpu_pool_explore_size", "miqp_solver_pool_explore",
                     "miqp_solver_canonical_decisions", "miqp_solver_canonical_labels", "miqp_solver_pool_explore_distinct",
-                    "miqp_solver_settle_decisions", "miqp_solver_pool_explore_settled", "miqp_gpu_pool_settle_passes"]
+                    "miqp_solver_settle_decisions", "miqp_solver_pool_explore_settled", "miqp_gpu_pool_settle_passes",
+                    "miqp_solver_pool_explore_multi", "miqp_gpu_pool_explore_plan", "miqp_gpu_pool_explore_multi_last"]
 
 
 # a row of CplexWrapper.launchPlan (NodeLaunch in csrc/miqp_gpu.hip)
@@ -714,8 +720,7 @@ class CplexWrapper:
         out = (PoolExploreC * n)()
         call = self._L.miqp_solver_pool_explore_settled if settled else self._L.miqp_solver_pool_explore_distinct if distinct else self._L.miqp_solver_pool_explore
         rc = int(call(self._h, int(max_passes), float(max_rel), out, n))
-        return rc, [dict(parent=o.parent, **{"pass": o.pass_}, first=o.first, stride=o.stride, count=o.count, value=o.value, iterations=o.iterations,
-                         objective=float(o.objective), **({"solves": o.reserved} if settled else {})) for o in out[:max(rc, 0)]]
+        return rc, _explore_dicts(out[:max(rc, 0)], settled)
 
     def solveDecisions(self, decisions):
         """the continuous QPs of many DECISION records of this wrapper's instance in one device call (miqp_solver_solve_decisions): ``decisions`` is
@@ -1000,6 +1005,59 @@ def pool_improve_plan(move_counts):
     if ns < 1:
         raise RuntimeError("miqp_gpu_pool_improve_plan failed (%d)" % ns)
     return [int(x) for x in first[:ns + 1]]
+
+
+POOL_EXPLORE_PLAIN, POOL_EXPLORE_DISTINCT, POOL_EXPLORE_SETTLED = 0, 1, 2   # MIQP_POOL_EXPLORE_* (include/miqp_gpu.h): the admission of explore_solution_pools
+
+
+def _explore_dicts(records, settled):
+    return [dict(parent=o.parent, **{"pass": o.pass_}, first=o.first, stride=o.stride, count=o.count, value=o.value, iterations=o.iterations,
+                 objective=float(o.objective), **({"solves": o.reserved} if settled else {})) for o in records]
+
+
+def explore_solution_pools(wrappers, max_passes=4, max_rel=-1.0, distinct=False, settled=False):
+    """the free places of the solution pools of many wrappers filled with neighbouring manoeuvre classes in one device call
+    (miqp_solver_pool_explore_multi): per wrapper (added_count, [dicts]) - what its own exploreSolutionPool(max_passes, max_rel, distinct, settled)
+    returns, bit for bit, pool, last timing [2 .. 5] and lastError() behind it included.  All wrappers start pass 1 together and the neighbours of
+    a pass fill common launch groups.  The wrappers may differ in filter and capacity; one whose pool is empty or full takes no part whatever its
+    filter and gets (0, []).  ``distinct`` and ``settled`` together raise ValueError.  Raises RuntimeError where the library refuses the call
+    (wrappers of different shape, a wrapper with entries and free places under a filter the explore cannot jump under, no device), on -2 with the
+    first non-empty lastError() among the wrappers; a refused call leaves every pool alone."""
+    if distinct and settled:
+        raise ValueError("distinct and settled are two admissions: choose one")
+    L = load_library()
+    n = len(wrappers)
+    cap = pool_max()
+    out = (PoolExploreC * (max(n, 1) * cap))()
+    counts = (C.c_int * max(n, 1))()
+    hs = (C.c_void_p * max(n, 1))(*[w._h for w in wrappers])
+    mode = POOL_EXPLORE_SETTLED if settled else POOL_EXPLORE_DISTINCT if distinct else POOL_EXPLORE_PLAIN
+    rc = L.miqp_solver_pool_explore_multi(hs, n, mode, int(max_passes), float(max_rel), out, cap, counts)
+    if rc < 0:
+        why = next((w.lastError() for w in wrappers if w.lastError()), "") if rc == -2 else ""   # (a handle with a filter without jumps is named in ITS last error)
+        raise RuntimeError("miqp_solver_pool_explore_multi failed (%d)%s" % (rc, ": " + why if why else ""))
+    return [(int(counts[h]), _explore_dicts(out[h * cap:h * cap + counts[h]], settled)) for h in range(n)]
+
+
+def pool_explore_plan(handle_totals):
+    """the slices of a pass of explore_solution_pools for these per-wrapper neighbour totals (miqp_gpu_pool_explore_plan): the list slice_first,
+    entry s the first wrapper of slice s and the last one len(handle_totals) - runs of whole wrappers whose neighbours fit 8192 results, formed
+    greedily in order; a wrapper without neighbours rides along.  Needs no device."""
+    c = np.ascontiguousarray(handle_totals, dtype=np.int32)
+    if c.ndim != 1 or c.size == 0:
+        raise ValueError("a non-empty vector of neighbour totals expected")
+    first = np.zeros(c.size + 2, dtype=np.int32)
+    ns = load_library().miqp_gpu_pool_explore_plan(c.ctypes.data_as(C.POINTER(C.c_int)), c.size, first.ctypes.data_as(C.POINTER(C.c_int)), first.size)
+    if ns < 1:
+        raise RuntimeError("miqp_gpu_pool_explore_plan failed (%d)" % ns)
+    return [int(x) for x in first[:ns + 1]]
+
+
+def pool_explore_multi_last():
+    """(passes, slices) the calling thread's last explore_solution_pools ran on the device (miqp_gpu_pool_explore_multi_last)"""
+    p, s = C.c_int(0), C.c_int(0)
+    load_library().miqp_gpu_pool_explore_multi_last(C.byref(p), C.byref(s))
+    return p.value, s.value
 
 
 def certify_last_timing():
