@@ -300,6 +300,19 @@ class CplexWrapper {
     added.resize(rc > 0 ? (size_t)rc : 0);
     return rc;
   }
+  // carrySolutionPool: the kept entries of src - the wrapper of the cycle `shift` steps ago - shifted, re-expressed in this instance's alternatives,
+  // settled here and admitted to this pool's free places when their class is new (miqp_solver_pool_carry); returns the number added, < 0 on failure
+  // (both pools are untouched then).  records: one miqp_pool_carry_c per SOURCE entry (status 0 admitted .. 6 no place free).  This wrapper's
+  // parameters must be loaded (a solve, or poolSignature / solveDecisions before); an empty pool takes the best carried record as its entry 0.
+  int carrySolutionPool(const CplexWrapper& src, int shift = 1, double max_rel = -1.0, std::vector<miqp_pool_carry_c>* records = nullptr) {
+    std::vector<miqp_pool_carry_c> out((size_t)miqp_gpu_pool_max(), miqp_pool_carry_c{-1, -1, 0, 0, 0, 0, std::nan("")});
+    if (records) records->clear();
+    if (!h_ || !src.h_) return -1;
+    const int rc = miqp_solver_pool_carry(h_, src.h_, shift, max_rel, out.data(), (int)out.size());
+    if (rc >= 0 && records)
+      for (const miqp_pool_carry_c& o : out) if (o.status >= 0) records->push_back(o);
+    return rc;
+  }
   SolutionProperties getSolutionProperties() const { return solutionProperties_; }
   void setDebugOutputPrint(bool v) { print_debug_outputs_ = v; }
   void setDebugOutputFilePath(std::string in) { debugOutputFilePath_ = in; }

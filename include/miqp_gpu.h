@@ -556,6 +556,56 @@ int miqp_gpu_pool_explore_plan(const int* handle_totals, int n, int* slice_first
 /* diagnostic: the passes and the slices the calling thread's last successful miqp_solver_pool_explore_multi ran on the device (either may be NULL) */
 void miqp_gpu_pool_explore_multi_last(int* passes, int* slices);
 
+/* ---- the kept manoeuvres of one planning cycle CARRIED into the pool of the next.  Opt-in and new: nothing changes unless it is
+ * called.  A receding-horizon caller solves a new instance every cycle and miqp_solver_set_params empties the pool; the carry is the pool's
+ * counterpart of miqp_calculate_warmstart (a CPLEX user would re-add the members of the old pool as MIP starts of the new model). ----
+ *
+ * The SHIFT of a record of D decision bytes (the layout of miqp_solver_pool_found_decisions) by `shift` steps: for every site and every step
+ * i = 1 .. steps - 1 the byte of `out` is the byte of `decisions` at step min(i + shift, steps - 1) - the last decided state is held -, re-expressed
+ * for the destination instance: a region byte q * 4 + h becomes region_map[c * p_src + q] * 4 + h (c the car; h, the half-plane or slow alternative,
+ * is kept); an environment byte e becomes env_map[e], -1 (undecided) where the map says so; obstacle and car/car bytes are kept - obstacle o of the
+ * destination is obstacle o of the source `shift` steps later: the caller's contract.  Negative bytes stay -1, step 0 of every site is -1, bytes of
+ * `out` behind D are -1.  A NULL map is the identity.  A region byte whose target is -1 makes the whole record UNMAPPABLE: the return value is -4 and
+ * `out` is written all the same, with -1 at those bytes.  Returns D; -1 NULL pointers or non-positive dimensions, -2 shift outside 1 .. steps - 2,
+ * -3 len < D.  Pure host code - no handle, no device - and the very function pool_shift_kernel compiles. */
+int miqp_gpu_pool_shift(int cars, int steps, int obstacles, int shift, const int* region_map, int p_src, const int* env_map, int e_src, const signed char* decisions,
+                        signed char* out, int len);
+/* both maps of a carry from the instances loaded in src and dst.  region_map[c * p_src + q]: the destination's possible-region index of the region
+ * NUMBER that is the source's q-th possible region of car c, or -1 (p_src: the most possible regions a car of the source has); env_map[e], e < the
+ * source's environment pieces: the first piece of the destination whose rounded edge tuples equal those of the source's piece e, or -1.  Returns
+ * p_src.  -1: NULL, src == dst, a handle without an instance.  -2, with the reason in miqp_solver_last_error(dst): the instances differ in cars,
+ * steps, obstacles, max_lines_obstacles or the obstacles' soft flags, or do not carry the same region tables.  -3: cap_r < cars * p_src or cap_e
+ * below the source's pieces.  Needs no device; miqp_solver_last_error(dst) is cleared at the start. */
+int miqp_solver_pool_carry_maps(const miqp_solver_t* src, const miqp_solver_t* dst, int* region_map, int cap_r, int* env_map, int cap_e);
+/* The carry.  The SOURCE entries are the first min(miqp_solver_pool_count(src), 16) entries of src's pool as found (improved and explored entries
+ * included); src is only read.  Each is shifted (above, with the maps of the two instances), the mappable ones are settled on dst's instance in the
+ * rounds of miqp_solver_settle_decisions - together with dst's own kept entries, whose settled signatures the admission needs -, and the feasible ones
+ * are visited in ascending (objective of the first solve, source entry number).  A record is appended behind dst's pool when it is within the cost cap
+ * (else status 5), its signature under dst's filter is not in the pool (3), it has settled labels whose signature is not among the settled signatures
+ * of the pool (4) and a place is free (6), in that order of tests; entries admitted earlier in the call count in both signature tests.  Stored for an
+ * admitted entry: the shifted bytes, objective and iterations of its FIRST solve - the settled explore's convention, so miqp_solver_pool_solve behind
+ * the call merges away nothing it added.  No existing entry is changed or moved; a refined pool dst held is dropped.
+ * Cost cap: max_rel < 0 none, else objective - obj0 <= max_rel * |obj0|, obj0 = dst's entry 0 as found, every operation rounded on its own.
+ * dst may hold an EMPTY pool (capacity and filter set, instance loaded, no solve yet or a solve that found nothing): the first record admitted is
+ * admitted whatever max_rel is, becomes entry 0, and its objective is obj0 from then on; miqp_solver_pool_count(dst) then counts the carried entries
+ * until the next solve or the next parameters.
+ * out[k], k < source entries: one record per SOURCE entry (miqp_pool_carry_c).  Returns the number admitted; 0 without touching a device when src
+ * keeps nothing or dst is full.  -1: NULL, cap < 0, max_rel a NaN, src == dst, a handle without an instance.  -2: shift outside 1 .. steps - 2; dst's
+ * capacity 0; dst's filter outside 1 .. 15 (no jump family is needed here); what miqp_solver_pool_carry_maps refuses with -2; cap below the source
+ * entries.  -3: no device / kernel image / HIP error, or a shape whose fix record does not fit the LDS of the kernels (miqp_solver_last_error(dst)
+ * says which).  All but -3 are decided before a device is touched; on every failure out and both pools are untouched.
+ * miqp_solver_last_error(dst) is cleared at the start.  miqp_solver_last_timing(dst): out[0] the call, out[1] of which on the device, out[2] launch
+ * groups of the settle rounds, out[3] solves (dst's own entries included), out[4] their iterations, out[5] 1 when a carried record still moved after
+ * the last settle pass.  The call is a function of the two pools and the two instances alone: reproducible bit for bit.
+ * Out of scope: many (src, dst) pairs in one call; obstacle re-numbering; replacing a kept entry by a better carried one of its class (the climb's
+ * job); feeding carried records to the SEARCH as MIP starts (that would change solves).  No reference counterpart. */
+int miqp_solver_pool_carry(miqp_solver_t* dst, const miqp_solver_t* src, int shift, double max_rel, miqp_pool_carry_c* out, int cap);
+/* sizeof(miqp_pool_carry_c) of the built library (binding check) */
+int miqp_gpu_pool_carry_size(void);
+/* diagnostic: the seconds the calling thread's last successful miqp_solver_pool_carry spent in pool_shift_kernel and in pool_carry_admit_kernel, from
+ * the call's own device events (either may be NULL) */
+void miqp_gpu_pool_carry_last(double* shift_s, double* admit_s);
+
 /* 1 when instances of this shape (NrCars, N) have the dual active-set launches - one or two cars, a horizon of up to 20 steps - else 0 (their node
  * relaxations are interior point solves).  Pure host code: no device is needed or touched.  A call switches the launches off with MIQP_AS=0 */
 int miqp_gpu_has_active_set(int num_cars, int num_steps);

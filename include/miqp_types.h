@@ -206,6 +206,19 @@ typedef struct miqp_pool_explore_c {
   double objective; /* with the constant cost of step 0; what miqp_solver_pool_found reports for the entry */
 } miqp_pool_explore_c;
 
+/* What miqp_solver_pool_carry answers for one entry of the SOURCE pool: what became of its shifted record on the destination's instance. */
+typedef struct miqp_pool_carry_c {
+  int status;       /* 0 admitted; 1 its first solve on the destination's instance was not feasible; 2 unmappable (a region it uses is not possible on
+                       the destination); 3 its signature under the destination's filter is in the pool; 4 no settled labels, or the signature of its
+                       settled labels is in the pool; 5 beyond the cost cap; 6 new in every respect, but no place is free */
+  int place;        /* the entry of the destination's pool it became; -1 unless status 0 */
+  int solves;       /* the solves its settling took (0 for status 2) */
+  int iterations;   /* interior point iterations of its first solve (0 for status 2) */
+  int reserved;     /* 0 */
+  int reserved1;    /* 0 */
+  double objective; /* of its first solve, with the constant cost of step 0: what miqp_solver_pool_found reports for an admitted entry; NaN for status 2 */
+} miqp_pool_carry_c;
+
 #ifdef __cplusplus
 }
 #endif

@@ -138,9 +138,10 @@ struct miqp_solver {
   // their objectives as found and the record length; of the last miqp_solver_pool_solve: per entry whether it came out feasible, the fix record it was
   // refined with and its trajectory.  Dropped by the next solve and whenever the instance changes
   int pool_cap = 0, pool_n = 0, pool_fixlen = 0; std::vector<signed char> pool_fix; std::vector<double> pool_obj;
+  bool pool_carried = false;   // the pool holds carried entries and no solve stands behind it (miqp_solver_pool_carry into an empty pool): miqp_solver_pool_count counts them
   int pool_fam = 0;   // miqp_solver_set_pool_filter: the families whose signature says which leaves are one entry, 0 = off (a setting like pool_cap: it stays)
   int pr_n = 0; std::vector<char> pr_ok; std::vector<signed char> pr_fix; std::vector<double> pr_Z;
-  void drop_pool() { pool_n = 0; pr_n = 0; std::vector<signed char>().swap(pool_fix); std::vector<double>().swap(pool_obj); std::vector<char>().swap(pr_ok); std::vector<signed char>().swap(pr_fix); std::vector<double>().swap(pr_Z); }
+  void drop_pool() { pool_n = 0; pr_n = 0; pool_carried = false; std::vector<signed char>().swap(pool_fix); std::vector<double>().swap(pool_obj); std::vector<char>().swap(pr_ok); std::vector<signed char>().swap(pr_fix); std::vector<double>().swap(pr_Z); }
   std::string err;
 };
 
@@ -1164,7 +1165,7 @@ void prepare_instances(miqp_solver_t* const* S, const Layout& Y, const CallShape
   std::vector<std::vector<int>> inst_root_depth(n);
   std::vector<char> h_feas0(n, 0);
   auto prepare_one = [&](int k) {
-    miqp_solver* s = S[k]; s->lay = Y; s->has_sol = false; s->rescache.reset();
+    miqp_solver* s = S[k]; s->lay = Y; s->has_sol = false; s->pool_carried = false; s->rescache.reset();
     compile_instance(s->inst, Y, &hD[(size_t)k * Y.dstride], &hT[(size_t)k * Y.istride]);
     HostGeo G{s->inst, Y, &hD[(size_t)k * Y.dstride], &hT[(size_t)k * Y.istride]};
     double cobj = 0; bool feas0 = step0_check(G, cobj);
@@ -1726,9 +1727,10 @@ bool solve_batch_impl(miqp_solver_t* const* S, int n, int* statuses, const Split
 #include "pool_label.hip"
 #include "pool_settle.hip"
 #include "pool_explore.hip"
+#include "pool_carry.hip"
 
 // the caches of the calls above, by device ordinal; used under the device lock (DevCtx::mu of lane 0)
-std::map<int, std::tuple<CertDev, FixedDev, PoolImproveDev, PoolEntryDev, PoolLabelDev, PoolSettleDev, PoolExploreDev>> g_call_devs;
+std::map<int, std::tuple<CertDev, FixedDev, PoolImproveDev, PoolEntryDev, PoolLabelDev, PoolSettleDev, PoolExploreDev, PoolCarryDev>> g_call_devs;
 template <class D> D& call_dev(int device) { return std::get<D>(g_call_devs[device]); }
 
 // ================================================================================================

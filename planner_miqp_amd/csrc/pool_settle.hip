@@ -119,10 +119,11 @@ bool pool_settle_compact(DevCtx& X, const PoolSettleArgs& S, int& live, PoolSett
 }
 
 // Rounds `first` .. POOL_PASSES over the `live` records of the list in S.live, whose instances are among the call's.  Bp: fixed_chain_settings; Z: the
-// rows of one chunk.  false: HIP error
-bool pool_settle_rounds(const FixedCall& call, const DevBuf& Bp, PoolSettleArgs S, double* Z, int first, int live, PoolSettleTally& T) {
+// rows of one chunk.  A caller that wants the words of a round before the next one writes over them (the carry: the answers of round 1) stops behind
+// round `last` and goes on from there with the live count it received.  false: HIP error
+bool pool_settle_rounds(const FixedCall& call, const DevBuf& Bp, PoolSettleArgs S, double* Z, int first, int& live, PoolSettleTally& T, int last = POOL_PASSES) {
   DevCtx& X = *call.X; const Layout& Y = call.Y; hipStream_t st = X.stream;
-  for (int p = first; p <= POOL_PASSES && live > 0; ++p) {
+  for (int p = first; p <= last && live > 0; ++p) {
     S.round = p;
     for (int c0 = 0; c0 < live; c0 += FB_CHUNK) {
       const int bc = std::min(FB_CHUNK, live - c0);
@@ -152,7 +153,8 @@ bool pool_settle_records(const FixedCall& call, const DevBuf& Bp, const PoolSett
   HIP_OK(hipMemsetAsync(S.round_it, 0, (size_t)S.n * sizeof(int), st)); HIP_OK(hipMemsetAsync(S.moved, 0, (size_t)S.n * sizeof(int), st));
   HIP_OK(hipMemsetAsync(S.solves, 0, (size_t)S.n * sizeof(int), st)); HIP_OK(hipMemsetAsync(S.acc_it, 0, (size_t)S.n * sizeof(int), st));
   HIP_OK(hipStreamSynchronize(st));   // (ident is a local)
-  return pool_settle_rounds(call, Bp, S, Z, 1, S.n, T);
+  int live = S.n;
+  return pool_settle_rounds(call, Bp, S, Z, 1, live, T);
 }
 
 }  // namespace

@@ -481,7 +481,7 @@ int miqp_solver_pool_found_decisions(const miqp_solver_t* s, int k, signed char*
   return D;
 }
 
-int miqp_solver_pool_count(const miqp_solver_t* s) { return (s && s->has_inst && s->has_sol && s->pool_cap > 0) ? s->pool_n : 0; }
+int miqp_solver_pool_count(const miqp_solver_t* s) { return (s && s->has_inst && (s->has_sol || s->pool_carried) && s->pool_cap > 0) ? s->pool_n : 0; }
 
 int miqp_solver_pool_found(const miqp_solver_t* s, double* obj, int cap) {
   if (!s || !obj || cap < 0) return -1;

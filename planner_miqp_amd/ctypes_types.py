@@ -116,6 +116,12 @@ class PoolExploreC(C.Structure):
                 ("iterations", C.c_int), ("reserved", C.c_int), ("objective", C.c_double)]
 
 
+class PoolCarryC(C.Structure):
+    """miqp_pool_carry_c (include/miqp_types.h): what CplexWrapper.carrySolutionPool answers for one entry of the source pool"""
+    _fields_ = [("status", C.c_int), ("place", C.c_int), ("solves", C.c_int), ("iterations", C.c_int), ("reserved", C.c_int), ("reserved1", C.c_int),
+                ("objective", C.c_double)]
+
+
 class SolverOptsC(C.Structure):
     _fields_ = [("precision", C.c_int), ("device", C.c_int), ("nodes_per_round", C.c_int),
                 ("max_open_nodes", C.c_int), ("gap_override", C.c_double), ("verbose", C.c_int)]

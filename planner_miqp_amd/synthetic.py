@@ -124,3 +124,31 @@ def generate(config="cfg3", seed=0, gap=0.01, max_time=10.0):
     p.ObstacleConvexPolygon = obs
     p.obstacle_is_soft = [0] * O
     return p
+
+
+def advance(params, record, steps=1, extra_possible=()):
+    """the next cycle's ModelParameters of a synthetic instance in a receding horizon, ``steps`` steps after ``params`` was solved to ``record``
+    (a RawResults): the initial state of every car is the record's state at step ``steps`` and initial_region its active region there; the
+    references are moved on by steps * ts * (vx_ref, vy_ref); every obstacle polygon is moved ``steps`` steps along its constant velocity (the
+    displacement between its first two steps).  Everything else is unchanged.  ``extra_possible``: (car, region index from 0) pairs that become
+    possible regions of the new instance as well, so that its possible-region indices are not those of ``params``.  ``params`` is left as it is."""
+    q = params.copy()
+    Cn, N = int(q.NumCars), int(q.NumSteps)
+    s = int(steps)
+    if not 1 <= s <= N - 1:
+        raise ValueError("steps outside 1 .. NumSteps - 1")
+    x0 = np.array(q.IntitialState, float).reshape(Cn, 6)
+    init = np.array(q.initial_region, int).reshape(Cn)
+    for c in range(Cn):
+        x0[c] = [record.pos_x[c, s], record.vel_x[c, s], record.acc_x[c, s], record.pos_y[c, s], record.vel_y[c, s], record.acc_y[c, s]]
+        init[c] = int(np.argmax(record.active_region[c, s])) + 1
+    q.IntitialState, q.initial_region = x0, init
+    vx, vy = np.array(q.vx_ref, float).reshape(Cn, N), np.array(q.vy_ref, float).reshape(Cn, N)
+    q.x_ref = np.array(q.x_ref, float).reshape(Cn, N) + s * q.ts * vx
+    q.y_ref = np.array(q.y_ref, float).reshape(Cn, N) + s * q.ts * vy
+    q.ObstacleConvexPolygon = [[np.asarray(o[i], float) + s * (np.asarray(o[1], float) - np.asarray(o[0], float)) for i in range(N)] for o in q.ObstacleConvexPolygon]
+    poss = np.array(q.possible_region, int).reshape(Cn, -1)
+    for c, j in extra_possible:
+        poss[int(c), int(j)] = 1
+    q.possible_region = poss
+    return q

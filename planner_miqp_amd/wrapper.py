@@ -12,7 +12,7 @@ import numpy as np
 # (four concurrent launches per round + the null stream: see miqp_gpu.hip - effective when set before the process's first HIP call)
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
-from .ctypes_types import (AsNodeC, Certificate, CertificateC, FixedResultC, ModelParameters, ModelParamsC, PoolExploreC, PoolImproveC, RawResults, RawResultsC, SolutionPropertiesC, SolverOptsC,
+from .ctypes_types import (AsNodeC, Certificate, CertificateC, FixedResultC, ModelParameters, ModelParamsC, PoolCarryC, PoolExploreC, PoolImproveC, RawResults, RawResultsC, SolutionPropertiesC, SolverOptsC,
                            c_double_p)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -147,6 +147,15 @@ def load_library():
     L.miqp_solver_solve_fixed_multi.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(C.POINTER(RawResultsC)), C.POINTER(C.c_int), C.POINTER(FixedResultC), C.POINTER(C.c_int)]
     L.miqp_solver_pool_solve_multi.restype = C.c_int
     L.miqp_solver_pool_solve_multi.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(FixedResultC), C.c_int, C.POINTER(C.c_int)]
+    L.miqp_gpu_pool_shift.restype = C.c_int
+    L.miqp_gpu_pool_shift.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_byte), C.POINTER(C.c_byte), C.c_int]
+    L.miqp_solver_pool_carry_maps.restype = C.c_int; L.miqp_solver_pool_carry_maps.argtypes = [vp, vp, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_int]
+    L.miqp_solver_pool_carry.restype = C.c_int; L.miqp_solver_pool_carry.argtypes = [vp, vp, C.c_int, C.c_double, C.POINTER(PoolCarryC), C.c_int]
+    L.miqp_gpu_pool_carry_size.restype = C.c_int; L.miqp_gpu_pool_carry_size.argtypes = []
+    L.miqp_gpu_pool_carry_last.restype = None; L.miqp_gpu_pool_carry_last.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    if L.miqp_gpu_pool_carry_size() != C.sizeof(PoolCarryC):
+        raise RuntimeError("libmiqp_gpu.so and ctypes_types.PoolCarryC disagree on miqp_pool_carry_c (%d / %d bytes): rebuild the library"
+                           % (L.miqp_gpu_pool_carry_size(), C.sizeof(PoolCarryC)))
     if L.miqp_gpu_as_node_size() != C.sizeof(AsNodeC):
         raise RuntimeError("libmiqp_gpu.so and ctypes_types.AsNodeC disagree on miqp_as_node_c (%d / %d bytes): rebuild the library"
                            % (L.miqp_gpu_as_node_size(), C.sizeof(AsNodeC)))
@@ -188,7 +197,8 @@ EXPORTED_SYMBOLS = ["miqp_solver_create", "miqp_solver_destroy", "miqp_solver_se
                     "miqp_gpu_pool_jumps", "miqp_gpu_pool_explore_size", "miqp_solver_pool_explore",
                     "miqp_solver_canonical_decisions", "miqp_solver_canonical_labels", "miqp_solver_pool_explore_distinct",
                     "miqp_solver_settle_decisions", "miqp_solver_pool_explore_settled", "miqp_gpu_pool_settle_passes",
-                    "miqp_solver_pool_explore_multi", "miqp_gpu_pool_explore_plan", "miqp_gpu_pool_explore_multi_last"]
+                    "miqp_solver_pool_explore_multi", "miqp_gpu_pool_explore_plan", "miqp_gpu_pool_explore_multi_last",
+                    "miqp_gpu_pool_shift", "miqp_solver_pool_carry_maps", "miqp_solver_pool_carry", "miqp_gpu_pool_carry_size", "miqp_gpu_pool_carry_last"]
 
 
 # a row of CplexWrapper.launchPlan (NodeLaunch in csrc/miqp_gpu.hip)
@@ -265,6 +275,45 @@ def pool_jumps(cars, steps, obstacles, max_lines, families, decisions):
     if n < 0:
         raise ValueError("miqp_gpu_pool_jumps refused the arguments (%d)" % n)
     return out[:n].copy()
+
+
+def pool_shift(cars, steps, obstacles, shift, decisions, region_map=None, env_map=None):
+    """a record's D decision bytes shifted by ``shift`` steps and re-expressed for the next cycle's instance (miqp_gpu_pool_shift): byte i of every
+    site is the source byte of step min(i + shift, steps - 1); a region byte q * 4 + h becomes region_map[c, q] * 4 + h, an environment byte e
+    becomes env_map[e]; obstacle and car/car bytes stay; negative bytes and step 0 are -1.  ``region_map`` is an int array [cars, p_src] (None: the
+    identity), ``env_map`` an int vector (None: the identity), as CplexWrapper.poolCarryMaps returns them.  Returns (mappable, int8 array of D bytes):
+    mappable is False when a region byte has no target - those bytes are -1.  A pure function on bytes: needs no wrapper and no device.  Raises
+    ValueError where the library refuses the arguments (shift outside 1 .. steps - 2)."""
+    d = np.ascontiguousarray(decisions, dtype=np.int8)
+    D = _decision_len(int(cars), int(steps), int(obstacles))
+    if d.ndim != 1 or d.size < D or D <= 0:
+        raise ValueError("%d decision bytes given, the shape has %d" % (d.size, D))
+    ip = C.POINTER(C.c_int)
+    rm = em = None
+    if region_map is not None:
+        rm = np.ascontiguousarray(region_map, dtype=np.int32)
+        if rm.ndim != 2 or rm.shape[0] != int(cars) or rm.shape[1] < 1:
+            raise ValueError("a region map of shape [cars, p_src] expected, got %s" % (rm.shape,))
+    if env_map is not None:
+        em = np.ascontiguousarray(env_map, dtype=np.int32)
+        if em.ndim != 1:
+            raise ValueError("an environment map is a vector")
+    out = np.empty(D, dtype=np.int8)
+    bp = C.POINTER(C.c_byte)
+    rc = load_library().miqp_gpu_pool_shift(int(cars), int(steps), int(obstacles), int(shift), rm.ctypes.data_as(ip) if rm is not None else None,
+                                            rm.shape[1] if rm is not None else 0, em.ctypes.data_as(ip) if em is not None and em.size else None,
+                                            em.size if em is not None else 0, d.ctypes.data_as(bp), out.ctypes.data_as(bp), D)
+    if rc != D and rc != -4:
+        raise ValueError("miqp_gpu_pool_shift refused the arguments (%d)" % rc)
+    return rc == D, out
+
+
+def pool_carry_last():
+    """(seconds in pool_shift_kernel, seconds in pool_carry_admit_kernel) of the calling thread's last carrySolutionPool, from the call's own device
+    events (miqp_gpu_pool_carry_last)"""
+    a, b = C.c_double(0.0), C.c_double(0.0)
+    load_library().miqp_gpu_pool_carry_last(C.byref(a), C.byref(b))
+    return a.value, b.value
 
 
 def pool_max():
@@ -721,6 +770,48 @@ class CplexWrapper:
         call = self._L.miqp_solver_pool_explore_settled if settled else self._L.miqp_solver_pool_explore_distinct if distinct else self._L.miqp_solver_pool_explore
         rc = int(call(self._h, int(max_passes), float(max_rel), out, n))
         return rc, _explore_dicts(out[:max(rc, 0)], settled)
+
+    def _loaded(self):
+        """the instance is in the library (a loaded instance is kept: loading drops its pool); False: invalid parameters"""
+        d = (C.c_int * 6)()
+        return self._L.miqp_solver_get_dims(self._h, d) == 0 or (self._push_inputs() == 0 and self._L.miqp_solver_get_dims(self._h, d) == 0)
+
+    def poolCarryMaps(self, src):
+        """the two maps of a carry from ``src`` (last cycle's wrapper) into this wrapper's instance (miqp_solver_pool_carry_maps): (region_map,
+        env_map) - region_map[c, q] this instance's possible-region index of the region number that is src's q-th possible region of car c, or
+        -1; env_map[e] this instance's environment piece of the same edges as src's piece e, or -1.  Needs no device.  Raises ValueError, with
+        lastError(), where the library refuses the pair (instances of different shape, obstacle soft flags or region tables)."""
+        if not self._loaded() or not src._loaded():
+            raise ValueError("invalid parameters")
+        d = (C.c_int * 6)()
+        self._L.miqp_solver_get_dims(src._h, d)
+        rm = np.full(d[0] * d[2], -1, dtype=np.int32); em = np.full(max(d[3], 1), -1, dtype=np.int32)
+        ip = C.POINTER(C.c_int)
+        p = int(self._L.miqp_solver_pool_carry_maps(src._h, self._h, rm.ctypes.data_as(ip), rm.size, em.ctypes.data_as(ip), d[3]))
+        if p < 1:
+            raise ValueError("miqp_solver_pool_carry_maps refused the pair (%d)%s" % (p, ": " + self.lastError() if self.lastError() else ""))
+        return rm[:d[0] * p].reshape(d[0], p).copy(), em[:d[3]].copy()
+
+    def carrySolutionPool(self, src, shift=1, max_rel=-1.0):
+        """the kept entries of ``src`` - the wrapper of the cycle ``shift`` steps ago, its pool as it stands (explored entries included) - carried
+        into the free places of this wrapper's pool in one device-resident call (miqp_solver_pool_carry): every record shifted by ``shift`` steps
+        and re-expressed in this instance's alternatives (pool_shift with poolCarryMaps), settled on this instance, and admitted under this
+        wrapper's filter when its class is new - by its own signature and by that of its settled labels, so solveSolutionPool behind the call
+        merges away nothing it added - within ``max_rel`` (as exploreSolutionPool; an empty pool admits its first record whatever the cap).
+        Returns (added, records): added the number of entries appended - or the library's code < 0: -2 the shift is outside 1 .. NumSteps - 2, no
+        capacity, a filter outside 1 .. 15, instances the maps refuse; -3 no device; both pools are untouched then - and one dict per SOURCE
+        entry (status, place, solves, iterations, objective; empty for a code < 0): status 0 admitted, 1 not feasible here, 2 unmappable, 3
+        signature in the pool, 4 no settled labels or settled signature in the pool, 5 beyond the cost cap, 6 no place free.  ``src`` is only
+        read; old entries keep bytes and places; a refined pool is dropped: call solveSolutionPool afterwards."""
+        if not self._loaded() or not src._loaded():
+            return -1, []
+        n = pool_max()
+        out = (PoolCarryC * n)(*[PoolCarryC(-1, -1, 0, 0, 0, 0, float("nan")) for _ in range(n)])   # (a call that touches no device writes nothing)
+        ns = min(src.solutionPoolCount(), n)
+        rc = int(self._L.miqp_solver_pool_carry(self._h, src._h, int(shift), float(max_rel), out, n))
+        if rc < 0:
+            return rc, []
+        return rc, [dict(status=o.status, place=o.place, solves=o.solves, iterations=o.iterations, objective=float(o.objective)) for o in out[:ns] if o.status >= 0]
 
     def solveDecisions(self, decisions):
         """the continuous QPs of many DECISION records of this wrapper's instance in one device call (miqp_solver_solve_decisions): ``decisions`` is
