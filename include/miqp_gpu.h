@@ -597,9 +597,36 @@ int miqp_solver_pool_carry_maps(const miqp_solver_t* src, const miqp_solver_t* d
  * miqp_solver_last_error(dst) is cleared at the start.  miqp_solver_last_timing(dst): out[0] the call, out[1] of which on the device, out[2] launch
  * groups of the settle rounds, out[3] solves (dst's own entries included), out[4] their iterations, out[5] 1 when a carried record still moved after
  * the last settle pass.  The call is a function of the two pools and the two instances alone: reproducible bit for bit.
- * Out of scope: many (src, dst) pairs in one call; obstacle re-numbering; replacing a kept entry by a better carried one of its class (the climb's
- * job); feeding carried records to the SEARCH as MIP starts (that would change solves).  No reference counterpart. */
+ * Out of scope: obstacle re-numbering; replacing a kept entry by a better carried one of its class (the climb's job); feeding carried records to the
+ * SEARCH as MIP starts (that would change solves).  Many (src, dst) pairs in one call: miqp_solver_pool_carry_multi below.  No reference counterpart. */
 int miqp_solver_pool_carry(miqp_solver_t* dst, const miqp_solver_t* src, int shift, double max_rel, miqp_pool_carry_c* out, int cap);
+/* ---- the carry of many (src, dst) pairs in ONE device call: a scenario-parallel caller drains a queue of handles every
+ * cycle.  The carry is almost only settle rounds, and a round costs the same for 30 records as for a thousand: the records of all pairs fill
+ * common launch groups, behind one lock, one context and one upload. ----
+ * Pair p carries the kept entries of srcs[p] into the free places of dsts[p].  shift and max_rel are common; both maps, the capacity, the filter,
+ * obj0 and the entry counts are each pair's own.  out[p * cap + k] is the record of source entry k of pair p, counts[p] the number admitted to
+ * dsts[p]; the return value is their sum.  PER PAIR the call answers bit for bit what miqp_solver_pool_carry(dsts[p], srcs[p], shift, max_rel, ..)
+ * answers for the pair alone: the count, every out record, the destination's pool afterwards (old entries untouched and in place), the dropped
+ * refined pool, miqp_solver_last_timing(dst) out[2 .. 5] (out[2]: the rounds in which the pair had a live record - its launch groups, a pair having
+ * at most 32 records) and miqp_solver_last_error(dst), the "still moved" text included.  out[0] and out[1] of the last timing are the CALL's.
+ * Sources are only read; one source may feed several destinations (one pool of last cycle branching into several scenarios of the next).
+ * A pair with nothing to carry or a full destination takes no part: counts[p] = 0, its rows of out are not written, its pool and last timing
+ * stay, its last error is cleared - as the single call leaves it.  A call in which no pair takes part returns 0 without touching a device.
+ * -1: NULL arrays, n <= 0, cap < 0, max_rel a NaN; a NULL handle or one without an instance; srcs[p] == dsts[p]; a destination named twice; a handle
+ * that is the destination of one pair and the source of another (the answer would depend on the order); a kept pool whose record length is not the
+ * common Layout's.  -5: more than 2048 pairs (65536 / 32 records: a pair has at most 16 own and 16 carried ones) - decided on n alone, before
+ * a handle is read.  -2: shift outside 1 .. steps - 2; what the single call refuses of a pair with -2 - capacity 0, a filter outside 1 .. 15, what
+ * miqp_solver_pool_carry_maps refuses -: the pairs are checked in order, the first refusal decides and its reason is THAT destination's last error
+ * (the last errors of the other destinations stay what they were); destinations that do not share a shape or a device (as
+ * miqp_solver_solve_fixed_multi refuses them, with its text as every destination's last error); cap below the largest number of source entries
+ * among the pairs.  -3: no device / kernel image / HIP error, or the LDS refusals of the single call (the destinations that take part then carry
+ * its text).  All but -3 are decided before a device is touched; on EVERY failure out, counts and every pool are untouched.
+ * miqp_solver_last_error of every destination is cleared once nothing of the above but -3 refuses the call.
+ * Device memory: 16 places per pair x (5 records + a few words) and 32 records per pair of the settle rounds.  No reference counterpart. */
+int miqp_solver_pool_carry_multi(miqp_solver_t* const* dsts, const miqp_solver_t* const* srcs, int n, int shift, double max_rel, miqp_pool_carry_c* out, int cap, int* counts);
+/* diagnostic: the settle rounds and the launch groups the calling thread's last successful miqp_solver_pool_carry_multi ran on the device (either may
+ * be NULL) */
+void miqp_gpu_pool_carry_multi_last(int* rounds, int* groups);
 /* sizeof(miqp_pool_carry_c) of the built library (binding check) */
 int miqp_gpu_pool_carry_size(void);
 /* diagnostic: the seconds the calling thread's last successful miqp_solver_pool_carry spent in pool_shift_kernel and in pool_carry_admit_kernel, from

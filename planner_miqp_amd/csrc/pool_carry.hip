@@ -1,4 +1,5 @@
-// pool_carry.hip - the kept manoeuvres of one planning cycle carried into the pool of the next (miqp_solver_pool_carry).  DESIGN.md 6l.
+// pool_carry.hip - the kept manoeuvres of one planning cycle carried into the pool of the next (miqp_solver_pool_carry, for many pairs of
+// handles in one call miqp_solver_pool_carry_multi).  DESIGN.md 6l, 6m.
 //
 // Counterpart of re-adding the members of a CPLEX solution pool as MIP starts of the next model.  A receding-horizon caller solves a new instance every
 // cycle, and miqp_solver_set_params empties the pool: the fallback the explore paid for in cycle t is gone in cycle t + 1.  The CARRY takes the kept
@@ -15,7 +16,7 @@
 // without a target makes the whole record UNMAPPABLE: a record with an undecided region byte has no labels, so it cannot be settled.
 //
 // The call:
-//   pool_shift_kernel        one wavefront per source entry: the record staged in LDS (16-byte loads), one lane per site - in a loop when there are
+//   pool_shift_kernel        one wavefront per (pair, source entry): the record staged in LDS (16-byte loads), one lane per site - in a loop when there are
 //                            more sites than lanes - through pool_shift_site, the maps read from device memory; the shifted record leaves in 16-byte
 //                            stores, to its carry place (what an admitted entry stores) and to its record of the settle rounds; one word per record
 //                            says "unmappable", one whether it is live in round 1
@@ -23,15 +24,26 @@
 //                            exist - pass 0 of the settled explore) and the mappable carried records (n0 + k) in the same rounds; the compaction
 //                            forms the live list of round 1 from the words of the shift kernel.  The answers of round 1 are kept: objective and
 //                            iterations of an admitted entry are its FIRST solve's, the settled explore's convention
-//   pool_carry_admit_kernel  ONE wavefront, a sibling of the explore's admission built from the same steps of pool_blocks.hip: the signatures of the
+//   pool_carry_admit_kernel  ONE wavefront per pair, a sibling of the explore's admission built from the same steps of pool_blocks.hip: the signatures of the
 //                            destination's entries, then the feasible carried records in ascending (objective of the first solve, source number):
 //                            beyond the cost cap (5), plain signature in the pool (3), no settled labels or settled signature in the pool (4), no
 //                            place free (6), else appended behind the pool (0) - the entries admitted earlier count in both signature tests.  An
 //                            EMPTY destination pool admits its first record whatever the cap; that record's objective is obj0 from then on
-// Owner computes: no atomics, no scratch, no wavefront waits on another.  The shift kernel is latency-bound (at most 16 wavefronts); it exists so that
-// shift, settle and admission stay one device-resident sequence, not for throughput.
-// Out of scope: many (source, destination) pairs in one call; obstacle re-numbering; replacing a kept entry by a better carried one of its class
-// (the climb's job); feeding carried records to the SEARCH as MIP starts (that would change solves).
+// Owner computes: no atomics, no scratch, no wavefront waits on another.  The shift kernel is latency-bound (at most 16 wavefronts a pair); it exists
+// so that shift, settle and admission stay one device-resident sequence, not for throughput.
+//
+// MANY PAIRS (miqp_solver_pool_carry_multi).  pool_carry_run carries the pools of np (source, destination) pairs whose destinations
+// share a shape; miqp_solver_pool_carry is that run with one pair, on the same kernels.  The carry is almost only settle rounds, and a round costs
+// the same for 30 records as for a thousand: the records of all pairs are numbered densely and pair-major - a pair's own kept entries, then its
+// carried records - so that the rounds of all pairs fill common launch groups.  inst[k] of a record is its destination's index in the call.
+// Everything per PLACE (the source records, the carry places, the destination's pool, both signatures, has_sig, `out`) is strided by MIQP_POOL_MAX
+// per pair; per pair one row of words (PoolCarryPair: its first record, n0, ns, K, filter, p_src, e_src and where its two maps begin in the call's
+// two map arrays) and six state words.  pool_shift_kernel runs one wavefront per (pair, source entry), pool_carry_admit_kernel one workgroup of one
+// wavefront per pair: it sees its own records only, in the single call's order, so a pair's answer is the single call's, bit for bit.  What the
+// single call's host summed over its rounds - launch groups, solves, iterations - the admission sums per pair from the per-record words `solves`
+// and `acc_it`: a pair has at most 32 records, so its launch groups are the rounds in which it had a live record, the largest |solves| among them.
+// Out of scope: obstacle re-numbering; replacing a kept entry by a better carried one of its class (the climb's job); feeding carried records to
+// the SEARCH as MIP starts (that would change solves).
 #pragma once
 
 namespace {
@@ -61,72 +73,102 @@ __host__ __device__ inline bool pool_shift_site(const PoolDims& d, int s, int sh
   return ok;
 }
 
+// the words of one pair of a call (device memory, one row per pair).  first: the call's number of the pair's first record - records first .. first +
+// n0 - 1 are the destination's own kept entries, first + n0 + k is the carried record k; ns source entries, n0 kept entries of the destination, K its
+// capacity, fam its filter; rmap, emap: where the pair's maps begin in the call's two map arrays
+struct PoolCarryPair { int first, n0, ns, K, fam, p_src, e_src, rmap, emap; };
+constexpr int POOL_CARRY_STATE = 6;   // state words of a pair: entries in the pool, admitted, rounds with a live record, solves, their iterations, carried records still moving
+
+// Places - the source's records, the carry places, the destination's pool and what goes with it - are strided by MIQP_POOL_MAX per pair: place
+// p * MIQP_POOL_MAX + k is place k of pair p.  With one pair every numbering is the single call's
 struct PoolCarryArgs {
-  PoolDims dims; int fixlen, fam, ns, n0, K, shift;   // ns source entries, n0 kept entries of the destination, K its capacity
-  PoolCarryMaps maps;                 // (device memory)
-  const signed char* src;             // [ns] the source's records
-  signed char* shifted;               // [ns] the carry places: the shifted records
-  int* unmappable;                    // [ns]
-  // the settle rounds' words (PoolSettleArgs): record j < n0 is the destination's entry j, record n0 + k the carried record k
-  signed char* lab; int* moved; const int* solves; const miqp_fixed_result_c* last;
-  const miqp_fixed_result_c* first;   // [n0 + ns] the answers of round 1
-  // the destination's places
-  signed char* pool; double* pool_obj; signed char* sig; signed char* csig; int* has_sig;   // [MIQP_POOL_MAX]
+  PoolDims dims; int fixlen, np, shift;   // np pairs
+  const PoolCarryPair* pair;          // [np]
+  const int* rmap; const int* emap;   // the region maps of all pairs, their environment maps (device memory)
+  const signed char* src;             // [places] the sources' records
+  signed char* shifted;               // [places] the carry places: the shifted records
+  int* unmappable;                    // [places]
+  // the settle rounds' words (PoolSettleArgs), by the call's record number
+  signed char* lab; int* moved; const int* solves; const int* acc_it; const miqp_fixed_result_c* last;
+  const miqp_fixed_result_c* first;   // [records] the answers of round 1
+  // the destinations' places
+  signed char* pool; double* pool_obj; signed char* sig; signed char* csig; int* has_sig;   // [places]
   double max_rel;
-  miqp_pool_carry_c* out;             // [ns]
-  int* state;                         // [0] entries in the pool, [1] admitted
+  miqp_pool_carry_c* out;             // [places]
+  int* state;                         // [np][POOL_CARRY_STATE]
 };
 
+// One wavefront per (pair, source entry): blockIdx.x is the place
 __global__ __launch_bounds__(64) void pool_shift_kernel(const PoolCarryArgs A) {
   extern __shared__ uint4 ps_lds[];   // the source record, the shifted record
-  const int k = blockIdx.x, lane = threadIdx.x, chunks = A.fixlen >> 4;
-  if (k >= A.ns) return;
+  const int p = blockIdx.x / MIQP_POOL_MAX, k = blockIdx.x % MIQP_POOL_MAX, lane = threadIdx.x, chunks = A.fixlen >> 4;
+  if (p >= A.np) return;
+  const PoolCarryPair W = A.pair[p];
+  if (k >= W.ns || W.n0 < 0) return;   // (uniform)
+  const PoolCarryMaps maps{A.rmap + W.rmap, W.p_src, A.emap + W.emap, W.e_src};
+  const size_t place = blockIdx.x, r = (size_t)W.first + W.n0 + k;
   uint4* const rec = ps_lds; uint4* const out = rec + chunks;
-  pool_stage(rec, (const uint4*)A.src + (size_t)k * chunks, chunks, lane, out);   // (out: all -1)
+  pool_stage(rec, (const uint4*)A.src + place * chunks, chunks, lane, out);   // (out: all -1)
   __syncthreads();
   bool ok = true;
-  for (int s = lane, n = pool_sites(A.dims); s < n; s += 64) ok = pool_shift_site(A.dims, s, A.shift, A.maps, (const signed char*)rec, (signed char*)out) && ok;
+  for (int s = lane, n = pool_sites(A.dims); s < n; s += 64) ok = pool_shift_site(A.dims, s, A.shift, maps, (const signed char*)rec, (signed char*)out) && ok;
   const bool bad = __ballot(!ok) != 0ull;
   __syncthreads();
-  pool_stage((uint4*)A.shifted + (size_t)k * chunks, out, chunks, lane);
-  pool_stage((uint4*)A.lab + (size_t)(A.n0 + k) * chunks, out, chunks, lane);
-  if (lane == 0) { A.unmappable[k] = bad ? 1 : 0; A.moved[A.n0 + k] = bad ? 0 : 1; }
+  pool_stage((uint4*)A.shifted + place * chunks, out, chunks, lane);
+  pool_stage((uint4*)A.lab + r * chunks, out, chunks, lane);
+  if (lane == 0) { A.unmappable[place] = bad ? 1 : 0; A.moved[r] = bad ? 0 : 1; }
 }
 
 constexpr int POOL_CARRY_ADMITTED = 0, POOL_CARRY_INFEASIBLE = 1, POOL_CARRY_UNMAPPABLE = 2, POOL_CARRY_KNOWN = 3, POOL_CARRY_SETTLED_KNOWN = 4, POOL_CARRY_BEYOND_CAP = 5,
               POOL_CARRY_NO_PLACE = 6;
 
+// One workgroup of one wavefront per pair: blockIdx.x is the pair.  Everything below is the pair's own: its places, its records from its first on
 __global__ __launch_bounds__(64) void pool_carry_admit_kernel(const PoolCarryArgs A) {
   extern __shared__ uint4 ca_lds[];   // the candidate's record, its signature, its settled labels, their signature
-  const int lane = threadIdx.x, chunks = A.fixlen >> 4;
-  const int ns = min(max(A.ns, 0), MIQP_POOL_MAX), K = min(max(A.K, 0), MIQP_POOL_MAX), n0 = min(max(A.n0, 0), K);
+  const int lane = threadIdx.x, chunks = A.fixlen >> 4, p = blockIdx.x;
+  if (p >= A.np) return;   // (uniform)
+  const PoolCarryPair W = A.pair[p];
+  const int ns = min(max(W.ns, 0), MIQP_POOL_MAX), K = min(max(W.K, 0), MIQP_POOL_MAX), n0 = min(max(W.n0, 0), K), fam = W.fam;
+  const size_t pb = (size_t)p * MIQP_POOL_MAX;   // the pair's first place
   uint4* const cand = ca_lds; uint4* const csg = cand + chunks; uint4* const clab = csg + chunks; uint4* const clsg = clab + chunks;
-  uint4* const pool = (uint4*)A.pool; uint4* const sig = (uint4*)A.sig; uint4* const ssig = (uint4*)A.csig;
+  uint4* const pool = (uint4*)A.pool + pb * chunks; uint4* const sig = (uint4*)A.sig + pb * chunks; uint4* const ssig = (uint4*)A.csig + pb * chunks;
+  const uint4* const shifted = (const uint4*)A.shifted + pb * chunks; const uint4* const lab = (const uint4*)A.lab + (size_t)W.first * chunks;
+  const int* const solves = A.solves + W.first; const miqp_fixed_result_c* const last = A.last + W.first;
+  int* const has_sig = A.has_sig + pb; double* const pool_obj = A.pool_obj + pb; miqp_pool_carry_c* const out = A.out + pb;
   // both signatures of the destination's own entries (a kept entry without settled labels has no settled signature: it matches nothing)
   for (int j = 0; j < n0; ++j) {
     pool_stage(cand, pool + (size_t)j * chunks, chunks, lane, csg);
-    pool_sign(A.dims, A.fam, cand, csg, lane);
+    pool_sign(A.dims, fam, cand, csg, lane);
     pool_stage(sig + (size_t)j * chunks, csg, chunks, lane);
-    pool_stage(clab, (const uint4*)A.lab + (size_t)j * chunks, chunks, lane, clsg);
-    pool_sign(A.dims, A.fam, clab, clsg, lane);
+    pool_stage(clab, lab + (size_t)j * chunks, chunks, lane, clsg);
+    pool_sign(A.dims, fam, clab, clsg, lane);
     pool_stage(ssig + (size_t)j * chunks, clsg, chunks, lane);
   }
-  for (int j = lane; j < MIQP_POOL_MAX; j += 64) A.has_sig[j] = j < n0 && A.last[j].status == 0 ? 1 : 0;
+  for (int j = lane; j < MIQP_POOL_MAX; j += 64) has_sig[j] = j < n0 && last[j].status == 0 ? 1 : 0;
+  // the pair's sums over its records, one per lane (at most 32): what the host of a single call sums over its rounds.  A record was live in
+  // rounds 1 .. |solves|, so the largest |solves| is the number of rounds - of launch groups - the pair took part in
+  {
+    const bool mine = lane < n0 + ns;
+    const int sv = mine ? solves[lane] : 0;
+    int rounds = abs(sv), all = abs(sv), it = mine ? A.acc_it[W.first + lane] : 0, still = mine && lane >= n0 && sv < 0 ? 1 : 0;
+    for (int d = 32; d >= 1; d >>= 1) { rounds = max(rounds, __shfl_xor(rounds, d, 64)); all += __shfl_xor(all, d, 64); it += __shfl_xor(it, d, 64); still += __shfl_xor(still, d, 64); }
+    if (lane == 0) { int* const st = A.state + (size_t)p * POOL_CARRY_STATE; st[2] = rounds; st[3] = all; st[4] = it; st[5] = still; }
+  }
   // lane k holds source entry k: its record of `out` as far as it is known without a visit, and the objective the visiting order goes by
   double key = POOL_ADMIT_NONE;
   if (lane < ns) {
-    const bool bad = A.unmappable[lane] != 0;
-    const miqp_fixed_result_c r = A.first[n0 + lane];
+    const bool bad = A.unmappable[pb + lane] != 0;
+    const miqp_fixed_result_c r = A.first[W.first + n0 + lane];
     const bool feasible = !bad && r.status == 0 && r.objective < POOL_ADMIT_NONE;
     miqp_pool_carry_c o;
-    o.status = bad ? POOL_CARRY_UNMAPPABLE : POOL_CARRY_INFEASIBLE; o.place = -1; o.solves = bad ? 0 : abs(A.solves[n0 + lane]); o.iterations = bad ? 0 : r.iterations;
+    o.status = bad ? POOL_CARRY_UNMAPPABLE : POOL_CARRY_INFEASIBLE; o.place = -1; o.solves = bad ? 0 : abs(solves[n0 + lane]); o.iterations = bad ? 0 : r.iterations;
     o.objective = bad ? __longlong_as_double(0x7FF8000000000000ll) : r.objective; o.reserved = 0; o.reserved1 = 0;
-    A.out[lane] = o;
+    out[lane] = o;
     if (feasible) key = r.objective;
   }
   __syncthreads();
   int n = n0, added = 0;
-  double obj0 = n0 > 0 ? A.pool_obj[0] : 0.0;
+  double obj0 = n0 > 0 ? pool_obj[0] : 0.0;
   for (int visit = 0; visit < ns; ++visit) {
     double bo = key; int bg = key < POOL_ADMIT_NONE ? lane : 0x7FFFFFFF;
     pool_wave_argmin(bo, bg);
@@ -135,42 +177,45 @@ __global__ __launch_bounds__(64) void pool_carry_admit_kernel(const PoolCarryArg
     int st;
     if (n > 0 && !pool_within_cap(obj0, bo, A.max_rel)) st = POOL_CARRY_BEYOND_CAP;
     else {
-      pool_stage(cand, (const uint4*)A.shifted + (size_t)bg * chunks, chunks, lane, csg);
-      pool_sign(A.dims, A.fam, cand, csg, lane);
+      pool_stage(cand, shifted + (size_t)bg * chunks, chunks, lane, csg);
+      pool_sign(A.dims, fam, cand, csg, lane);
       if (pool_known(csg, sig, n, chunks, lane)) st = POOL_CARRY_KNOWN;
-      else if (A.solves[n0 + bg] == 0 || A.last[n0 + bg].status != 0) st = POOL_CARRY_SETTLED_KNOWN;   // (no settled labels)
+      else if (solves[n0 + bg] == 0 || last[n0 + bg].status != 0) st = POOL_CARRY_SETTLED_KNOWN;   // (no settled labels)
       else {
-        pool_stage(clab, (const uint4*)A.lab + (size_t)(n0 + bg) * chunks, chunks, lane, clsg);
-        pool_sign(A.dims, A.fam, clab, clsg, lane);
-        if (pool_known(clsg, ssig, n, chunks, lane, A.has_sig)) st = POOL_CARRY_SETTLED_KNOWN;
+        pool_stage(clab, lab + (size_t)(n0 + bg) * chunks, chunks, lane, clsg);
+        pool_sign(A.dims, fam, clab, clsg, lane);
+        if (pool_known(clsg, ssig, n, chunks, lane, has_sig)) st = POOL_CARRY_SETTLED_KNOWN;
         else if (n >= K) st = POOL_CARRY_NO_PLACE;
         else {
           for (int c = lane; c < chunks; c += 64) { pool[(size_t)n * chunks + c] = cand[c]; sig[(size_t)n * chunks + c] = csg[c]; ssig[(size_t)n * chunks + c] = clsg[c]; }
-          if (lane == 0) { A.pool_obj[n] = bo; A.has_sig[n] = 1; A.out[bg].place = n; }
+          if (lane == 0) { pool_obj[n] = bo; has_sig[n] = 1; out[bg].place = n; }
           if (n == 0) obj0 = bo;
           st = POOL_CARRY_ADMITTED; n++; added++;
         }
       }
     }
-    if (lane == 0) A.out[bg].status = st;
+    if (lane == 0) out[bg].status = st;
     __syncthreads();   // (the appended signatures are compared with the next record's)
   }
-  if (lane == 0) { A.state[0] = n; A.state[1] = added; }
+  if (lane == 0) { A.state[(size_t)p * POOL_CARRY_STATE] = n; A.state[(size_t)p * POOL_CARRY_STATE + 1] = added; }
 }
 
 // buffers of the call beside the settle rounds', cached per device (DevArr: grown, not shrunk), and the events around its two kernels
+// Per place and per pair, so they grow with the pairs of a call; `first` with its records (np pairs, nrec records, nr and ne map words in all)
 struct PoolCarryDev {
   DevArr<signed char> src, shifted, pool, sig, csig; DevArr<int> rmap, emap, unmappable, has_sig, state; DevArr<double> pool_obj; DevArr<miqp_fixed_result_c> first; DevArr<miqp_pool_carry_c> out;
+  DevArr<PoolCarryPair> pair;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  bool ensure(size_t fl, size_t nr, size_t ne) {
-    const size_t m = MIQP_POOL_MAX;
+  bool ensure(size_t np, size_t nrec, size_t fl, size_t nr, size_t ne) {
+    const size_t m = np * MIQP_POOL_MAX, f = MIQP_POOL_MAX;
     for (auto& e : ev) if (!e) HIP_OK(hipEventCreate(&e));
-    return src.need(m * fl) && shifted.need(m * fl) && pool.need(m * fl) && sig.need(m * fl) && csig.need(m * fl) && rmap.need(nr, 256) && emap.need(ne, 64) && unmappable.need(m) &&
-           has_sig.need(m) && state.need(2) && pool_obj.need(m) && first.need(2 * m) && out.need(m);
+    return src.need(m * fl, f * fl) && shifted.need(m * fl, f * fl) && pool.need(m * fl, f * fl) && sig.need(m * fl, f * fl) && csig.need(m * fl, f * fl) && rmap.need(nr, 256) && emap.need(ne, 64) &&
+           unmappable.need(m, f) && has_sig.need(m, f) && state.need(np * POOL_CARRY_STATE, 64) && pool_obj.need(m, f) && first.need(nrec, 2 * f) && out.need(m, f) && pair.need(np, 16);
   }
 };
 
 thread_local double g_pool_carry_last[2] = {0.0, 0.0};   // seconds of the calling thread's last carry in pool_shift_kernel and in pool_carry_admit_kernel
+thread_local int g_pool_carry_multi_last[2] = {0, 0};    // rounds and launch groups of the calling thread's last miqp_solver_pool_carry_multi (miqp_gpu_pool_carry_multi_last)
 
 // Both maps of a carry from the two loaded instances, and what the carry refuses of a pair of instances (err: why).  rmap: C x p_src, emap: E of src
 bool pool_carry_build_maps(const HostInst& A, const HostInst& B, std::vector<int>& rmap, int& p_src, std::vector<int>& emap, std::string& err) {
@@ -196,79 +241,165 @@ bool pool_carry_build_maps(const HostInst& A, const HostInst& B, std::vector<int
   return true;
 }
 
-// what the call found out before it touches a device
-struct PoolCarryPlan { Layout Y; int ns, n0, K, p_src; std::vector<int> rmap, emap; };
+// what the call found out of one pair before it touches a device
+struct PoolCarryPlan { miqp_solver_t* dst = nullptr; const miqp_solver_t* src = nullptr; int ns = 0, n0 = 0, K = 0, p_src = 0; std::vector<int> rmap, emap; };
 
-// The device part of the carry.  own: the destination's n0 entries and src: the source's ns, both completed as miqp_solver_solve_decisions completes
-// decision bytes.  false: HIP error or a refusal (err)
-struct PoolCarryOut { std::vector<miqp_pool_carry_c> out; std::vector<signed char> fix; std::vector<double> obj; std::vector<int> solves; int n = 0, added = 0; PoolSettleTally tally; float dev_ms = 0, shift_ms = 0, admit_ms = 0; std::string err; };
-bool pool_carry_run(const FixedCall& call, const PoolCarryPlan& P, int fam, int shift, double max_rel, const std::vector<signed char>& own, const std::vector<double>& own_obj, const std::vector<signed char>& src, PoolCarryOut& O) {
-  DevCtx& X = *call.X; DevBuf& B = X.B; hipStream_t st = X.stream; const Layout& Y = P.Y;
-  const size_t fl = (size_t)Y.fixlen; const int n = P.n0 + P.ns;
+// The host side of a call's uploads: the pairs' words, their maps in a row, and the records - own (the destinations' entries) and src (the sources'),
+// both completed as miqp_solver_solve_decisions completes decision bytes: the bytes behind them are "none"
+struct PoolCarryStage {
+  int n = 0;   // records of the call
+  std::vector<PoolCarryPair> pair; std::vector<int> rmap, emap, live0, inst; std::vector<signed char> src, pool, cur; std::vector<double> obj;
+  PoolCarryStage(const std::vector<PoolCarryPlan>& P, const Layout& Y) {
+    const size_t fl = (size_t)Y.fixlen, D = (size_t)Y.f_c2n, np = P.size(), m = np * MIQP_POOL_MAX;
+    pair.resize(np);
+    for (size_t q = 0; q < np; ++q) {
+      pair[q] = PoolCarryPair{n, P[q].n0, P[q].ns, P[q].K, P[q].dst->pool_fam, P[q].p_src, (int)P[q].emap.size(), (int)rmap.size(), (int)emap.size()};
+      rmap.insert(rmap.end(), P[q].rmap.begin(), P[q].rmap.end()); emap.insert(emap.end(), P[q].emap.begin(), P[q].emap.end());
+      n += P[q].n0 + P[q].ns;
+    }
+    src.assign(m * fl, (signed char)-1); pool.assign(m * fl, (signed char)-1); cur.assign((size_t)n * fl, (signed char)-1); obj.assign(m, 0.0);
+    live0.assign(n, 0); inst.resize(n);   // (the destinations' own entries are live in round 1; the shift kernel says which carried ones are)
+    for (size_t q = 0; q < np; ++q) {
+      const PoolCarryPlan& p = P[q]; const size_t pb = q * MIQP_POOL_MAX, first = (size_t)pair[q].first;
+      for (int j = 0; j < p.n0; ++j) {
+        std::memcpy(cur.data() + (first + j) * fl, p.dst->pool_fix.data() + (size_t)j * fl, D);
+        std::memcpy(pool.data() + (pb + j) * fl, p.dst->pool_fix.data() + (size_t)j * fl, D);
+        obj[pb + j] = p.dst->pool_obj[j]; live0[first + j] = 1;
+      }
+      for (int k = 0; k < p.ns; ++k) std::memcpy(src.data() + (pb + k) * fl, p.src->pool_fix.data() + (size_t)k * fl, D);
+      for (int r = 0; r < p.n0 + p.ns; ++r) inst[first + r] = (int)q;
+    }
+  }
+};
+
+// The device part of the carry of the call's pairs: pair q carries into handle q of the open call.  false: HIP error or a refusal (err); nothing of
+// any handle has been touched
+struct PoolCarryOut {
+  std::vector<miqp_pool_carry_c> out; std::vector<signed char> fix; std::vector<double> obj;   // the places at the end, MIQP_POOL_MAX per pair
+  std::vector<int> state;   // POOL_CARRY_STATE words per pair
+  PoolSettleTally tally; float dev_ms = 0, shift_ms = 0, admit_ms = 0; std::string err;
+};
+bool pool_carry_run(const FixedCall& call, const std::vector<PoolCarryPlan>& P, const PoolCarryStage& G, int shift, double max_rel, PoolCarryOut& O) {
+  DevCtx& X = *call.X; DevBuf& B = X.B; hipStream_t st = X.stream; const Layout& Y = call.Y;
+  const size_t fl = (size_t)Y.fixlen; const int np = (int)P.size(), m = np * MIQP_POOL_MAX, n = G.n;
   static const char* const name = "miqp_solver_pool_carry";
+  if (np != call.n || np < 1 || n < 1 || n > FB_CAP) return false;
   if (4 * fl > POOL_EXPLORE_LDS_MAX) {
     O.err = std::string(name) + ": the fix record of this shape does not fit the LDS of pool_carry_admit_kernel four times";
     std::fprintf(stderr, "[miqp_gpu] %s (%zu bytes)\n", O.err.c_str(), 4 * fl); return false;
   }
   if (!pool_label_fits(Y, name, O.err)) return false;
   PoolImproveDev& R = call_dev<PoolImproveDev>(X.device); PoolSettleDev& W = call_dev<PoolSettleDev>(X.device); PoolCarryDev& Q = call_dev<PoolCarryDev>(X.device);
-  if (!R.ensure((size_t)Y.N * Y.nz) || !W.ensure((size_t)n, fl) || !Q.ensure(fl, P.rmap.size(), std::max<size_t>(P.emap.size(), 1)) || !pool_label_set_lds(Y)) return false;
+  if (!R.ensure((size_t)Y.N * Y.nz) || !W.ensure((size_t)n, fl) || !Q.ensure((size_t)np, (size_t)n, fl, std::max<size_t>(G.rmap.size(), 1), std::max<size_t>(G.emap.size(), 1)) || !pool_label_set_lds(Y)) return false;
   HIP_OK(hipFuncSetAttribute((const void*)pool_shift_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * fl)));
   HIP_OK(hipFuncSetAttribute((const void*)pool_carry_admit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * fl)));
   const DevBuf Bp = fixed_chain_settings(B);
   const PoolSettleArgs S = pool_settle_args(W, B, Y, n);
   PoolCarryArgs A;
-  A.dims = pool_dims(Y); A.fixlen = (int)fl; A.fam = fam; A.ns = P.ns; A.n0 = P.n0; A.K = P.K; A.shift = shift;
-  A.maps = PoolCarryMaps{Q.rmap, P.p_src, Q.emap, (int)P.emap.size()};
-  A.src = Q.src; A.shifted = Q.shifted; A.unmappable = Q.unmappable; A.lab = W.cur; A.moved = W.moved; A.solves = W.solves; A.last = W.last; A.first = Q.first;
+  A.dims = pool_dims(Y); A.fixlen = (int)fl; A.np = np; A.shift = shift; A.pair = Q.pair; A.rmap = Q.rmap; A.emap = Q.emap;
+  A.src = Q.src; A.shifted = Q.shifted; A.unmappable = Q.unmappable; A.lab = W.cur; A.moved = W.moved; A.solves = W.solves; A.acc_it = W.acc_it; A.last = W.last; A.first = Q.first;
   A.pool = Q.pool; A.pool_obj = Q.pool_obj; A.sig = Q.sig; A.csig = Q.csig; A.has_sig = Q.has_sig; A.max_rel = max_rel; A.out = Q.out; A.state = Q.state;
-  std::vector<int> live0(n, 0); for (int j = 0; j < P.n0; ++j) live0[j] = 1;   // (the destination's own entries are live in round 1; the shift kernel says which carried ones are)
   HIP_OK(hipMemsetAsync(B.batch_inst, 0, (size_t)FB_CHUNK * 4, st));
-  HIP_OK(hipMemcpyAsync(Q.src, src.data(), (size_t)P.ns * fl, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(Q.rmap, P.rmap.data(), P.rmap.size() * sizeof(int), hipMemcpyHostToDevice, st));
-  if (!P.emap.empty()) HIP_OK(hipMemcpyAsync(Q.emap, P.emap.data(), P.emap.size() * sizeof(int), hipMemcpyHostToDevice, st));
-  if (P.n0 > 0) {
-    HIP_OK(hipMemcpyAsync(W.cur, own.data(), (size_t)P.n0 * fl, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(Q.pool, own.data(), (size_t)P.n0 * fl, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(Q.pool_obj, own_obj.data(), (size_t)P.n0 * sizeof(double), hipMemcpyHostToDevice, st));
-  }
-  HIP_OK(hipMemcpyAsync(W.moved, live0.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemsetAsync(W.inst, 0, (size_t)n * sizeof(int), st)); HIP_OK(hipMemsetAsync(W.round_it, 0, (size_t)n * sizeof(int), st));
+  HIP_OK(hipMemcpyAsync(Q.pair, G.pair.data(), (size_t)np * sizeof(PoolCarryPair), hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(Q.src, G.src.data(), (size_t)m * fl, hipMemcpyHostToDevice, st));
+  if (!G.rmap.empty()) HIP_OK(hipMemcpyAsync(Q.rmap, G.rmap.data(), G.rmap.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  if (!G.emap.empty()) HIP_OK(hipMemcpyAsync(Q.emap, G.emap.data(), G.emap.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(W.cur, G.cur.data(), (size_t)n * fl, hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(Q.pool, G.pool.data(), (size_t)m * fl, hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(Q.pool_obj, G.obj.data(), (size_t)m * sizeof(double), hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(W.moved, G.live0.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(W.inst, G.inst.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemsetAsync(W.round_it, 0, (size_t)n * sizeof(int), st));
   HIP_OK(hipMemsetAsync(W.solves, 0, (size_t)n * sizeof(int), st)); HIP_OK(hipMemsetAsync(W.acc_it, 0, (size_t)n * sizeof(int), st));
   HIP_OK(hipMemsetAsync(W.last, 0xFF, (size_t)n * sizeof(miqp_fixed_result_c), st)); HIP_OK(hipMemsetAsync(Q.first, 0xFF, (size_t)n * sizeof(miqp_fixed_result_c), st));   // (status -1: never solved)
   HIP_OK(hipEventRecord(X.ev0, st));
   HIP_OK(hipEventRecord(Q.ev[0], st));
-  hipLaunchKernelGGL(pool_shift_kernel, dim3(P.ns), dim3(64), 2 * fl, st, A);
+  hipLaunchKernelGGL(pool_shift_kernel, dim3(m), dim3(64), 2 * fl, st, A);
   HIP_OK(hipGetLastError());
   HIP_OK(hipEventRecord(Q.ev[1], st));
   int live = 0;
-  if (!pool_settle_compact(X, S, live, O.tally)) return false;   // (waits: live0 is a local)
+  if (!pool_settle_compact(X, S, live, O.tally)) return false;   // (waits: the stage is the caller's and outlives the call)
   if (!pool_settle_rounds(call, Bp, S, R.Z, 1, live, O.tally, 1)) return false;
   HIP_OK(hipMemcpyAsync(Q.first, W.last, (size_t)n * sizeof(miqp_fixed_result_c), hipMemcpyDeviceToDevice, st));
   if (!pool_settle_rounds(call, Bp, S, R.Z, 2, live, O.tally)) return false;
   HIP_OK(hipEventRecord(Q.ev[2], st));
-  hipLaunchKernelGGL(pool_carry_admit_kernel, dim3(1), dim3(64), 4 * fl, st, A);
+  hipLaunchKernelGGL(pool_carry_admit_kernel, dim3(np), dim3(64), 4 * fl, st, A);
   HIP_OK(hipGetLastError());
   HIP_OK(hipEventRecord(Q.ev[3], st));
   HIP_OK(hipEventRecord(X.ev1, st));
-  int state[2] = {0, 0};
-  O.out.resize(P.ns); O.fix.resize((size_t)MIQP_POOL_MAX * fl); O.obj.resize(MIQP_POOL_MAX); O.solves.resize(n);
-  HIP_OK(hipMemcpyAsync(state, Q.state, sizeof state, hipMemcpyDeviceToHost, st));
-  HIP_OK(hipMemcpyAsync(O.out.data(), Q.out, (size_t)P.ns * sizeof(miqp_pool_carry_c), hipMemcpyDeviceToHost, st));
-  HIP_OK(hipMemcpyAsync(O.fix.data(), Q.pool, (size_t)MIQP_POOL_MAX * fl, hipMemcpyDeviceToHost, st));
-  HIP_OK(hipMemcpyAsync(O.obj.data(), Q.pool_obj, (size_t)MIQP_POOL_MAX * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIP_OK(hipMemcpyAsync(O.solves.data(), W.solves, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
+  O.state.assign((size_t)np * POOL_CARRY_STATE, 0); O.out.resize(m); O.fix.resize((size_t)m * fl); O.obj.resize(m);
+  HIP_OK(hipMemcpyAsync(O.state.data(), Q.state, O.state.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(O.out.data(), Q.out, (size_t)m * sizeof(miqp_pool_carry_c), hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(O.fix.data(), Q.pool, (size_t)m * fl, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(O.obj.data(), Q.pool_obj, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, st));
   HIP_OK(hipStreamSynchronize(st)); HIP_OK(hipGetLastError());
   (void)hipEventElapsedTime(&O.dev_ms, X.ev0, X.ev1); (void)hipEventElapsedTime(&O.shift_ms, Q.ev[0], Q.ev[1]); (void)hipEventElapsedTime(&O.admit_ms, Q.ev[2], Q.ev[3]);
-  O.n = state[0]; O.added = state[1];
-  if (O.n != P.n0 + O.added || O.added < 0 || O.added > P.ns || O.n > P.K) { std::fprintf(stderr, "[miqp_gpu] %s: %d entries behind %d, %d admitted\n", name, O.n, P.n0, O.added); return false; }
+  for (int q = 0; q < np; ++q) {
+    const int* const s = O.state.data() + (size_t)q * POOL_CARRY_STATE;
+    if (s[0] != P[q].n0 + s[1] || s[1] < 0 || s[1] > P[q].ns || s[0] > P[q].K || s[2] < 0 || s[2] > POOL_PASSES || s[3] < 0 || s[4] < 0 || s[5] < 0 || s[5] > P[q].ns) {
+      std::fprintf(stderr, "[miqp_gpu] %s: pair %d: %d entries behind %d, %d admitted, %d rounds\n", name, q, s[0], P[q].n0, s[1], s[2]); return false;
+    }
+  }
   return true;
+}
+
+// The carry of pairs that all take part (entries to carry, a free place), behind every refusal but -3: one lock, one context over the destinations,
+// one upload, the run, and - behind its last read-back - what the handles keep: the admitted entries behind the old ones, which stay as the handle
+// holds them, the dropped refined pool, last_timing and the "still moved" text.  outs[q]: the `out` rows of pair q, counts[q]: its admitted
+// entries.  Entries admitted in all, or -3 (the destinations then carry the run's refusal, if it gave one)
+int pool_carry_call(const std::vector<PoolCarryPlan>& P, const Layout& Y, int shift, double max_rel, double t_call, miqp_pool_carry_c* const* outs, int* counts, int* rounds = nullptr, int* groups = nullptr) {
+  static const char* const name = "miqp_solver_pool_carry";
+  const int np = (int)P.size(); const size_t fl = (size_t)Y.fixlen;
+  const PoolCarryStage G(P, Y);
+  const double setup_s = wall_s() - t_call;
+  std::vector<miqp_solver_t*> dsts(np);
+  for (int q = 0; q < np; ++q) dsts[q] = P[q].dst;
+  FixedCall call;
+  if (call.open(dsts.data(), np, Y) != 0) return -3;
+  PoolCarryOut O;
+  if (!pool_carry_run(call, P, G, shift, max_rel, O)) {
+    (void)hipStreamSynchronize(call.X->stream);
+    if (!O.err.empty()) for (int q = 0; q < np; ++q) dsts[q]->err = O.err;
+    return -3;
+  }
+  const double call_s = wall_s() - t_call;
+  int all = 0, most = 0;
+  for (int q = 0; q < np; ++q) {
+    miqp_solver_t* dst = dsts[q]; const int n0 = P[q].n0; const int* const s = O.state.data() + (size_t)q * POOL_CARRY_STATE;
+    const signed char* const pf = O.fix.data() + (size_t)q * MIQP_POOL_MAX * fl; const double* const po = O.obj.data() + (size_t)q * MIQP_POOL_MAX;
+    dst->pool_fix.resize((size_t)n0 * fl); dst->pool_obj.resize(n0);
+    dst->pool_fix.insert(dst->pool_fix.end(), pf + (size_t)n0 * fl, pf + (size_t)s[0] * fl);
+    dst->pool_obj.insert(dst->pool_obj.end(), po + n0, po + s[0]);
+    dst->pool_n = s[0]; dst->pool_fixlen = (int)fl;
+    if (!dst->has_sol && s[0] > 0) dst->pool_carried = true;   // (a pool without a solve behind it: the carried entries are all it holds)
+    dst->pr_n = 0; std::vector<char>().swap(dst->pr_ok); std::vector<signed char>().swap(dst->pr_fix); std::vector<double>().swap(dst->pr_Z);
+    for (int k = 0; k < P[q].ns; ++k) outs[q][k] = O.out[(size_t)q * MIQP_POOL_MAX + k];
+    counts[q] = s[1];
+    if (s[5]) {
+      char msg[200]; std::snprintf(msg, sizeof msg, "%s: the labels of %d carried records still moved after %d solves; their settled signature is that of the last labels", name, s[5], POOL_PASSES);
+      dst->err = msg;
+    }
+    dst->setup[0] = setup_s;
+    dst->timing[0] = call_s; dst->timing[1] = O.dev_ms * 1e-3; dst->timing[2] = s[2]; dst->timing[3] = (double)s[3]; dst->timing[4] = (double)s[4]; dst->timing[5] = s[5] ? 1 : 0;
+    all += s[1]; most = std::max(most, s[2]);
+  }
+  g_pool_carry_last[0] = O.shift_ms * 1e-3; g_pool_carry_last[1] = O.admit_ms * 1e-3;
+  if (rounds) *rounds = most;
+  if (groups) *groups = O.tally.groups;
+  return all;
 }
 
 // what both entries refuse of a pair of handles, -1 or -2, else 0 with the maps
 int pool_carry_pair(const miqp_solver_t* src, const miqp_solver_t* dst, std::vector<int>& rmap, int& p_src, std::vector<int>& emap, std::string& err) {
   if (!src || !dst || src == dst || !src->has_inst || !dst->has_inst) return -1;
   return pool_carry_build_maps(src->inst, dst->inst, rmap, p_src, emap, err) ? 0 : -2;
+}
+
+// the kept pools of a pair hold records of the Layout's length
+bool pool_carry_fits(const PoolCarryPlan& P, const Layout& Y) {
+  const size_t fl = (size_t)Y.fixlen;
+  if (P.ns > 0 && (P.src->pool_fixlen != Y.fixlen || P.src->pool_fix.size() < (size_t)P.ns * fl)) return false;
+  return P.n0 == 0 || (P.dst->pool_fixlen == Y.fixlen && P.dst->pool_fix.size() >= (size_t)P.n0 * fl && P.dst->pool_obj.size() >= (size_t)P.n0);
 }
 
 }  // namespace
@@ -301,58 +432,80 @@ int miqp_solver_pool_carry_maps(const miqp_solver_t* src, const miqp_solver_t* d
 }
 
 int miqp_solver_pool_carry(miqp_solver_t* dst, const miqp_solver_t* src, int shift, double max_rel, miqp_pool_carry_c* out, int cap) {
-  static const char* const name = "miqp_solver_pool_carry";
   if (dst) dst->err.clear();   // (miqp_solver_last_error speaks of this call from here on)
   if (!out || cap < 0 || max_rel != max_rel) return -1;
-  PoolCarryPlan P; std::string err;
+  std::vector<PoolCarryPlan> one(1);
+  PoolCarryPlan& P = one[0]; std::string err;
   if (const int rc = pool_carry_pair(src, dst, P.rmap, P.p_src, P.emap, err)) { if (dst && !err.empty()) dst->err = err; return rc; }
   if (shift < 1 || shift > dst->inst.N - 2) return -2;
+  P.dst = dst; P.src = src;
   P.K = std::min(dst->pool_cap, MIQP_POOL_MAX);
   if (P.K <= 0 || dst->pool_fam < 1 || dst->pool_fam >= POOL_FAM_TIMING) return -2;
   P.ns = std::min(miqp_solver_pool_count(src), MIQP_POOL_MAX); P.n0 = miqp_solver_pool_count(dst);
   if (cap < P.ns) return -2;
-  miqp_solver_t* one[1] = {dst};
-  BatchShape bs = batch_layout(one, 1);
+  miqp_solver_t* h[1] = {dst};
+  BatchShape bs = batch_layout(h, 1);
   if (!bs.ok) { dst->err = bs.err; return -2; }
-  P.Y = bs.Y;
-  const size_t fl = (size_t)P.Y.fixlen, D = (size_t)P.Y.f_c2n;
-  if (P.ns > 0 && (src->pool_fixlen != P.Y.fixlen || src->pool_fix.size() < (size_t)P.ns * fl)) return -1;
-  if (P.n0 > 0 && (dst->pool_fixlen != P.Y.fixlen || dst->pool_fix.size() < (size_t)P.n0 * fl || dst->pool_obj.size() < (size_t)P.n0)) return -1;
+  if (!pool_carry_fits(P, bs.Y)) return -1;
   if (P.ns == 0 || P.n0 >= P.K) return 0;   // (nothing to carry, or no free place: no device is touched)
   { int ndev = 0; if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return -3; }
   const double t_call = wall_s();
-  // decision bytes, completed as miqp_solver_solve_decisions completes them: the bytes behind them are "none"
-  std::vector<signed char> own((size_t)P.n0 * fl, (signed char)-1), from((size_t)P.ns * fl, (signed char)-1);
-  for (int j = 0; j < P.n0; ++j) std::memcpy(own.data() + (size_t)j * fl, dst->pool_fix.data() + (size_t)j * fl, D);
-  for (int k = 0; k < P.ns; ++k) std::memcpy(from.data() + (size_t)k * fl, src->pool_fix.data() + (size_t)k * fl, D);
-  const std::vector<double> own_obj(dst->pool_obj.begin(), dst->pool_obj.begin() + P.n0);
-  const double setup_s = wall_s() - t_call;
-  FixedCall call;
-  if (call.open(one, 1, P.Y) != 0) return -3;
-  PoolCarryOut O;
-  if (!pool_carry_run(call, P, dst->pool_fam, shift, max_rel, own, own_obj, from, O)) {
-    (void)hipStreamSynchronize(call.X->stream);
-    if (!O.err.empty()) dst->err = O.err;
-    return -3;
+  int added = 0;
+  return pool_carry_call(one, bs.Y, shift, max_rel, t_call, &out, &added);
+}
+
+int miqp_solver_pool_carry_multi(miqp_solver_t* const* dsts, const miqp_solver_t* const* srcs, int n, int shift, double max_rel, miqp_pool_carry_c* out, int cap, int* counts) {
+  static const char* const name = "miqp_solver_pool_carry_multi";
+  if (!dsts || !srcs || !out || !counts || n <= 0 || cap < 0 || max_rel != max_rel) return -1;
+  if (n > FB_CAP / (2 * MIQP_POOL_MAX)) return -5;   // (on the count alone: the arrays are not read)
+  for (int p = 0; p < n; ++p) if (!dsts[p] || !srcs[p] || srcs[p] == dsts[p] || !dsts[p]->has_inst || !srcs[p]->has_inst) return -1;
+  {  // a destination named twice, or one that is the source of another pair: the answer would depend on the order of the pairs
+    std::vector<const miqp_solver_t*> d(dsts, dsts + n), s(srcs, srcs + n);
+    std::sort(d.begin(), d.end()); std::sort(s.begin(), s.end());
+    if (std::adjacent_find(d.begin(), d.end()) != d.end()) return -1;
+    for (const miqp_solver_t* h : d) if (std::binary_search(s.begin(), s.end(), h)) return -1;
   }
-  // the old entries stay as the handle holds them; the admitted ones go behind them
-  dst->pool_fix.resize((size_t)P.n0 * fl); dst->pool_obj.resize(P.n0);
-  dst->pool_fix.insert(dst->pool_fix.end(), O.fix.begin() + (size_t)P.n0 * fl, O.fix.begin() + (size_t)O.n * fl);
-  dst->pool_obj.insert(dst->pool_obj.end(), O.obj.begin() + P.n0, O.obj.begin() + O.n);
-  dst->pool_n = O.n; dst->pool_fixlen = (int)fl;
-  if (!dst->has_sol && O.n > 0) dst->pool_carried = true;   // (a pool without a solve behind it: the carried entries are all it holds)
-  dst->pr_n = 0; std::vector<char>().swap(dst->pr_ok); std::vector<signed char>().swap(dst->pr_fix); std::vector<double>().swap(dst->pr_Z);
-  for (int k = 0; k < P.ns; ++k) out[k] = O.out[k];
-  int still = 0;
-  for (int k = 0; k < P.ns; ++k) if (O.solves[P.n0 + k] < 0) still++;
-  if (still) {
-    char msg[200]; std::snprintf(msg, sizeof msg, "%s: the labels of %d carried records still moved after %d solves; their settled signature is that of the last labels", name, still, POOL_PASSES);
-    dst->err = msg;
+  // what the single call refuses of a pair with -2, pair by pair: the first refusal decides, and its reason is that destination's last error
+  std::vector<PoolCarryPlan> all(n);
+  for (int p = 0; p < n; ++p) {
+    PoolCarryPlan& P = all[p]; miqp_solver_t* dst = dsts[p]; std::string err;
+    P.dst = dst; P.src = srcs[p];
+    if (shift < 1 || shift > dst->inst.N - 2) return -2;
+    if (!pool_carry_build_maps(srcs[p]->inst, dst->inst, P.rmap, P.p_src, P.emap, err)) { dst->err = err; return -2; }
+    P.K = std::min(dst->pool_cap, MIQP_POOL_MAX);
+    if (P.K <= 0 || dst->pool_fam < 1 || dst->pool_fam >= POOL_FAM_TIMING) {
+      char msg[200]; std::snprintf(msg, sizeof msg, "%s: the destination of pair %d has capacity %d and filter %d; the carry needs a capacity and a filter in 1 .. 15", name, p, dst->pool_cap, dst->pool_fam);
+      dst->err = msg; return -2;
+    }
+    P.ns = std::min(miqp_solver_pool_count(srcs[p]), MIQP_POOL_MAX); P.n0 = miqp_solver_pool_count(dst);
   }
-  dst->setup[0] = setup_s;
-  dst->timing[0] = wall_s() - t_call; dst->timing[1] = O.dev_ms * 1e-3; dst->timing[2] = O.tally.groups; dst->timing[3] = (double)O.tally.solves; dst->timing[4] = (double)O.tally.iterations; dst->timing[5] = still ? 1 : 0;
-  g_pool_carry_last[0] = O.shift_ms * 1e-3; g_pool_carry_last[1] = O.admit_ms * 1e-3;
-  return O.added;
+  BatchShape bs;
+  if (const int rc = fixed_multi_check(dsts, n, bs)) return rc;
+  int most = 0;
+  for (int p = 0; p < n; ++p) { if (!pool_carry_fits(all[p], bs.Y)) return -1; most = std::max(most, all[p].ns); }
+  if (cap < most) return -2;
+  for (int p = 0; p < n; ++p) dsts[p]->err.clear();   // (miqp_solver_last_error of every destination speaks of this call from here on)
+  // a pair takes part when it has entries to carry and its destination a free place
+  std::vector<int> part;
+  for (int p = 0; p < n; ++p) if (all[p].ns > 0 && all[p].n0 < all[p].K) part.push_back(p);
+  if (part.empty()) { for (int p = 0; p < n; ++p) counts[p] = 0; return 0; }   // (nothing to run: no device is touched)
+  { int ndev = 0; if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return -3; }
+  const double t_call = wall_s();
+  const int np = (int)part.size();
+  std::vector<PoolCarryPlan> P(np); std::vector<miqp_pool_carry_c*> outs(np); std::vector<int> added(np, 0);
+  for (int q = 0; q < np; ++q) { P[q] = std::move(all[part[q]]); outs[q] = out + (size_t)part[q] * cap; }
+  int rounds = 0, groups = 0;
+  const int rc = pool_carry_call(P, bs.Y, shift, max_rel, t_call, outs.data(), added.data(), &rounds, &groups);
+  if (rc < 0) return rc;
+  for (int p = 0; p < n; ++p) counts[p] = 0;
+  for (int q = 0; q < np; ++q) counts[part[q]] = added[q];
+  g_pool_carry_multi_last[0] = rounds; g_pool_carry_multi_last[1] = groups;
+  return rc;
+}
+
+void miqp_gpu_pool_carry_multi_last(int* rounds, int* groups) {
+  if (rounds) *rounds = g_pool_carry_multi_last[0];
+  if (groups) *groups = g_pool_carry_multi_last[1];
 }
 
 void miqp_gpu_pool_carry_last(double* shift_s, double* admit_s) {

@@ -153,6 +153,9 @@ def load_library():
     L.miqp_solver_pool_carry.restype = C.c_int; L.miqp_solver_pool_carry.argtypes = [vp, vp, C.c_int, C.c_double, C.POINTER(PoolCarryC), C.c_int]
     L.miqp_gpu_pool_carry_size.restype = C.c_int; L.miqp_gpu_pool_carry_size.argtypes = []
     L.miqp_gpu_pool_carry_last.restype = None; L.miqp_gpu_pool_carry_last.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.miqp_solver_pool_carry_multi.restype = C.c_int
+    L.miqp_solver_pool_carry_multi.argtypes = [C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_int, C.c_double, C.POINTER(PoolCarryC), C.c_int, C.POINTER(C.c_int)]
+    L.miqp_gpu_pool_carry_multi_last.restype = None; L.miqp_gpu_pool_carry_multi_last.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int)]
     if L.miqp_gpu_pool_carry_size() != C.sizeof(PoolCarryC):
         raise RuntimeError("libmiqp_gpu.so and ctypes_types.PoolCarryC disagree on miqp_pool_carry_c (%d / %d bytes): rebuild the library"
                            % (L.miqp_gpu_pool_carry_size(), C.sizeof(PoolCarryC)))
@@ -198,7 +201,8 @@ EXPORTED_SYMBOLS = ["miqp_solver_create", "miqp_solver_destroy", "miqp_solver_se
                     "miqp_solver_canonical_decisions", "miqp_solver_canonical_labels", "miqp_solver_pool_explore_distinct",
                     "miqp_solver_settle_decisions", "miqp_solver_pool_explore_settled", "miqp_gpu_pool_settle_passes",
                     "miqp_solver_pool_explore_multi", "miqp_gpu_pool_explore_plan", "miqp_gpu_pool_explore_multi_last",
-                    "miqp_gpu_pool_shift", "miqp_solver_pool_carry_maps", "miqp_solver_pool_carry", "miqp_gpu_pool_carry_size", "miqp_gpu_pool_carry_last"]
+                    "miqp_gpu_pool_shift", "miqp_solver_pool_carry_maps", "miqp_solver_pool_carry", "miqp_gpu_pool_carry_size", "miqp_gpu_pool_carry_last",
+                    "miqp_solver_pool_carry_multi", "miqp_gpu_pool_carry_multi_last"]
 
 
 # a row of CplexWrapper.launchPlan (NodeLaunch in csrc/miqp_gpu.hip)
@@ -1149,6 +1153,40 @@ def pool_explore_multi_last():
     p, s = C.c_int(0), C.c_int(0)
     load_library().miqp_gpu_pool_explore_multi_last(C.byref(p), C.byref(s))
     return p.value, s.value
+
+
+def carry_solution_pools(dsts, srcs, shift=1, max_rel=-1.0):
+    """the kept entries of many source wrappers carried into the pools of many destination wrappers in one device call
+    (miqp_solver_pool_carry_multi): pair p carries ``srcs[p]`` into ``dsts[p]``.  Per pair (added, [dict per source entry]) - what
+    ``dsts[p].carrySolutionPool(srcs[p], shift, max_rel)`` returns, bit for bit, pool, last timing [2 .. 5] and lastError() behind it included.
+    The settle rounds of all pairs fill common launch groups.  Sources are only read and one may feed several destinations; a pair with nothing
+    to carry or a full destination takes no part and gets (0, []).  Raises ValueError for lists of different lengths and RuntimeError where the
+    library refuses the call (a destination named twice or also a source, destinations of different shape, a pair the single call refuses, no
+    device), on -2 with the first non-empty lastError() among the destinations; a refused call leaves every pool alone."""
+    if len(dsts) != len(srcs):
+        raise ValueError("one source per destination")
+    L = load_library()
+    n = len(dsts)
+    if any(not w._loaded() for w in list(dsts) + list(srcs)):
+        raise RuntimeError("miqp_solver_pool_carry_multi failed (-1): invalid parameters")
+    cap = pool_max()
+    out = (PoolCarryC * (max(n, 1) * cap))(*[PoolCarryC(-1, -1, 0, 0, 0, 0, float("nan")) for _ in range(max(n, 1) * cap)])   # (a pair that takes no part is not written)
+    counts = (C.c_int * max(n, 1))()
+    hd = (C.c_void_p * max(n, 1))(*[w._h for w in dsts]); hs = (C.c_void_p * max(n, 1))(*[w._h for w in srcs])
+    ns = [min(w.solutionPoolCount(), cap) for w in srcs]
+    rc = L.miqp_solver_pool_carry_multi(hd, hs, n, int(shift), float(max_rel), out, cap, counts)
+    if rc < 0:
+        why = next((w.lastError() for w in dsts if w.lastError()), "") if rc == -2 else ""   # (a pair the single call refuses is named in ITS destination's last error)
+        raise RuntimeError("miqp_solver_pool_carry_multi failed (%d)%s" % (rc, ": " + why if why else ""))
+    return [(int(counts[p]), [dict(status=o.status, place=o.place, solves=o.solves, iterations=o.iterations, objective=float(o.objective))
+                              for o in out[p * cap:p * cap + ns[p]] if o.status >= 0]) for p in range(n)]
+
+
+def pool_carry_multi_last():
+    """(rounds, launch groups) the calling thread's last carry_solution_pools ran on the device (miqp_gpu_pool_carry_multi_last)"""
+    r, g = C.c_int(0), C.c_int(0)
+    load_library().miqp_gpu_pool_carry_multi_last(C.byref(r), C.byref(g))
+    return r.value, g.value
 
 
 def certify_last_timing():
