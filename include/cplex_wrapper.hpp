@@ -108,6 +108,7 @@ class CplexWrapper {
       if (!h_) return FAILED_SEG_FAULT;
       miqp_solver_set_pool(h_, poolCapacity_);
       miqp_solver_set_pool_filter(h_, poolFilter_);
+      miqp_solver_set_pool_starts(h_, poolStarts_);
       if (parameterSource_ == DATFILE || (parameterSource_ == MIXED && !parameters_)) {   // MIXED: the C++ inputs when given, else the file
         if (miqp_solver_load_dat(h_, datfile_.c_str()) != 0) return FAILED_SEG_FAULT;
       } else { if (!parameters_ || !pushParameters()) return FAILED_SEG_FAULT; }
@@ -313,6 +314,27 @@ class CplexWrapper {
       for (const miqp_pool_carry_c& o : out) if (o.status >= 0) records->push_back(o);
     return rc;
   }
+  // setSolutionPoolStarts: the handle's miqp_solver_set_pool_starts setting (0: off, the default; at most miqp_gpu_pool_max(); returns 0, -1 when
+  // refused), kept here and handed to the handle like capacity and filter.
+  // NOTE - THROUGH THIS CLASS ALONE NO SOLVE TAKES A START.  A solve takes starts from a pool that a carry put there and that no solve stands
+  // behind.  This class creates its handle and loads its parameters inside callCplex only, so carrySolutionPool always comes behind a solve (the
+  // carried entries then join a pool with a solve behind it), and the next callCplex loads the parameters again, which empties the pool.  A
+  // caller that wants the search of cycle t + 1 to start from the pool of cycle t drives that sequence on the C ABI - miqp_solver_set_params,
+  // miqp_solver_pool_carry into the empty pool, miqp_solver_solve (include/miqp_gpu.h) - or through the Python CplexWrapper, which can load
+  // without solving.  The two methods are here so that the setting travels with a wrapper's configuration and the last solve's answer can be read.
+  int setSolutionPoolStarts(int max_starts) {
+    if (max_starts < 0 || max_starts > miqp_gpu_pool_max()) return -1;
+    poolStarts_ = max_starts;
+    return h_ ? miqp_solver_set_pool_starts(h_, max_starts) : 0;
+  }
+  // solutionPoolStartsLast: per start root the last callCplex took from the carried pool, the entry of the pool after that solve that stands for it
+  // (miqp_solver_pool_starts_last), -1 when the pool holds none; empty when the solve took no starts
+  std::vector<int> solutionPoolStartsLast() const {
+    std::vector<int> place((size_t)miqp_gpu_pool_max(), -1);
+    const int t = h_ ? miqp_solver_pool_starts_last(h_, place.data(), (int)place.size()) : 0;
+    place.resize(t > 0 ? (size_t)std::min<int>(t, (int)place.size()) : 0);
+    return place;
+  }
   SolutionProperties getSolutionProperties() const { return solutionProperties_; }
   void setDebugOutputPrint(bool v) { print_debug_outputs_ = v; }
   void setDebugOutputFilePath(std::string in) { debugOutputFilePath_ = in; }
@@ -467,6 +489,7 @@ class CplexWrapper {
   miqp_solver_t* h_ = nullptr;  // created lazily
   int poolCapacity_ = 0;       // setSolutionPool
   int poolFilter_ = 0;         // setSolutionPoolFilter
+  int poolStarts_ = 0;         // setSolutionPoolStarts
 };
 
 }  // namespace cplex

@@ -597,8 +597,9 @@ int miqp_solver_pool_carry_maps(const miqp_solver_t* src, const miqp_solver_t* d
  * miqp_solver_last_error(dst) is cleared at the start.  miqp_solver_last_timing(dst): out[0] the call, out[1] of which on the device, out[2] launch
  * groups of the settle rounds, out[3] solves (dst's own entries included), out[4] their iterations, out[5] 1 when a carried record still moved after
  * the last settle pass.  The call is a function of the two pools and the two instances alone: reproducible bit for bit.
- * Out of scope: obstacle re-numbering; replacing a kept entry by a better carried one of its class (the climb's job); feeding carried records to the
- * SEARCH as MIP starts (that would change solves).  Many (src, dst) pairs in one call: miqp_solver_pool_carry_multi below.  No reference counterpart. */
+ * Out of scope: obstacle re-numbering; replacing a kept entry by a better carried one of its class (the climb's job).  The carried records of an
+ * EMPTY pool as MIP starts of the solve behind the carry: miqp_solver_set_pool_starts below.  Many (src, dst) pairs in one call:
+ * miqp_solver_pool_carry_multi below.  No reference counterpart. */
 int miqp_solver_pool_carry(miqp_solver_t* dst, const miqp_solver_t* src, int shift, double max_rel, miqp_pool_carry_c* out, int cap);
 /* ---- the carry of many (src, dst) pairs in ONE device call: a scenario-parallel caller drains a queue of handles every
  * cycle.  The carry is almost only settle rounds, and a round costs the same for 30 records as for a thousand: the records of all pairs fill
@@ -632,6 +633,37 @@ int miqp_gpu_pool_carry_size(void);
 /* diagnostic: the seconds the calling thread's last successful miqp_solver_pool_carry spent in pool_shift_kernel and in pool_carry_admit_kernel, from
  * the call's own device events (either may be NULL) */
 void miqp_gpu_pool_carry_last(double* shift_s, double* admit_s);
+/* ---- starts from the carried pool: the solve behind a carry into an EMPTY pool starts its search from the carried manoeuvres - with
+ * this the carry is the whole counterpart of a CPLEX user re-adding the old pool's members as MIP starts of the new model. ----
+ * miqp_solver_set_pool_starts: the most start roots a solve takes from the handle's pool; 0 is off and the default, 1 .. miqp_gpu_pool_max() are
+ * accepted.  Returns 0; -1 for a NULL handle or a value out of range (the previous setting stays).  The setting belongs to the handle and survives
+ * miqp_solver_set_params, as the capacity and the filter do.
+ * A handle TAKES STARTS in a solve when max_starts > 0, its pool is one that miqp_solver_pool_carry (or _carry_multi) put there and that no solve
+ * stands behind (so miqp_solver_set_params has not been called since: it empties the pool), the pool holds an entry whose record length is the
+ * call's, and the first step of the instance is feasible.  Its start roots are the first min(max_starts, entries) entries in pool order, each
+ * completed as miqp_solver_solve_decisions completes decision bytes, with depth word 0 and no repair root, appended behind the root and the roots of
+ * the two slots of miqp_solver_set_warmstart.  They are nodes of round 1: a feasible start is a candidate, the best one is the first incumbent, and
+ * the capture merges every feasible start into the pool of the solve with the leaves of the search - the fallback that was carried in survives the
+ * solve unless `capacity` better classes push it out.  Every entry point that solves takes them - miqp_solver_solve, _solve_batch, _solve_stream,
+ * _solve_batch_multi -, handle by handle; a tree-split call (miqp_solver_solve_split, _solve_split_rccl) IGNORES the setting.
+ * The root records per instance are the call's: 5 in a call in which no handle takes starts - every buffer and every kernel argument then has the
+ * value it has without this setting, and so has every result -, else 5 plus the largest max_starts SETTING among the handles of the call that take
+ * starts (the setting, not the number taken: a receding horizon carries another number of records every cycle).  A device context is rebuilt when
+ * that number changes, as for any other change of a call's shape (about a second for a single solve's context): between a call with starts and
+ * one without, and when the setting changes - not because a loop with one setting carries another number of records every cycle.
+ * No kernel is added or changed.  A start decides every disjunction, so
+ * its relaxation is larger than the on-chip node kernels hold: its record begins with the size mark that sends it to the memory-backed kernel in
+ * round 1 - unmarked it would be handed from kernel to kernel for two rounds and then meet the cutoff of the incumbent found meanwhile.
+ * With fewer nodes per instance and round than root records (at most 21; a batch of thousands of instances in flight runs 16 wide) the roots
+ * behind the first round meet the incumbent of round 1, and a start that is not better than it is dropped like any node: it is then no candidate. */
+int miqp_solver_set_pool_starts(miqp_solver_t* s, int max_starts);
+/* the handle's setting (0: off); -1 for a NULL handle */
+int miqp_solver_get_pool_starts(const miqp_solver_t* s);
+/* the number T of start roots the handle's last solve took from its pool (0: none); for k < min(T, cap) place[k] is the entry of the pool AFTER that
+ * solve that stands for start k - under the handle's filter the entry of the start's plain signature, without a filter the entry of the same
+ * decision bytes - or -1 when the pool holds no such entry.  Computed on the host behind the pool's read-back: needs no device.  New parameters
+ * reset it to 0.  -1: NULL handle (place may be NULL with cap 0) */
+int miqp_solver_pool_starts_last(const miqp_solver_t* s, int* place, int cap);
 
 /* 1 when instances of this shape (NrCars, N) have the dual active-set launches - one or two cars, a horizon of up to 20 steps - else 0 (their node
  * relaxations are interior point solves).  Pure host code: no device is needed or touched.  A call switches the launches off with MIQP_AS=0 */

@@ -142,6 +142,12 @@ struct miqp_solver {
   int pool_fam = 0;   // miqp_solver_set_pool_filter: the families whose signature says which leaves are one entry, 0 = off (a setting like pool_cap: it stays)
   int pr_n = 0; std::vector<char> pr_ok; std::vector<signed char> pr_fix; std::vector<double> pr_Z;
   void drop_pool() { pool_n = 0; pr_n = 0; pool_carried = false; std::vector<signed char>().swap(pool_fix); std::vector<double>().swap(pool_obj); std::vector<char>().swap(pr_ok); std::vector<signed char>().swap(pr_fix); std::vector<double>().swap(pr_Z); }
+  // starts from the carried pool (miqp_solver_set_pool_starts).  pool_starts: the most entries of a carried pool a solve takes as MIP-start
+  // roots, 0 = off (a setting like pool_cap: it stays).  A solve drops the handle's pool when it begins: st_fix holds the st_offer records (st_fixlen
+  // bytes each) it took from a carried pool before that, for prepare_instances.  Of the last solve: st_n start roots, and st_place[k], the entry of the
+  // pool behind the solve that stands for start k (-1: none)
+  int pool_starts = 0, st_offer = 0, st_fixlen = 0, st_n = 0; std::vector<signed char> st_fix; std::vector<int> st_place;
+  void drop_starts() { st_offer = 0; st_fixlen = 0; st_n = 0; std::vector<signed char>().swap(st_fix); std::vector<int>().swap(st_place); }
   std::string err;
 };
 
@@ -1086,6 +1092,8 @@ void split_roots(const Layout& Y, const int* T, std::vector<std::vector<std::pai
 
 // solution pool (solution_pool.hip): the capture launches behind a round's evaluation, `bc` nodes wide
 bool pool_capture(DevCtx& X, int bc);
+// starts from the carried pool (pool_carry.hip, pool_improve.hip): the range check of a decision record
+bool decisions_in_range(const HostInst& I, const Layout& Y, const int* T, const signed char* d);
 
 // ---------------------------------------------------------------- the batch solve: shape of the call
 // `inflight`: instances solved concurrently (<= 0 or >= n: all of them).  With fewer than n the call is a queue drained by
@@ -1095,11 +1103,12 @@ bool pool_capture(DevCtx& X, int bc);
 struct CallShape {
   int n, NS, lanes;          // instances, slots = instances in flight, lanes that share the device
   int npr, open_cap, MAXR;   // nodes per instance and round, near-list capacity asked for, root records per instance
+  int starts;                // of MAXR: the room for start roots from a carried pool - the largest max_starts setting (miqp_solver_set_pool_starts) among the handles that offer any, 0 in a call without such a handle
   bool adaptive_width; int width0, width_max;   // a single solve starts at width0 nodes per round and widens up to width_max
   bool queue_mode, clamp_open;
 };
 // pure: the layout, the options, the sizes of the call and the switches in, the shape out.  Precedence: opts.nodes_per_round > MIQP_NPR > the rules
-CallShape plan_call(const Layout& Y, const miqp_solver_opts& O0, int n, int inflight, int lanes, bool split, const CallSwitches& sw) {
+CallShape plan_call(const Layout& Y, const miqp_solver_opts& O0, int n, int inflight, int lanes, bool split, const CallSwitches& sw, int starts = 0) {
   CallShape sh{};
   sh.n = n; sh.lanes = lanes;
   const int NS = sh.NS = (split || inflight <= 0 || inflight >= n) ? n : inflight;   // slots = instances in flight
@@ -1136,7 +1145,8 @@ CallShape plan_call(const Layout& Y, const miqp_solver_opts& O0, int n, int infl
   // (list entries - 40 B per open node - must fit an eighth of the free device memory: ctx_prepare cuts the capacity when it builds the context)
   if ((size_t)NS * npr >= ((size_t)1 << 20)) npr = (int)((((size_t)1 << 20) - 1) / NS);
   sh.npr = npr; sh.open_cap = open_cap;
-  sh.MAXR = split ? SPLIT_MAXROOTS + 4 : 5;   // root records per instance: the root (or this rank's roots of a tree split), the MIP starts and their repair roots
+  sh.starts = split ? 0 : starts;
+  sh.MAXR = (split ? SPLIT_MAXROOTS + 4 : 5) + sh.starts;   // root records per instance: the root (or this rank's roots of a tree split), the MIP starts and their repair roots, the starts from a carried pool
   sh.queue_mode = NS < n; sh.clamp_open = O0.max_open_nodes <= 0;
   return sh;
 }
@@ -1150,16 +1160,16 @@ struct HostTables {
   std::vector<int> h_done;              // 1: never starts (infeasible first step, no root on this rank)
   std::vector<signed char> roots;       // fix records of all roots, in the order of their record numbers
   std::vector<int> on, od, oc; int nrec = 0;   // root records of every instance (record, depth word; count): the head of its open list at admission
+  std::vector<unsigned char> big;       // size marks of the first big.size() root records (empty without starts from a carried pool: every root starts unmarked)
 };
 
 // per instance (independent, spread over host threads): tables, step-0 check, the fix records of its roots, the raw model sizes
 void prepare_instances(miqp_solver_t* const* S, const Layout& Y, const CallShape& sh, const SplitCtx* split, HostTables& H) {
-  const int n = sh.n, MAXR = sh.MAXR;
+  const int n = sh.n, MAXR = sh.MAXR, WS_MAX = sh.MAXR - sh.starts;   // (the two warm-start slots and their repair roots share the records in front of the pool starts: today's 5)
   H.nD = (size_t)n * Y.dstride; H.nT = (size_t)n * Y.istride;
   H.D.reset(new double[H.nD]); H.T.reset(new int[H.nT]);
   double* const hD = H.D.get(); int* const hT = H.T.get();
   H.h_const.assign(n, 0.0); H.h_gap.resize(n); H.h_tlim.resize(n); H.h_done.assign(n, 0);
-  H.roots.reserve((size_t)MAXR * n * Y.fixlen);
   H.on.assign((size_t)n * MAXR, 0); H.od.assign((size_t)n * MAXR, 0); H.oc.assign(n, 0);
   std::vector<std::vector<std::vector<signed char>>> inst_roots(n);
   std::vector<std::vector<int>> inst_root_depth(n);
@@ -1192,8 +1202,22 @@ void prepare_instances(miqp_solver_t* const* S, const Layout& Y, const CallShape
       std::vector<signed char> rx(Y.fixlen, (signed char)-1);
       bool any_reg = false;
       for (int q = Y.f_reg; q < Y.f_reg + Y.C * Y.N; ++q) { rx[q] = fx[q]; any_reg = any_reg || fx[q] >= 0; }
-      if ((int)R.size() < MAXR) R.push_back(std::move(fx));
-      if (any_reg && (int)R.size() < MAXR) { R.push_back(std::move(rx)); inst_root_depth[k].resize(R.size(), 0); inst_root_depth[k].back() = REPAIR_ROOT; }
+      if ((int)R.size() < WS_MAX) R.push_back(std::move(fx));
+      if (any_reg && (int)R.size() < WS_MAX) { R.push_back(std::move(rx)); inst_root_depth[k].resize(R.size(), 0); inst_root_depth[k].back() = REPAIR_ROOT; }
+    }
+    // starts from the carried pool (miqp_solver_set_pool_starts; the counterpart of a CPLEX user re-adding the old pool's members as MIP starts): the
+    // records the call took from the handle's pool before it dropped it, each completed as miqp_solver_solve_decisions completes decision bytes - the
+    // bytes behind them "none" -, depth word 0, no repair root.  Nodes of round 1 like the starts above: a feasible one is a candidate of the capture
+    // and, the best of them, the first incumbent.  A record with a byte outside its site's alternatives (a carry never admits one) and the handle takes none
+    s->st_n = 0;
+    if (feas0 && !split && s->st_offer > 0 && s->st_fixlen == Y.fixlen) {
+      bool ok = (int)R.size() + s->st_offer <= MAXR && s->st_fix.size() >= (size_t)s->st_offer * Y.fixlen;
+      for (int q = 0; q < s->st_offer && ok; ++q) ok = decisions_in_range(s->inst, Y, &hT[(size_t)k * Y.istride], s->st_fix.data() + (size_t)q * Y.fixlen);
+      for (int q = 0; q < s->st_offer && ok; ++q) {
+        std::vector<signed char> fx(Y.fixlen, (signed char)-1);
+        std::memcpy(fx.data(), s->st_fix.data() + (size_t)q * Y.fixlen, (size_t)Y.f_c2n);
+        R.push_back(std::move(fx)); s->st_n++;
+      }
     }
     inst_root_depth[k].resize(R.size(), 0);
     int rows, bin, cont, nnz; raw_sizes(s->inst, rows, bin, cont, nnz);
@@ -1207,10 +1231,16 @@ void prepare_instances(miqp_solver_t* const* S, const Layout& Y, const CallShape
     for (int t = 0; t < nth; ++t) th.emplace_back([&] { for (int k = next.fetch_add(1); k < n; k = next.fetch_add(1)) prepare_one(k); });
     for (auto& t : th) t.join();
   }
+  { size_t nroot = 0; for (int k = 0; k < n; ++k) nroot += inst_roots[k].size(); H.roots.reserve(nroot * Y.fixlen); }   // (by the counts: not MAXR records for each of a stream's 51 200 handles)
   for (int k = 0; k < n; ++k) {
     if (!h_feas0[k]) H.h_done[k] = 1;
     for (size_t q = 0; q < inst_roots[k].size(); ++q) {
       const auto& fx = inst_roots[k][q];
+      // A start from the carried pool decides every disjunction: its relaxation has more general rows than either on-chip block holds (two cars, 20
+      // steps: over 480 against the 270 - 290 of a tree node).  Unmarked, the standard block would hand it to the larger one and that one to the
+      // memory-backed kernel, a round each - and from round 2 on a start meets the cutoff of round 1's incumbent and is dropped before it is a
+      // candidate.  So its record starts with the size mark those two hand-overs would leave: round 1 relaxes it, without a cutoff
+      if (q + (size_t)S[k]->st_n >= inst_roots[k].size()) { H.big.resize((size_t)H.nrec + 1, 0); H.big.back() = 2; }
       H.roots.insert(H.roots.end(), fx.begin(), fx.end()); H.on[(size_t)k * MAXR + H.oc[k]] = H.nrec++; H.od[(size_t)k * MAXR + H.oc[k]] = inst_root_depth[k][q]; H.oc[k]++;
     }
     if (H.oc[k] == 0) H.h_done[k] = 1;   // (a rank of a tree split may own no root)
@@ -1225,6 +1255,7 @@ bool upload_and_reset(DevCtx& X, const HostTables& H, const CallShape& sh) {
   HIP_OK(hipMemcpyAsync(B.pool_fix, H.roots.data(), H.roots.size(), hipMemcpyHostToDevice, st));
   const int pool0 = H.nrec;
   if (B.pool_big && H.nrec > 0) HIP_OK(hipMemsetAsync(B.pool_big, 0, (size_t)H.nrec, st));   // the root records start unmarked (children are marked or cleared when they are written)
+  if (B.pool_big && !H.big.empty()) HIP_OK(hipMemcpyAsync(B.pool_big, H.big.data(), std::min(H.big.size(), (size_t)H.nrec), hipMemcpyHostToDevice, st));   // ... but the starts from a carried pool (prepare_instances)
   HIP_OK(hipMemcpyAsync(B.pool_count, &pool0, 4, hipMemcpyHostToDevice, st));
   HIP_OK(hipMemsetAsync(B.free_head, 0, 4, st)); HIP_OK(hipMemsetAsync(B.free_tail, 0, 4, st)); HIP_OK(hipMemsetAsync(B.free_limit, 0, 4, st));
   HIP_OK(hipMemcpyAsync((void*)B.root_node, H.on.data(), H.on.size() * 4, hipMemcpyHostToDevice, st));
@@ -1642,12 +1673,25 @@ void report(miqp_solver_t* const* S, int* statuses, const Layout& Y, const HostT
 bool pool_prepare(DevCtx& X, miqp_solver_t* const* S, int n);
 bool pool_read_back(const DevCtx& X, miqp_solver_t* const* S, int n, const Results& R);   // (R.fix: the incumbents' records)
 
+// starts from the carried pool (miqp_solver_set_pool_starts): what a solve takes from the handle's pool before it drops it - the first
+// min(pool_starts, pool_n) entries in pool order of a pool that a carry put there and that no solve stands behind.  A tree split takes none
+void pool_starts_take(miqp_solver* s, bool split) {
+  s->drop_starts();
+  if (split || s->pool_starts <= 0 || !s->has_inst || !s->pool_carried || s->pool_n <= 0 || s->pool_fixlen <= 0) return;
+  const int t = std::min(s->pool_starts, s->pool_n);
+  if (s->pool_fix.size() < (size_t)t * s->pool_fixlen) return;
+  s->st_offer = t; s->st_fixlen = s->pool_fixlen;
+  s->st_fix.assign(s->pool_fix.begin(), s->pool_fix.begin() + (size_t)t * s->pool_fixlen);
+}
+// ... and behind the pool's read-back, on the host: where each start of the solve stands in the pool it left (pool_carry.hip)
+void pool_starts_places(miqp_solver* s, const Layout& Y);
+
 // ---------------------------------------------------------------- the batch solve
 bool solve_batch_impl(miqp_solver_t* const* S, int n, int* statuses, const SplitCtx* split = nullptr, int inflight = 0, int lane = 0, int lanes = 1) {
   // every way out of this function that is not report() at its end (a failed HIP call, a failed exchange) leaves "the solver could not
   // run" behind: a caller's zero-filled status array would otherwise read as SUCCESS for instances that were never solved.  Every phase
   // returns false on such a failure (HIP_OK does, after naming the call) and nothing before report() touches `statuses`
-  for (int k = 0; k < n; ++k) { statuses[k] = MIQP_STATUS_FAILED_SEG_FAULT; if (S[k]) { S[k]->status = MIQP_STATUS_FAILED_SEG_FAULT; S[k]->has_sol = false; S[k]->rescache.reset(); S[k]->drop_pool(); } }
+  for (int k = 0; k < n; ++k) { statuses[k] = MIQP_STATUS_FAILED_SEG_FAULT; if (S[k]) { S[k]->status = MIQP_STATUS_FAILED_SEG_FAULT; S[k]->has_sol = false; S[k]->rescache.reset(); pool_starts_take(S[k], split != nullptr); S[k]->drop_pool(); } }
   if (split && n != 1) return false;
   BatchShape bs = batch_layout(S, n);
   if (!bs.ok) { for (int k = 0; k < n; ++k) { if (S[k]) S[k]->err = bs.err; statuses[k] = MIQP_STATUS_FAILED_SEG_FAULT; } std::fprintf(stderr, "[miqp_gpu] %s\n", bs.err.c_str()); return false; }
@@ -1663,7 +1707,12 @@ bool solve_batch_impl(miqp_solver_t* const* S, int n, int* statuses, const Split
   std::lock_guard<std::mutex> ctx_lock(X.mu);
   if (hipSetDevice(X.device) != hipSuccess) return fail_all("hipSetDevice failed");
   const CallSwitches sw = read_call_switches();
-  const CallShape sh = plan_call(Y, O0, n, inflight, lanes, split != nullptr, sw);
+  // the root records of the call: today's, plus - when a handle offers starts from its carried pool (records of another length are not offered) - the
+  // largest max_starts SETTING among the handles that do.  The setting, not the number offered: the context is kept only while the root stride stays
+  // (ctx_matches), and a receding horizon carries another number of records every cycle
+  int starts = 0;
+  for (int k = 0; k < n; ++k) { if (S[k]->st_fixlen != Y.fixlen) S[k]->st_offer = 0; if (S[k]->st_offer > 0) starts = std::max(starts, S[k]->pool_starts); }
+  const CallShape sh = plan_call(Y, O0, n, inflight, lanes, split != nullptr, sw, starts);
   const size_t l_ipm = ipm_lds_bytes(Y), l_eval = eval_lds_bytes(Y, sw.seq_kinds);
   CallTimes T;
   {
@@ -1710,6 +1759,7 @@ bool solve_batch_impl(miqp_solver_t* const* S, int n, int* statuses, const Split
   if (split && !split_broadcast(split, L.sp, R)) return fail_all(nullptr);
   report(S, statuses, Y, H, L, R, T, split != nullptr);
   for (int k = 0; k < n; ++k) if (!S[k]->has_sol) S[k]->drop_pool();
+  for (int k = 0; k < n; ++k) if (S[k]->st_n > 0) pool_starts_places(S[k], Y);
   if (sw.stats) std::fprintf(stderr, "[miqp_gpu stats] reachable-set diameter (L1) of instance 0: %.1f\n", H.D[Y.d_misc + 2]);
   if (sw.stats) std::fprintf(stderr, "[miqp_gpu stats] host: setup %.3f s (device context %.3f, instance tables and presolve %.3f, upload %.3f), rounds %.3f s (%d), results %.3f s\n", T.t_setup, T.t_ctx, T.t_tables, T.t_setup - T.t_ctx - T.t_tables, T.t_solve, L.rounds, wall_s() - L.t0 - T.t_solve);
   return !L.abandoned;
@@ -1752,7 +1802,7 @@ void miqp_solver_destroy(miqp_solver_t* s) { delete s; }
 int miqp_solver_set_params(miqp_solver_t* s, const miqp_model_params_c* p) {
   if (!s || !p) return -1;
   s->has_inst = inst_from_params(p, s->opts.precision - 2, s->inst, s->err);
-  s->rescache.reset(); s->drop_fixed_batch(); s->drop_pool();
+  s->rescache.reset(); s->drop_fixed_batch(); s->drop_pool(); s->drop_starts();
   s->has_sol = false;   // MIP starts stay registered (the reference keeps them in the wrapper across resetParameters)
   if (!s->has_inst) std::fprintf(stderr, "[miqp_gpu] %s\n", s->err.c_str());
   return s->has_inst ? 0 : -2;
@@ -1761,7 +1811,7 @@ int miqp_solver_set_params(miqp_solver_t* s, const miqp_model_params_c* p) {
 int miqp_solver_load_dat(miqp_solver_t* s, const char* path) {
   if (!s || !path) return -1;
   s->has_inst = inst_from_dat(path, s->inst, s->err);
-  s->has_sol = false; s->rescache.reset(); s->drop_fixed_batch(); s->drop_pool();
+  s->has_sol = false; s->rescache.reset(); s->drop_fixed_batch(); s->drop_pool(); s->drop_starts();
   if (!s->has_inst) std::fprintf(stderr, "[miqp_gpu] %s\n", s->err.c_str());
   return s->has_inst ? 0 : -2;
 }

@@ -42,8 +42,13 @@
 // wavefront per pair: it sees its own records only, in the single call's order, so a pair's answer is the single call's, bit for bit.  What the
 // single call's host summed over its rounds - launch groups, solves, iterations - the admission sums per pair from the per-record words `solves`
 // and `acc_it`: a pair has at most 32 records, so its launch groups are the rounds in which it had a live record, the largest |solves| among them.
-// Out of scope: obstacle re-numbering; replacing a kept entry by a better carried one of its class (the climb's job); feeding carried records to
-// the SEARCH as MIP starts (that would change solves).
+// Out of scope: obstacle re-numbering; replacing a kept entry by a better carried one of its class (the climb's job).
+//
+// STARTS FROM THE CARRIED POOL (miqp_solver_set_pool_starts, miqp_solver_pool_starts_last).  With the switch on, the solve behind a carry
+// into an empty pool takes the first min(max_starts, entries) carried records as MIP-start roots of round 1 (prepare_instances, miqp_gpu.hip) -
+// that makes the carry the whole counterpart of re-adding the old pool's members as MIP starts.  It is host code only: a pool entry already is a fix
+// record, the start roots are nodes of round 1 like the warm-start roots, and eval_kernel, select_kernel and the capture kernels run as they are.
+// The end of this file holds the setting and the places of the starts in the pool behind the solve.
 #pragma once
 
 namespace {
@@ -402,9 +407,40 @@ bool pool_carry_fits(const PoolCarryPlan& P, const Layout& Y) {
   return P.n0 == 0 || (P.dst->pool_fixlen == Y.fixlen && P.dst->pool_fix.size() >= (size_t)P.n0 * fl && P.dst->pool_obj.size() >= (size_t)P.n0);
 }
 
+// Starts from the carried pool, behind the solve's read-back: st_place[k] is the entry of the pool the solve left that stands for start k - under the
+// handle's filter the entry of the start's plain signature, without one the entry of the same decision bytes -, -1 when the pool holds none
+void pool_starts_places(miqp_solver* s, const Layout& Y) {
+  const size_t fl = (size_t)Y.fixlen, D = (size_t)Y.f_c2n;
+  s->st_place.assign(s->st_n, -1);
+  if (s->pool_n <= 0 || s->pool_fixlen != Y.fixlen || s->st_fixlen != Y.fixlen || s->pool_fix.size() < (size_t)s->pool_n * fl || s->st_fix.size() < (size_t)s->st_n * fl) return;
+  const int fam = s->pool_fam & POOL_FAM_ALL;
+  std::vector<signed char> esig, ssig(fl);
+  if (fam) { esig.resize((size_t)s->pool_n * fl); for (int j = 0; j < s->pool_n; ++j) pool_signature(pool_dims(Y), fam, s->pool_fix.data() + (size_t)j * fl, esig.data() + (size_t)j * fl, fl); }
+  for (int k = 0; k < s->st_n; ++k) {
+    const signed char* const st = s->st_fix.data() + (size_t)k * fl;
+    if (fam) pool_signature(pool_dims(Y), fam, st, ssig.data(), fl);
+    for (int j = 0; j < s->pool_n && s->st_place[k] < 0; ++j)
+      if (fam ? std::memcmp(ssig.data(), esig.data() + (size_t)j * fl, fl) == 0 : std::memcmp(st, s->pool_fix.data() + (size_t)j * fl, D) == 0) s->st_place[k] = j;
+  }
+}
+
 }  // namespace
 
 extern "C" {
+
+int miqp_solver_set_pool_starts(miqp_solver_t* s, int max_starts) {
+  if (!s || max_starts < 0 || max_starts > MIQP_POOL_MAX) return -1;
+  s->pool_starts = max_starts;
+  return 0;
+}
+
+int miqp_solver_get_pool_starts(const miqp_solver_t* s) { return s ? s->pool_starts : -1; }
+
+int miqp_solver_pool_starts_last(const miqp_solver_t* s, int* place, int cap) {
+  if (!s) return -1;
+  for (int k = 0; place && k < s->st_n && k < cap; ++k) place[k] = k < (int)s->st_place.size() ? s->st_place[k] : -1;
+  return s->st_n;
+}
 
 int miqp_gpu_pool_carry_size(void) { return (int)sizeof(miqp_pool_carry_c); }
 

@@ -156,6 +156,9 @@ def load_library():
     L.miqp_solver_pool_carry_multi.restype = C.c_int
     L.miqp_solver_pool_carry_multi.argtypes = [C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_int, C.c_double, C.POINTER(PoolCarryC), C.c_int, C.POINTER(C.c_int)]
     L.miqp_gpu_pool_carry_multi_last.restype = None; L.miqp_gpu_pool_carry_multi_last.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.miqp_solver_set_pool_starts.restype = C.c_int; L.miqp_solver_set_pool_starts.argtypes = [vp, C.c_int]
+    L.miqp_solver_pool_starts_last.restype = C.c_int; L.miqp_solver_pool_starts_last.argtypes = [vp, C.POINTER(C.c_int), C.c_int]
+    L.miqp_solver_get_pool_starts.restype = C.c_int; L.miqp_solver_get_pool_starts.argtypes = [vp]
     if L.miqp_gpu_pool_carry_size() != C.sizeof(PoolCarryC):
         raise RuntimeError("libmiqp_gpu.so and ctypes_types.PoolCarryC disagree on miqp_pool_carry_c (%d / %d bytes): rebuild the library"
                            % (L.miqp_gpu_pool_carry_size(), C.sizeof(PoolCarryC)))
@@ -202,7 +205,8 @@ EXPORTED_SYMBOLS = ["miqp_solver_create", "miqp_solver_destroy", "miqp_solver_se
                     "miqp_solver_settle_decisions", "miqp_solver_pool_explore_settled", "miqp_gpu_pool_settle_passes",
                     "miqp_solver_pool_explore_multi", "miqp_gpu_pool_explore_plan", "miqp_gpu_pool_explore_multi_last",
                     "miqp_gpu_pool_shift", "miqp_solver_pool_carry_maps", "miqp_solver_pool_carry", "miqp_gpu_pool_carry_size", "miqp_gpu_pool_carry_last",
-                    "miqp_solver_pool_carry_multi", "miqp_gpu_pool_carry_multi_last"]
+                    "miqp_solver_pool_carry_multi", "miqp_gpu_pool_carry_multi_last",
+                    "miqp_solver_set_pool_starts", "miqp_solver_pool_starts_last", "miqp_solver_get_pool_starts"]
 
 
 # a row of CplexWrapper.launchPlan (NodeLaunch in csrc/miqp_gpu.hip)
@@ -386,6 +390,9 @@ class CplexWrapper:
         self._keep = None
         self._results = None
         self._warm = None
+        self._starts = 0           # setSolutionPoolStarts
+        self._solved = False       # a solve stands behind the loaded instance
+        self._keep_loaded = False  # the handle's pool is a carried one that the next solve may start from: that solve does not load the parameters again
         self.useSpecialOrderedSets_ = False
         self.useBranchingPriorities_ = False
         self.doWarmstart_ = WarmstartType.NO_WARMSTART
@@ -406,12 +413,15 @@ class CplexWrapper:
     # ---- parameters
     def setParameterDatFileRelative(self, datfile):
         self.datfile_ = "cplexmodel/" + datfile
+        self._keep_loaded = False
 
     def setParameterDatFileAbsolute(self, datfile):
         self.datfile_ = datfile
+        self._keep_loaded = False
 
     def resetParameters(self, parameters: ModelParameters):
         self._params = parameters  # shared with the caller, re-read on every callCplex (cplex_wrapper.cpp:661-664)
+        self._keep_loaded = False  # (new parameters: the next solve loads them, which empties a carried pool)
 
     def overrideSolverSettingsDataSource(self, parameters: ModelParameters):
         if self._params is not None:
@@ -457,7 +467,12 @@ class CplexWrapper:
 
     # ---- solve
     def _push_inputs(self):
-        if self.parameterSource_ == ParameterSource.DATFILE:
+        keep, self._keep_loaded = self._keep_loaded and self._starts > 0, False
+        if keep:
+            # starts from the carried pool (setSolutionPoolStarts): the instance stays the one carrySolutionPool settled its records on - loading
+            # the parameters again would empty the carried pool before the solve can start from it.  resetParameters loads afresh
+            rc = 0
+        elif self.parameterSource_ == ParameterSource.DATFILE:
             rc = self._L.miqp_solver_load_dat(self._h, self.datfile_.encode())
         elif self.parameterSource_ == ParameterSource.MIXED and self._params is None:
             rc = self._L.miqp_solver_load_dat(self._h, self.datfile_.encode())   # MIXED: the C++ inputs when given, else the file
@@ -468,6 +483,8 @@ class CplexWrapper:
             rc = self._L.miqp_solver_set_params(self._h, C.byref(s))
         if rc != 0:
             return rc
+        if not keep:
+            self._solved = False
         # MIP starts (src/cplex_wrapper.cpp:121-138): the receding-horizon start and, independently of it, the .mst
         # file of the last solution - with BOTH_WARMSTART_STRATEGIES the reference applies both
         self._L.miqp_solver_set_warmstart(self._h, None, int(WarmstartType.NO_WARMSTART))
@@ -508,6 +525,7 @@ class CplexWrapper:
     def _collect(self, status, lazy=False):
         """takes the result record over from the library; lazy (batch entry points): on the first getRawResults()"""
         self._stale = status == OptimizationStatus.SUCCESS
+        self._solved, self._keep_loaded = True, False
         if not self._stale:
             return OptimizationStatus(status)
         if not lazy:
@@ -815,7 +833,43 @@ class CplexWrapper:
         rc = int(self._L.miqp_solver_pool_carry(self._h, src._h, int(shift), float(max_rel), out, n))
         if rc < 0:
             return rc, []
+        self._carried_into(rc)
         return rc, [dict(status=o.status, place=o.place, solves=o.solves, iterations=o.iterations, objective=float(o.objective)) for o in out[:ns] if o.status >= 0]
+
+    def _carried_into(self, added):
+        """behind a carry: a pool without a solve behind it is one the next solve may start from (setSolutionPoolStarts)"""
+        if added > 0 and not self._solved:
+            self._keep_loaded = True
+
+    def setSolutionPoolStarts(self, max_starts):
+        """the next solves of this wrapper START THEIR SEARCH from the carried manoeuvres (miqp_solver_set_pool_starts; for a CPLEX user: the old
+        pool's members re-added as MIP starts): a solve behind carrySolutionPool into this wrapper's EMPTY pool - parameters loaded, capacity
+        and filter set, no solve yet - takes the first min(max_starts, entries) carried records as additional roots of its first round.  A
+        feasible one is the first incumbent, and the capture merges every feasible start into the pool of the solve, so the fallback that was
+        carried in survives the solve.  0: off, the default; at most pool_max().  Returns the library's code: 0, -1 when the value is refused
+        (the previous setting stays).  The order is resetParameters, carrySolutionPool, callCplex (or solve_batch): with the setting on, that solve
+        keeps the instance the carry settled its records on instead of loading the parameters again - which would empty the carried pool;
+        resetParameters in between loads afresh and so drops the carried pool.  THAT ONE SOLVE THEREFORE DOES NOT RE-READ THE SHARED
+        ModelParameters: an in-place edit of them between the carry and the solve, overrideSolverSettingsDataSource (gap, time limit)
+        included, takes effect from the next load on - make such edits before carrySolutionPool, or call resetParameters and give up the
+        starts.  A tree-split solve ignores the setting."""
+        rc = int(self._L.miqp_solver_set_pool_starts(self._h, int(max_starts)))
+        if rc == 0:
+            self._starts = int(max_starts)
+        return rc
+
+    def solutionPoolStarts(self):
+        """the setting of setSolutionPoolStarts as the library holds it (miqp_solver_get_pool_starts)"""
+        return int(self._L.miqp_solver_get_pool_starts(self._h))
+
+    def solutionPoolStartsLast(self):
+        """the places of the start roots the last solve took from the carried pool (miqp_solver_pool_starts_last): one int per start, the entry of
+        the pool after that solve that stands for the start - the entry of its signature under this wrapper's filter, without a filter the entry
+        of the same decision bytes - or -1 when the pool holds none.  [] when the solve took no starts; needs no device"""
+        n = pool_max()
+        place = (C.c_int * n)()
+        t = int(self._L.miqp_solver_pool_starts_last(self._h, place, n))
+        return [int(place[k]) for k in range(max(0, min(t, n)))]
 
     def solveDecisions(self, decisions):
         """the continuous QPs of many DECISION records of this wrapper's instance in one device call (miqp_solver_solve_decisions): ``decisions`` is
@@ -1178,6 +1232,8 @@ def carry_solution_pools(dsts, srcs, shift=1, max_rel=-1.0):
     if rc < 0:
         why = next((w.lastError() for w in dsts if w.lastError()), "") if rc == -2 else ""   # (a pair the single call refuses is named in ITS destination's last error)
         raise RuntimeError("miqp_solver_pool_carry_multi failed (%d)%s" % (rc, ": " + why if why else ""))
+    for p in range(n):
+        dsts[p]._carried_into(int(counts[p]))
     return [(int(counts[p]), [dict(status=o.status, place=o.place, solves=o.solves, iterations=o.iterations, objective=float(o.objective))
                               for o in out[p * cap:p * cap + ns[p]] if o.status >= 0]) for p in range(n)]
 
