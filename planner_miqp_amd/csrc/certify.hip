@@ -1,7 +1,7 @@
 // certify.hip - a-posteriori certificate of delivered records against the raw big-M model (miqp_solver_certify, _certify_batch).
 //
 // What is evaluated is the materialised RawResults record the caller holds, not the incumbent of the branch and bound: the
-// rows of cplexmodel/*.mod are generated on the fly (certify_rows.hpp, the order and constants of lp_export.hpp) from a
+// rows of cplexmodel/*.mod are generated on the fly (the row walker of raw_model.hpp, which also writes the .lp) from a
 // compact parameter block of the host instance, one workgroup of 256 threads per record.  Included by miqp_gpu.hip.
 //
 // Kernel layout: the twelve continuous arrays of the record are staged in LDS once (12 x C x N doubles; a chunk with a
@@ -14,7 +14,7 @@
 // kernel of the previous chunk runs on another; two staging and two device buffers of at most CERT_CHUNK_BYTES each, cached
 // per device and never taken from the solver's pools.  The call holds the device lock of a solve and touches no solver context.
 #pragma once
-#include "certify_rows.hpp"
+#include "raw_model.hpp"
 
 namespace {
 
@@ -54,7 +54,8 @@ __global__ __launch_bounds__(CERT_NT) void certify_kernel(const char* __restrict
 #pragma unroll
   for (int f = 0; f < 8; ++f) {
     CertMax m{0.0, -1};
-    cert_family(f, V, tid, CERT_NT, m);
+    RawEval ev{V, m, 0.0, 0};
+    raw_family(f, V, tid, CERT_NT, ev);
     double v = m.v; unsigned row = (unsigned)m.row;
     cert_wave_max(v, row);
     if (lane == 0) { s_v[wave] = v; s_r[wave] = row; }
@@ -164,7 +165,7 @@ bool certify_jobs(int device, const std::vector<CertJob>& jobs, miqp_certificate
     }
     const int nth = std::max(1, std::min({16, (int)std::thread::hardware_concurrency(), cnt / 32}));
     std::atomic<int> next{0};
-    auto work = [&] { for (int k = next.fetch_add(1); k < cnt; k = next.fetch_add(1)) cert_pack(*jobs[k0 + k].I, *jobs[k0 + k].r, H + off[k]); };
+    auto work = [&] { for (int k = next.fetch_add(1); k < cnt; k = next.fetch_add(1)) { cert_pack_params(*jobs[k0 + k].I, H + off[k]); cert_pack_record(*jobs[k0 + k].I, *jobs[k0 + k].r, H + off[k]); } };
     if (nth <= 1) work();
     else { std::vector<std::thread> th; for (int t = 0; t < nth; ++t) th.emplace_back(work); for (auto& t : th) t.join(); }
     pack_s += wall_s() - t0;

@@ -189,15 +189,12 @@ void raw_sizes(const HostInst& I, int& rows, int& bin, int& cont, int& nnz_out) 
   }
   nnz += 35 * R * (N - 1) * C;                  // A5 minimum_speed_constraints.mod:9-49
   long env_edges = E > 0 ? I.env_off[E] : 0;
-  long r = C * (17 + 5 * R) + 6 * (N - 1) * C + 12 * N * C + (N - 1) * a4 + 15 * R * (N - 1) * C;
   if (E > 0) {                                  // A6 obstacle_environment_constraints.mod:6-47
-    r += N * C * (5 * env_edges + 5);
     long per = 5 * E;
     for (long k = 0; k < env_edges; ++k) { const double* e = &I.env_edges[(size_t)k * 4]; per += 5 * (1 + nz(e[2] - e[0]) + nz(e[3] - e[1])); }
     nnz += N * C * per;
   }
   if (O > 0) {                                  // A7 :52-109
-    r += N * C * O * (5 * L + 5);
     for (int o = 0; o < O; ++o) for (int i = 0; i < N; ++i) {
       long per = 5 * (L + (I.obs_soft[o] == 1 ? 1 : 0));
       for (int k = 0; k < L; ++k) { const double* e = &I.obs_edges[((size_t)(o * N + i) * L + k) * 4]; per += 5 * (1 + nz(e[2] - e[0]) + nz(e[3] - e[1])); }
@@ -206,10 +203,10 @@ void raw_sizes(const HostInst& I, int& rows, int& bin, int& cont, int& nnz_out) 
   }
   if (C > 1) {                                  // A8 agent_collision_constraints.mod:10-73
     long tri = 0; for (long c1 = 2; c1 <= K; ++c1) tri += c1 - 1;
-    r += N * 20 * tri + 24 * N * C * (C - 1) / 2;
     nnz += N * 20 * tri + 76 * N * C * (C - 1) / 2;
   }
-  rows = (int)r; nnz_out = (int)nnz;
+  int base[9]; miqp::raw_row_bases(I.C, I.N, I.R, I.E, I.O, I.L, (int)env_edges, (int)a4, base);   // the rows: the walker's own count
+  rows = base[8]; nnz_out = (int)nnz;
 }
 
 // ---------------------------------------------------------------- host geometry helpers (results, step-1 presolve)

@@ -390,3 +390,69 @@ def node_instance(oracle, name):
         _INCUMBENTS[name] = (p, h, dims, canonical_record(res))
     return _INCUMBENTS[name]
 
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the exported .lp (miqp_solver_export_lp): the instances whose files are pinned by tests/golden/lp_sha256.json, and a reader of its rows
+LP_CASES = ["dat:cplexmodel_testcase.dat", "dat:test_sos.dat", "dat:cplexmodel.dat", "mini:0", "mini1soft:0", "mini3:0", "mini4:0",
+            "cfg3:0", "cfg3:1", "cfg4:0", "cfg4:1", "4x10x64x2x0:0"]
+
+
+def lp_case_params(case):
+    """ModelParameters of a synthetic LP_CASES entry: 'config:seed', 'mini1soft' is mini1 with its obstacle soft, 'AxBx...' a shape tuple"""
+    from planner_miqp_amd import synthetic
+    cfg, seed = case.split(":")
+    p = synthetic.generate("mini1" if cfg == "mini1soft" else tuple(int(x) for x in cfg.split("x")) if "x" in cfg else cfg, int(seed))
+    if cfg == "mini1soft":
+        p.obstacle_is_soft = [1]
+    return p
+
+
+def lp_case_wrapper(case):
+    """a handle with the inputs of an LP_CASES entry pushed (nothing is solved)"""
+    import planner_miqp_amd as P
+    if case.startswith("dat:"):
+        w = P.CplexWrapper(parameterSource=P.ParameterSource.DATFILE)
+        w.setParameterDatFileAbsolute(dat_path(case[4:]))
+    else:
+        w = P.CplexWrapper()
+        w.resetParameters(lp_case_params(case))
+    assert w._push_inputs() == 0, case
+    return w
+
+
+def parse_lp_rows(text):
+    """[(terms, sense, rhs)] of the `Subject To` section of an exported .lp, row c<k> at index k - 1; terms: [(coefficient, name)]"""
+    body = text.split("Subject To\n", 1)[1].split("Bounds\n", 1)[0]
+    rows = []
+    for k, line in enumerate(body.splitlines()):
+        head, rest = line.split(":", 1)
+        assert head == " c%d" % (k + 1), line
+        t = rest.split()
+        assert len(t) % 2 == 0 and t[-2] in ("<=", ">=", "="), line
+        rows.append(([(float(t[q]), t[q + 1]) for q in range(0, len(t) - 2, 2)], t[-2], float(t[-1])))
+    return rows
+
+
+def lp_row_value(row, values):
+    """(lhs, sum |coefficient * value|) of a parsed row on {name: value}"""
+    prods = [c * values[n] for c, n in row[0]]
+    return sum(prods), sum(abs(x) for x in prods)
+
+
+def lp_row_violation(row, values, lhs=None):
+    """violation of a parsed row on {name: value}, or of a given lhs: lhs - rhs for <=, rhs - lhs for >=, |lhs - rhs| for ="""
+    if lhs is None:
+        lhs = lp_row_value(row, values)[0]
+    return {"<=": lhs - row[2], ">=": row[2] - lhs, "=": abs(lhs - row[2])}[row[1]]
+
+
+def record_values(rec, use_real_slack=True):
+    """{name in the .lp: value} of a RawResults record; the car/car slacks are its real values or its ints, as for certify()"""
+    from planner_miqp_amd.ctypes_types import _RES_D, _RES_I
+    out = {}
+    for n in list(_RES_D) + list(_RES_I):
+        a = rec.slackvars_real if (n == "slackvars" and use_real_slack) else getattr(rec, n)
+        for idx, v in np.ndenumerate(a):
+            out[n + "".join("#%d" % (q + 1) for q in idx)] = float(v)
+    return out

@@ -44,7 +44,7 @@ def main():
         certs = P.certify_batch(ws)
         t_cert = time.time() - t
         tm = P.certify_last_timing()
-        print("certify call %d: %.4f s wall = %.1f %% of the stream (packing %.4f s, upload %.4f s, kernel %.4f s; %.2f us kernel per record)"
+        print("certify call %d: %.4f s wall = %.1f %% of the stream (packing %.6f s, upload %.6f s, kernel %.6f s; %.3f us kernel per record)"
               % (rep, t_cert, 100.0 * t_cert / max(t_stream, 1e-9), tm["pack_s"], tm["upload_s"], tm["kernel_s"], 1e6 * tm["kernel_s"] / max(1, solved)))
     ok = [(c.max_violation, k) for k, c in enumerate(certs) if c.status == 0]
     print("certificates: %d evaluated, %d without a solution, %d rows each" % (len(ok), len(certs) - len(ok), certs[ok[0][1]].rows if ok else -1))
